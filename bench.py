@@ -10,9 +10,13 @@ A *step* is one pass of the fused encode kernel (RGB -> XYZ -> Lu'v' -> PQ quant
 = LumaEncoder::encode minus the VP9 stage) over one batch of `--frames-per-step` synthetic 3840x2160 frames that
 are already resident in HBM.  The resident stream is BASELINE.json configs[1]'s 500 frames (25 batches of 20;
 fewer when memory is short); steps walk it cyclically, so every step reads 2 GB that the previous ~24 steps evicted
-from L2 / Infinity Cache.  W warm-up steps, then EXACTLY K steps between barrier + synchronize, MAX over ranks.  That
-K-step region is repeated until >= --min-seconds of device time has been spent (sustained clocks, not a burst);
-`ms_per_step` / `value` are the MEDIAN region, min / max are reported next to it.  Rank 0 prints ONE JSON line.
+from L2 / Infinity Cache.  W warm-up steps, then EXACTLY K steps between barrier + synchronize, MAX over ranks: ONE region,
+`ms_per_step` = its wall time / K, `value` = the pixels of its K steps per second.  Rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, write `--dump-outputs DIR` if given, print the line.
+`--full` adds everything below (each leg in K-step regions repeated until >= --min-seconds of device time, median region).
+`--dump-outputs DIR` writes, after the timed steps, the Y / U / V planes the last timed step computed as DIR/<name>.npy
+(float32, a fixed seeded sample of each plane: lumahdrv_amd/benchlib/outputs.py); the inputs are a function of the arguments.
 
 Multi-GPU: frames are independent, so rank r owns its own block of frame indices (weak scaling, no data-path
 collective); the only communication is one RCCL broadcast of the transfer-function table and the quantizer
@@ -23,10 +27,10 @@ plane digests all_gathered in stream order and spot-checked by rank 0.
 The K launches of a region are independent batches, so they run inside ONE unordered section of the C ABI
 (lumahip_begin_unordered ... lumahip_end_unordered, `--lanes`, default 2: successive batches alternate between two
 internal streams, so one batch's ramp-up and tail overlap its neighbours' steady state).  The hipEvent pair brackets the
-whole section on the context's stream; `kernel_ms` = that window / K.  `--lanes 0` (and the `*_ordered` fields of the default
+whole section on the context's stream; `kernel_ms` = that window / K.  `--lanes 0` (and the `*_ordered` fields of a --full
 run) is the same K launches back to back on one stream.
 
-Extra fields in the same line (not part of `value`): decode (its own `decode_roofline` block with a decode-shaped
+Extra fields of `--full` (not part of `value`): decode (its own `decode_roofline` block with a decode-shaped
 traffic-only probe) and encode+decode round trip, the roofline of the encode kernel (HIP events on the launch stream, live),
 `value_placement_off` (the same kernels on plainly allocated buffers), `other_workloads` (BASELINE configs[2] HDR10/YCbCr at
 4K and configs[3] LOG-12 at 7680x4320, each with its own roofline block and its decode rate; N = 1 only), `facade_hostfed`
@@ -54,6 +58,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from lumahdrv_amd.benchlib.legs import load_profile, run_workload  # noqa: E402,F401
+from lumahdrv_amd.benchlib.outputs import write_outputs  # noqa: E402
 from lumahdrv_amd.benchlib.plan import (H4K, OTHER_WORKLOADS, SEED, W4K, config_block, plan_only, pool_request,  # noqa: E402,F401
                                         stream_shard_plan)
 from lumahdrv_amd.benchlib.resident import StreamDoesNotFit, make_pool, make_small_pool  # noqa: E402
@@ -64,14 +69,23 @@ from lumahdrv_amd.benchlib.timing import Timer, ranks_seen  # noqa: E402,F401
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=25, help="steps per timed region (default 25 = one pass over the 500-frame stream)")
+    ap.add_argument("--steps", type=int, default=25,
+                    help="timed steps of the headline (default 25 = one pass over the 500-frame stream); steps per region of the other legs")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything else the line can carry: decode, round trip, packed-layout decode, ordered and roofline figures, "
+                         "placement-off and small-pool legs, the other BASELINE workloads, the host-fed facade and the CPU baseline "
+                         "(default: the headline encode only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the Y / U / V planes the last timed step computed (a fixed, seeded sample of "
+                         "each, float32) as DIR/<name>.npy")
     ap.add_argument("--frames-per-step", type=int, default=20)
     ap.add_argument("--width", type=int, default=W4K)
     ap.add_argument("--height", type=int, default=H4K)
     ap.add_argument("--workload", default="pq11_luv", choices=["pq11_luv", "pq10_ycbcr", "log12_luv"])
     ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="repeat the K-step timed region until this much device time has been measured (per leg)")
+                    help="repeat the K-step timed region until this much device time has been measured (per leg of --full and of "
+                         "--stream-frames; the headline is always ONE region of exactly --steps steps)")
     ap.add_argument("--max-repeats", type=int, default=400)
     ap.add_argument("--stream-frames", type=int, default=0,
                     help="BASELINE configs[4] mode: ONE stream of this many frames (2000) block-sharded over the ranks")
@@ -214,6 +228,9 @@ def main():
     args = parse()
     if args.plan_only:
         raise SystemExit(plan_only(args))
+    if args.dump_outputs and args.stream_frames > 0:
+        raise SystemExit("bench.py: --dump-outputs writes the headline's outputs; the --stream-frames mode reports per-frame digests "
+                         "(--dump-digests)")
     multi_driver = args.stream_frames > 0 and args.driver == "multi"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not multi_driver:
         respawn(args)
@@ -266,14 +283,18 @@ def main():
 
     try:
         if args.stream_frames > 0:
-            res = run_stream(L, args, rank, n_gpus, local_rank, use_dist, dev)
+            res, outputs = run_stream(L, args, rank, n_gpus, local_rank, use_dist, dev), None
         else:
-            res = run_default(L, args, config, rank, n_gpus, local_rank, use_dist, dev, sha)
+            res, outputs = run_default(L, args, config, rank, n_gpus, local_rank, use_dist, dev, sha)
     except StreamDoesNotFit as e:
         sys.stderr.write("bench.py: %s\n" % (e,))
         os._exit(EXIT_DOES_NOT_FIT)        # (no JSON line; os._exit: peers blocked in a collective must not keep this rank alive)
     res["rccl_ranks_seen"] = rccl_ranks_seen
     res["kernel_source_sha"] = sha
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, outputs)
+        res["outputs_dumped"] = {"dir": args.dump_outputs, "files": sorted(k + ".npy" for k in outputs),
+                                 "what": "Y / U / V codes of the batch the last timed step encoded (seeded sample, float32)"}
 
     if rank == 0:
         os.write(real_stdout, (json.dumps(res) + "\n").encode())
@@ -283,12 +304,17 @@ def main():
 
 
 def run_default(L, args, config, rank, n_gpus, local_rank, use_dist, dev, sha):
-    """the default line: the headline workload on every rank (weak scaling) + at N = 1 the other single-GPU configurations"""
+    """the default line: the headline workload on every rank (weak scaling); with --full also its other legs, the roofline
+    blocks and at N = 1 the other single-GPU configurations"""
     w, h, B, K, Wm = args.width, args.height, args.frames_per_step, args.steps, args.warmup
+    full = args.full
     # the host-fed leg first: its own process on a GPU this process has not allocated anything on yet (facade_hostfed says why)
-    hostfed = facade_hostfed(w, h) if (rank == 0 and n_gpus == 1 and not args.no_facade_hostfed) else None
-    pool = make_pool(L, args, dev, local_rank, w, h, B)
-    r, cfg = run_workload(L, args, args.workload, w, h, B, K, Wm, rank, n_gpus, local_rank, use_dist, dev, True, sha, pool)
+    hostfed = facade_hostfed(w, h) if (full and rank == 0 and n_gpus == 1 and not args.no_facade_hostfed) else None
+    # (a plain run keeps no decoded output: the pool's fastest float chunks still hold the input, as in the --full run)
+    pool = make_pool(L, args, dev, local_rank, w, h, B, with_output=full)
+    r, cfg = run_workload(L, args, args.workload, w, h, B, K, Wm, rank, n_gpus, local_rank, use_dist, dev, True, sha, pool,
+                          legs="full" if full else "headline", dump=bool(args.dump_outputs) and rank == 0)
+    outputs = r.pop("outputs")
     config = dict(config, world_size_reported_by="torch.distributed (RCCL)" if use_dist else "single process")
     degraded = bool(r["config_degraded"])
     if degraded:     # --allow-short-stream and short memory: say what actually ran, and say that it is not the configuration asked for
@@ -306,7 +332,14 @@ def run_default(L, args, config, rank, n_gpus, local_rank, use_dist, dev, sha):
         "config": config, "config_degraded": degraded,
         "repeats": r["repeats"], "timed_seconds": r["timed_seconds"],
         "ms_per_step_min": r["ms_per_step_min"], "ms_per_step_max": r["ms_per_step_max"],
-        "ms_per_step_over_ranks": r["ms_per_step_over_ranks"], "lanes": r["lanes"],
+        "ms_per_step_over_ranks": r["ms_per_step_over_ranks"], "lanes": r["lanes"], "full": full,
+        "placement": dict({"mode": args.placement, "resident_stream": r["resident_stream"]}, **(pool.stats if pool is not None else {})),
+    }
+    if not full:
+        if pool is not None:
+            pool.close()
+        return res, outputs
+    res.update({
         "value_ordered": r.get("value_ordered"), "decode_mpix_s_ordered": r.get("decode_mpix_s_ordered"),
         "decode_mpix_s": r["decode_mpix_s"], "decode_output_layout": r["decode_output_layout"],
         "roundtrip_mpix_s": r["roundtrip_mpix_s"],
@@ -315,8 +348,7 @@ def run_default(L, args, config, rank, n_gpus, local_rank, use_dist, dev, sha):
         # (lumahip_decoded_ring_*: the frames of a batch rotating over three region groups), two launches in flight / ordered
         "decode_packed_mpix_s": ((r.get("decode_packed_layout") or {}).get("library_ring") or {}).get("value"),
         "decode_packed_frac": ((r.get("decode_packed_layout") or {}).get("library_ring") or {}).get("frac_ordered"),
-        "placement": dict({"mode": args.placement, "resident_stream": r["resident_stream"]}, **(pool.stats if pool is not None else {})),
-    }
+    })
     if rank == 0:
         res["roofline"] = r["roofline"]
         res["decode_roofline"] = r["decode_roofline"]
@@ -356,7 +388,7 @@ def run_default(L, args, config, rank, n_gpus, local_rank, use_dist, dev, sha):
         res["facade_hostfed"] = hostfed
     if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args, cfg, w, h)
-    return res
+    return res, outputs
 
 
 if __name__ == "__main__":

@@ -11,6 +11,7 @@ import torch
 from .plan import BYTES_PER_PIXEL, READ_BYTES_PER_PIXEL, CLOCK_GHZ, HBM_PEAK_GBS, N_SIMD, PACKED_RING, SEED, WORKLOADS, resident_frames, workload_text
 from lumahdrv_amd.placement import CHUNK_BYTES
 
+from .outputs import plane_samples
 from .resident import ResidentStream
 from .timing import Timer
 
@@ -28,10 +29,14 @@ def load_profile(path, workload, px_step, sha):
     return None
 
 
-def run_workload(L, args, name, w, h, B, K, Wm, rank, world, local_rank, use_dist, dev, main, sha, pool=None, legs="full", nbatch=None):
+def run_workload(L, args, name, w, h, B, K, Wm, rank, world, local_rank, use_dist, dev, main, sha, pool=None, legs="full", nbatch=None,
+                 dump=False):
     """one workload: resident synthetic stream, encode timed (plus decode / round trip for the main one), roofline blocks.
-    legs: "full" = every leg; "encode" = the encode leg only, two lanes and ordered (the placement-off and small-pool comparisons).
-    nbatch: batches of the resident stream when it is not the plan's (the small-pool leg: 2)."""
+    legs: "full" = every leg; "encode" = the encode leg only, two lanes and ordered (the placement-off and small-pool comparisons);
+    "headline" = the encode leg only, as timed (the plain bench run).
+    main: the headline workload -- its encode leg is ONE region of exactly K steps after the W warm-up steps.
+    nbatch: batches of the resident stream when it is not the plan's (the small-pool leg: 2).
+    dump: r["outputs"] = samples of the planes the last timed step wrote (benchlib/outputs.py), taken before any other leg."""
     from lumahdrv_amd.sharding import broadcast_quantizer
     ptf, bits, cs, bitsC, maxLum, minLum, sc, profile, desc, xf_desc, kname = WORKLOADS[name]
     cfg0 = lut0 = None
@@ -71,7 +76,14 @@ def run_workload(L, args, name, w, h, B, K, Wm, rank, world, local_rank, use_dis
     lanes = max(0, args.lanes)
     tm = Timer(K, Wm, use_dist, dev, args.min_seconds, args.max_repeats, ctx, lanes)
     px_step = float(B) * w * h
-    te = tm.run(enc)
+    te = tm.run(enc, min_seconds=0 if main else None)
+    outputs = None
+    if dump:                                               # the last timed step was step Wm + K - 1 (timing.py: one region)
+        outputs = plane_samples(ptrs((Wm + K - 1) % nbatch)[2], B, w, h, profile, dev)
+    if legs == "full" and Wm + K < nbatch:
+        for b in range(Wm + K, nbatch):                    # the decode legs read every batch's planes: encode the ones the timed
+            enc(b)                                         # steps did not reach (untimed)
+        torch.cuda.synchronize()
 
     def rate(t):
         return world * K * px_step / t / 1e6
@@ -87,7 +99,11 @@ def run_workload(L, args, name, w, h, B, K, Wm, rank, world, local_rank, use_dis
          "workload": workload_text(name, w, h, B, nfr), "resident_frames": nfr, "config_degraded": rs.degraded,
          "resident_stream": rs.placement_report(),
          "frames_per_step": B, "width": w, "height": h, "preScaling": sc, "profile": profile,
-         "distinct_input_GB_per_gpu": round(nfr * n3 * 4 / 1e9, 2)}
+         "distinct_input_GB_per_gpu": round(nfr * n3 * 4 / 1e9, 2), "outputs": outputs}
+    if legs == "headline":
+        ctx.close()
+        rs.close()
+        return r, cfg
     if legs == "encode":
         if lanes:
             r["value_ordered"] = round(rate(tm.run(enc, lanes=0)["wall_median"]), 1)   # the same launches back to back on one stream

@@ -115,9 +115,9 @@ def config_block(args, n_gpus):
     frames = resident_frames(w, h, B, True)
     return {"resident_frames": frames, "stream_frames": frames * n_gpus, "resident_frames_per_rank": [frames] * n_gpus,
             "workload": workload_text(name, w, h, B, frames),
-            "timed": "the quantize (encode) pass: K steps per region, region repeated until >= %.1f s of device time; "
-                     "value / ms_per_step = the median region; decode and encode+decode round trip are timed "
-                     "the same way and reported as decode_mpix_s / roundtrip_mpix_s" % args.min_seconds,
+            "timed": "the quantize (encode) pass: W warm-up steps, then ONE region of exactly K steps; value / ms_per_step = "
+                     "that region; with --full, decode and encode+decode round trip are timed in K-step regions repeated until "
+                     ">= %.1f s of device time and reported as decode_mpix_s / roundtrip_mpix_s" % args.min_seconds,
             "frames_per_step": B, "width": w, "height": h, "preScaling": sc, "profile": profile,
             "parallelism": "frame-sharded x%d" % n_gpus, "scaling": "weak",
             "distinct_input_GB_per_gpu": round(frames * n3 * 4 / 1e9, 2)}

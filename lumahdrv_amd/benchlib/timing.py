@@ -60,8 +60,10 @@ class Timer:
             dist.barrier()
         return wall, (e0.elapsed_time(e1) if self.cuda else 1e3 * wall)
 
-    def run(self, fn, lanes=None):
+    def run(self, fn, lanes=None, min_seconds=None):
+        """min_seconds=0: ONE region of exactly K steps (the headline of bench.py); None: the Timer's own min_seconds"""
         lanes = self.lanes if lanes is None else lanes
+        min_seconds = self.min_seconds if min_seconds is None else min_seconds
         # warm-up in the mode that is timed: the lane streams of an unordered section are created, and get their first launch, here
         # (the first launch of a large-LDS kernel on a fresh stream has been seen to take seconds, once)
         if lanes and self.Wm > 0:
@@ -70,6 +72,13 @@ class Timer:
             fn(i)
         if lanes and self.Wm > 0:
             self.ctx.end_unordered()
+        if self.cuda:
+            # the runtime sets up its timing events on the first one a process records: that one-time cost is not a step's
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            b.record()
+            b.synchronize()
+            a.elapsed_time(b)
         walls, devs = [], []
         step = self.Wm
         while True:
@@ -78,7 +87,7 @@ class Timer:
             walls.append(wall)
             devs.append(dev_ms)
             # every rank must take the same decision: rank 0 decides
-            more = torch.tensor([1 if (sum(devs) * 1e-3 < self.min_seconds and len(devs) < self.max_repeats) else 0],
+            more = torch.tensor([1 if (sum(devs) * 1e-3 < min_seconds and len(devs) < self.max_repeats) else 0],
                                 dtype=torch.int32, device=self.dev)
             if self.use_dist:
                 dist.broadcast(more, src=0)

@@ -169,7 +169,40 @@ def main():
     np.savez_compressed(os.path.join(OUT, "ref_transform.npz"), **tr)
     for fn in ("ref_luts.npz", "ref_quantize.npz", "ref_transform.npz", "ref_planes.npz", "ref_plane_digests.json"):
         print(fn, os.path.getsize(os.path.join(OUT, fn)), "bytes")
+    write_live_fixture()
+    write_argparser_fixture()
+
+
+def write_argparser_fixture():
+    """ref_argparser.json: [command line, answer of the reference's ArgParser (oracle/_ref/ref_argparser_tool)] for every line of
+    tests/test_host_side.py's option-handling check"""
+    import json
+    import subprocess
+    from tests.test_host_side import argparser_lines
+    tool = os.path.join(ROOT, "oracle", "_ref", "ref_argparser_tool")
+    rec = [[a, subprocess.run([tool] + a, capture_output=True, text=True, timeout=30).stdout.strip()] for a in argparser_lines()]
+    fn = os.path.join(OUT, "ref_argparser.json")
+    with open(fn, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r) for r in rec) + "\n]\n")
+    print("ref_argparser.json", os.path.getsize(fn), "bytes")
+
+
+def write_live_fixture():
+    """ref_live_<check>.npz: the reference's results, call by call, in the live checks of tests/test_oracle_golden.py (recorded
+    while they run against it, so the oracle's side is checked on the way)"""
+    from tests import test_oracle_golden as t
+    assert o.have_ref() and o.have_ref_planes()
+    for check in (t.check_random_frames, t.check_extreme_inputs, t.check_whole_frame_encode, t.check_plane_loops):
+        tape = t.Tape()
+        check(o, tape)
+        fn = os.path.join(OUT, "ref_live_%s.npz" % check.__name__)
+        t.save_tape(check.__name__, tape, fn)
+        print(os.path.basename(fn), os.path.getsize(fn), "bytes")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--live-only"]:
+        write_live_fixture()
+        write_argparser_fixture()
+    else:
+        main()

@@ -254,17 +254,8 @@ def test_decoder_base_class_usage_compiles_against_both_trees():
                     "-I" + os.path.join(ref, "lib", "matroska"), "-I" + os.path.join(vpx, "vpx"), "-I" + vpx, src], check=True)
 
 
-def test_lumaenc_option_handling_equals_the_reference_parser(tmp_path):
-    """tools/lumaenc's option handling (tools/luma_cli.h) against the reference's own ArgParser (src/arg_parser.cpp compiled
-    unmodified behind lumaenc's option table: oracle/_ref/ref_argparser_tool, build container only) on the same command
-    lines: same accept / reject decision, same message, same parsed values -- atoi / atof conversions, range and
-    value-set checks, repeated options, missing values, help."""
-    tool = os.path.join(ROOT, "oracle", "_ref", "ref_argparser_tool")
-    if not os.path.exists(tool):
-        if not os.path.isdir("/root/reference/src"):
-            pytest.skip("needs /root/reference")
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref_args"], check=True)
-    enc = os.path.join(ROOT, "lumahdrv_amd", "bin", "lumaenc")
+def argparser_lines():
+    """the command lines of the option-handling check: fixed ones, then random numeric options with values around their limits"""
     rng = np.random.default_rng(12)
     lines = [
         ["-o", "a.lhs"], ["--output", "a.lhs", "-i", "__test__", "-f", "1:2:9"], ["-o", "a.lhs", "-p", "0", "-q", "63", "-sc", "2.5e3"],
@@ -278,7 +269,7 @@ def test_lumaenc_option_handling_equals_the_reference_parser(tmp_path):
     names = [("-p", "--profile"), ("-q", "--quantizer-scaling"), ("-pb", "--ptf-bitdepth"), ("-cb", "--color-bitdepth"), ("-b", "--bitrate"),
              ("-k", "--keyframe-interval"), ("-eb", "--encoding-bitdepth"), ("-sc", "--pre-scaling"), ("-ma", "--max-luminance"),
              ("-mi", "--min-luminance"), ("-fps", "--framerate")]
-    for _ in range(150):                                     # random numeric options with values around their limits
+    for _ in range(150):
         args = ["-o", "r.lhs"]
         for _ in range(int(rng.integers(1, 5))):
             short, long_ = names[int(rng.integers(0, len(names)))]
@@ -286,8 +277,24 @@ def test_lumaenc_option_handling_equals_the_reference_parser(tmp_path):
                             "99.99", "100.5", "1e5", "100001", "0.5", "-3", "x"])
             args += [short if rng.random() < 0.5 else long_, str(v)]
         lines.append(args)
-    for args in lines:
-        ref = subprocess.run([tool] + args, capture_output=True, text=True, timeout=30).stdout.strip()
+    return lines
+
+
+def test_lumaenc_option_handling_equals_the_reference_parser(tmp_path):
+    """tools/lumaenc's option handling (tools/luma_cli.h) against the reference's own ArgParser (src/arg_parser.cpp compiled
+    unmodified behind lumaenc's option table: oracle/_ref/ref_argparser_tool) on the same command lines: same accept / reject
+    decision, same message, same parsed values -- atoi / atof conversions, range and value-set checks, repeated options,
+    missing values, help.  The parser's answers are recorded in tests/golden/ref_argparser.json (tests/golden/make_golden.py);
+    where oracle/_ref/ is built the parser also runs live and must give the recorded answers."""
+    import json
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_argparser.json")))
+    assert [a for a, _ in rec] == argparser_lines()
+    tool = os.path.join(ROOT, "oracle", "_ref", "ref_argparser_tool")
+    live = os.path.exists(tool)
+    enc = os.path.join(ROOT, "lumahdrv_amd", "bin", "lumaenc")
+    for args, ref in rec:
+        if live:
+            assert subprocess.run([tool] + args, capture_output=True, text=True, timeout=30).stdout.strip() == ref, args
         r = subprocess.run([enc] + args, capture_output=True, text=True, timeout=30, env=dict(os.environ, LUMAENC_PRINT_ARGS="1"))
         if ref.startswith("OK "):
             assert r.returncode == 0 and r.stdout.strip() == ref, (args, ref, r.stdout, r.stderr)

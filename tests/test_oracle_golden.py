@@ -1,7 +1,8 @@
 """The oracle against (a) the committed fixtures that tests/golden/make_golden.py generated from the real
 reference -- LumaQuantizer (oracle/_ref/libluma_ref.so) and the plane loops LumaEncoder::setChannels /
 LumaDecoder::getVpxChannels (oracle/_ref/ref_planes_tool), both compiled unmodified -- and (b), where those builds
-are present, the reference itself, live.  CPU only; bit-exact everywhere (NaN == NaN)."""
+are present, the reference itself, live; where they are not, its results on the same seeded inputs as recorded in
+tests/golden/ref_live_*.npz.  CPU only; bit-exact everywhere (NaN == NaN)."""
 import os
 
 import numpy as np
@@ -22,6 +23,137 @@ def table_for(o, cfg):
         nm = "psi" if cfg[0] == o.PTF_PSI else "jnd_hdrvdp"
         return np.fromfile(os.path.join(d, "ptf_%s_%d.f32" % (nm, cfg[1])), dtype="<f4")
     return None
+
+
+# ---- the live-reference checks: the reference's results on their (seeded) inputs are recorded in
+# ---- tests/golden/ref_live_<check>.npz (tests/golden/make_golden.py), so every check runs against the recording; where
+# ---- oracle/_ref/ is built it runs live too
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def live_fixture(name):
+    return os.path.join(GOLDEN, "ref_live_%s.npz" % name)
+
+
+class Tape:
+    """what the reference returned, call by call: recorded from the live reference (live=True) or replayed from the fixture"""
+
+    def __init__(self, items=None):
+        self.live = items is None
+        self.items = [] if items is None else items
+        self.pos = 0
+
+    def take(self):
+        assert self.pos < len(self.items), "more reference calls than the recording holds"
+        self.pos += 1
+        return self.items[self.pos - 1]
+
+    def done(self):
+        assert self.live or self.pos == len(self.items), "fewer reference calls than the recording holds"
+
+
+def load_tape(name):
+    calls = {}
+    with np.load(live_fixture(name)) as z:
+        for k in z.files:
+            i, j = k.split("/")
+            calls.setdefault(int(i), {})[int(j)] = z[k]
+    return Tape([[c[j] for j in sorted(c)] for _, c in sorted(calls.items())])
+
+
+def save_tape(name, tape, path=None):
+    np.savez_compressed(path or live_fixture(name), **{"%04d/%d" % (i, j): a for i, call in enumerate(tape.items)
+                                                       for j, a in enumerate(call)})
+
+
+class RefQ:
+    """o.RefQuantizer through a tape"""
+
+    def __init__(self, o, tape, *cfg):
+        self.t = tape
+        self.r = o.RefQuantizer(*cfg) if tape.live else None
+
+    def _rec(self, arrays):
+        self.t.items.append([np.asarray(a) for a in arrays])
+
+    @property
+    def stale(self):
+        return self.t.live and not hasattr(self.r.L, "ref_encode_frame")
+
+    @property
+    def mapping(self):
+        if not self.t.live:
+            return self.t.take()[0]
+        m = self.r.mapping
+        self._rec([m])
+        return m
+
+    def transform(self, frame, to_cs, sc=1.0):
+        if not self.t.live:
+            frame[...] = self.t.take()[0]
+            return frame
+        self.r.transform(frame, to_cs, sc)
+        self._rec([frame.copy()])
+        return frame
+
+    def quantize_array(self, a, ch=0):
+        if not self.t.live:
+            return self.t.take()[0]
+        q = self.r.quantize_array(a, ch)
+        self._rec([q])
+        return q
+
+    def encode(self, frame, sc=1.0, profile=2):
+        if not self.t.live:
+            c = self.t.take()
+            return list(c[:3]), [int(x) for x in c[3]], float(c[4][0])
+        planes, st, avg = self.r.encode(frame, sc, profile)
+        self._rec(list(planes) + [np.array(st, dtype=np.int32), np.array([avg], dtype=np.float64)])
+        return planes, st, avg
+
+    def encode_y_digest(self, frame, sc=1.0, profile=2):
+        """the SURVEY digest of the Y plane the reference encodes (the plane itself is not recorded)"""
+        if not self.t.live:
+            return str(self.t.take()[0])
+        from oracle import oracle_py as o
+        planes, _, _ = self.r.encode(frame, sc, profile)
+        d = o.survey_digest(o.packed_rows(planes[0], 2 * frame.shape[2]))
+        self._rec([np.array(d)])
+        return d
+
+
+class RefP:
+    """o.RefPlanes through a tape"""
+
+    def __init__(self, o, tape, *cfg, lut_override=None):
+        self.t = tape
+        self.r = o.RefPlanes(*cfg, lut_override=lut_override) if tape.live else None
+
+    def encode(self, frame, sc=1.0, profile=2, strides=None):
+        if not self.t.live:
+            c = self.t.take()
+            return list(c[:3]), tuple(int(x) for x in c[3]), (float(c[4][0]) if c[4].size else None)
+        planes, st, mean = self.r.encode(frame, sc, profile, strides=strides)
+        self.t.items.append(list(planes) + [np.array(st, dtype=np.int32),
+                                            np.array([] if mean is None else [mean], dtype=np.float64)])
+        return planes, st, mean
+
+    def decode(self, planes, strides, w, h, sc=1.0, profile=2, xform=True):
+        if not self.t.live:
+            return self.t.take()[0]
+        d = self.r.decode(planes, strides, w, h, sc, profile, xform=xform)
+        self.t.items.append([d])
+        return d
+
+
+def run_live_check(o, check, have_live):
+    """the check against the recording, and against the live reference where it is built"""
+    tape = load_tape(check.__name__)
+    check(o, tape)
+    tape.done()
+    if have_live:
+        check(o, Tape())
 
 
 @pytest.fixture(scope="module")
@@ -68,15 +200,11 @@ def test_transform_matches_reference(oracle_mod, gold, name, sc):
     assert same(g, t["%s_inv_sc%g" % (name, sc)])
 
 
-def test_live_reference_random_frames(oracle_mod):
-    """oracle vs the reference .so on fresh random frames, all colour spaces, both directions"""
-    o = oracle_mod
-    if not o.have_ref():
-        pytest.skip("oracle/_ref/libluma_ref.so not built (needs /root/reference)")
+def check_random_frames(o, tape):
     rng = np.random.default_rng(1234)
     for name, cfg in CONFIGS.items():
         qq = o.Oracle(*cfg, table=table_for(o, cfg))
-        r = o.RefQuantizer(*cfg)
+        r = RefQ(o, tape, *cfg)
         assert same(qq.mapping, r.mapping)
         f = np.exp(rng.uniform(np.log(1e-5), np.log(1e5), size=(3, 32, 64))).astype(np.float32)
         f[:, 0, :4] = [[0, np.nan, np.inf, -3], [1, 1, 1, 2], [2, 1, 1, 1]]
@@ -95,17 +223,17 @@ def test_live_reference_random_frames(oracle_mod):
             assert same(a2, b2), (name, sc, "inv")
 
 
-def test_live_reference_extreme_inputs(oracle_mod):
-    """inf - inf patterns, +-FLT_MAX, NaNs of both signs in every position, -0, denormals: the oracle's forward transform
-    and whole-frame encode against the REAL LumaQuantizer, every configuration, preScaling 1 and 20"""
+def test_live_reference_random_frames(oracle_mod):
+    """oracle vs the reference .so on seeded random frames, all colour spaces, both directions"""
+    run_live_check(oracle_mod, check_random_frames, oracle_mod.have_ref())
+
+
+def check_extreme_inputs(o, tape):
     from tests.golden.make_golden import extreme_frame
-    o = oracle_mod
-    if not o.have_ref():
-        pytest.skip("oracle/_ref/libluma_ref.so not built (needs /root/reference)")
     f = extreme_frame()
     for name, cfg in CONFIGS.items():
         qq = o.Oracle(*cfg, table=table_for(o, cfg))
-        r = o.RefQuantizer(*cfg)
+        r = RefQ(o, tape, *cfg)
         for sc in (1.0, 20.0):
             a, b = f.copy(), f.copy()
             with np.errstate(all="ignore"):
@@ -116,6 +244,12 @@ def test_live_reference_extreme_inputs(oracle_mod):
                 pa, _, _ = qq.encode(f.copy(), sc, profile)
                 pb, _, _ = r.encode(f.copy(), sc, profile)
                 assert all(np.array_equal(x, y) for x, y in zip(pa, pb)), (name, sc, profile)
+
+
+def test_live_reference_extreme_inputs(oracle_mod):
+    """inf - inf patterns, +-FLT_MAX, NaNs of both signs in every position, -0, denormals: the oracle's forward transform
+    and whole-frame encode against the REAL LumaQuantizer, every configuration, preScaling 1 and 20"""
+    run_live_check(oracle_mod, check_extreme_inputs, oracle_mod.have_ref())
 
 
 def test_roundtrip_decode_of_encode(oracle_mod):
@@ -136,18 +270,11 @@ def test_roundtrip_decode_of_encode(oracle_mod):
         assert np.median(np.abs(np.log2(Yd / Y))) < (0.2 if profile < 2 else 0.02)
 
 
-def test_live_reference_whole_frame_encode(oracle_mod):
-    """the oracle's whole-frame encode against the REAL LumaQuantizer driven through the harness's plane loop
-    (oracle/ref_harness.cpp: ref_encode_frame), every profile; PSI/HDR-VDP included (tables compiled into the
-    reference).  Also reproduces the SURVEY Y-plane digest with the real quantizer."""
-    o = oracle_mod
-    if not o.have_ref():
-        pytest.skip("oracle/_ref/libluma_ref.so not built (needs /root/reference)")
+def check_whole_frame_encode(o, tape):
     for name, cfg in CONFIGS.items():
         qq = o.Oracle(*cfg, table=table_for(o, cfg))
-        r = o.RefQuantizer(*cfg)
-        if not hasattr(r.L, "ref_encode_frame"):
-            pytest.skip("stale reference library")
+        r = RefQ(o, tape, *cfg)
+        assert not r.stale, "oracle/_ref/libluma_ref.so predates ref_encode_frame: rebuild it"
         f = o.synth_frame(96, 40, frame=2)
         f[:, 0, :3] = [[np.nan, 0, -1], [1, 0, 5], [1, 0, 2]]
         for profile in (0, 1, 2, 3):
@@ -155,9 +282,15 @@ def test_live_reference_whole_frame_encode(oracle_mod):
             b, _, avgb = r.encode(f.copy(), 1.0, profile)
             assert all(np.array_equal(x, y) for x, y in zip(a, b)), (name, profile)
             assert (np.isnan(avga) and np.isnan(avgb)) or avga == avgb
-    r = o.RefQuantizer(o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005)
-    planes, _, _ = r.encode(o.test_frame(1280, 720), 1.0, 2)
-    assert o.survey_digest(o.packed_rows(planes[0], 2560)) == "e0ff09731298e8f6"
+    r = RefQ(o, tape, o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005)
+    assert r.encode_y_digest(o.test_frame(1280, 720), 1.0, 2) == "e0ff09731298e8f6"
+
+
+def test_live_reference_whole_frame_encode(oracle_mod):
+    """the oracle's whole-frame encode against the REAL LumaQuantizer driven through the harness's plane loop
+    (oracle/ref_harness.cpp: ref_encode_frame), every profile; PSI/HDR-VDP included (tables compiled into the
+    reference).  Also reproduces the SURVEY Y-plane digest with the real quantizer."""
+    run_live_check(oracle_mod, check_whole_frame_encode, oracle_mod.have_ref())
 
 
 # ---- the plane loops: LumaEncoder::setChannels / setVpxChannel (src/luma_encoder.cpp:196-201,260-317) and
@@ -224,17 +357,11 @@ def test_plane_digests_from_the_reference_loops(oracle_mod, golden_dir):
         assert o.survey_digest(qq.decode(planes, st, 1280, 720, 1.0, profile)) == d["decoded"]
 
 
-def test_live_reference_plane_loops(oracle_mod):
-    """oracle vs the reference's compiled setChannels / getVpxChannels on fresh frames: every configuration, every
-    profile, ragged sizes, odd strides, an attachment-434 style table override.  Also the mean luminance the reference
-    prints in its warning (sequential fp32 sum) against the oracle's."""
-    o = oracle_mod
-    if not o.have_ref_planes():
-        pytest.skip("oracle/_ref/ref_planes_tool not built (needs /root/reference)")
+def check_plane_loops(o, tape):
     rng = np.random.default_rng(77)
     for name, cfg in CONFIGS.items():
         qq = o.Oracle(*cfg, table=table_for(o, cfg))
-        rp = o.RefPlanes(*cfg)
+        rp = RefP(o, tape, *cfg)
         sc = 20.0 if cfg[2] == o.CS_YCBCR else 1.0
         for (w, h) in ((6, 2), (50, 22)):
             f = np.exp(rng.uniform(np.log(1e-4), np.log(3e4), size=(3, h, w))).astype(np.float32)
@@ -254,7 +381,7 @@ def test_live_reference_plane_loops(oracle_mod):
                 assert same(qq.decode(garbage, st, w, h, sc, profile), rp.decode(garbage, st, w, h, sc, profile)), (name, profile)
     # dark frame: the reference prints its warning; its number is the sequential fp32 sum / (w*h)
     qq = o.Oracle(o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005)
-    rp = o.RefPlanes(o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005)
+    rp = RefP(o, tape, o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005)
     dark = (o.synth_frame(320, 180, frame=1) * np.float32(1e-5)).astype(np.float32)
     _, _, mo = qq.encode(dark.copy(), 1.0, 2)
     _, _, mr = rp.encode(dark.copy(), 1.0, 2)
@@ -264,9 +391,16 @@ def test_live_reference_plane_loops(oracle_mod):
     lut[100:110] *= np.float32(1.01)
     q2 = o.Oracle(o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005)
     q2.overwrite_mapping(lut)
-    rp2 = o.RefPlanes(o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005, lut_override=lut[:-1])   # getSize() = maxVal floats
+    rp2 = RefP(o, tape, o.PTF_PQ, 11, o.CS_LUV, 8, 1e4, 0.005, lut_override=lut[:-1])   # getSize() = maxVal floats
     lut_eff = lut.copy()
     lut_eff[-1] = qq.mapping[-1]
     q2.overwrite_mapping(lut_eff)
     planes, st, _ = q2.encode(o.synth_frame(64, 32, frame=9), 1.0, 2)
     assert same(q2.decode(planes, st, 64, 32, 1.0, 2), rp2.decode(planes, st, 64, 32, 1.0, 2))
+
+
+def test_live_reference_plane_loops(oracle_mod):
+    """oracle vs the reference's compiled setChannels / getVpxChannels on seeded frames: every configuration, every
+    profile, ragged sizes, odd strides, an attachment-434 style table override.  Also the mean luminance the reference
+    prints in its warning (sequential fp32 sum) against the oracle's."""
+    run_live_check(oracle_mod, check_plane_loops, oracle_mod.have_ref_planes())

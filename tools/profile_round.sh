@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/profile_round.sh <tag> [workload [width height frames_per_launch]] -- run on the GPU box (via gpurun).  Collects, under
 # gpurun_out/prof_<tag>_<wl>/ (default shape 3840x2160 x 20; BASELINE configs[3] is `log12_luv 7680 4320 5`):
-#   stats/   rocprofv3 --kernel-trace --stats of `python bench.py --steps 10 --warmup 2` (the default bench command,
+#   stats/   rocprofv3 --kernel-trace --stats of `python bench.py --full --steps 10 --warmup 2` (the --full bench command,
 #            shorter), whose per-kernel average must agree with bench.py's own hipEvent timing;
 #   pmc_*/   PMC counters of tools/prof_driver.py, one rocprofv3 run per counter group (--pmc is never combined
 #            with other tracing domains; FETCH_SIZE and WRITE_SIZE do not fit one pass; 8 SQ counters per pass).
@@ -15,7 +15,7 @@ mkdir -p $OUT
 P="rocprofv3 --kernel-trace --output-format csv"
 # --no-float-inputs: the float-input legs of the YCbCr workload run their first launches (and every probe) on the SAME half-input
 # kernel on data it is slow for; without the flag that kernel's average in the stats below is no longer the headline launch's
-BARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-other-workloads --no-facade-hostfed --no-placement-off --no-float-inputs --min-seconds 0.3 --workload $WL --width $W --height $H --frames-per-step $B"
+BARGS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-other-workloads --no-facade-hostfed --no-placement-off --no-float-inputs --min-seconds 0.3 --workload $WL --width $W --height $H --frames-per-step $B"
 echo "{\"width\": $W, \"height\": $H, \"frames\": $B}" > $OUT/shape.json
 $P --stats -d $OUT/stats -o bench -- python bench.py $BARGS > $OUT/bench_under_rocprof.log 2>&1
 python bench.py $BARGS > $OUT/bench_plain.log 2>&1
