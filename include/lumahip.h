@@ -37,6 +37,9 @@ extern "C" {
 
 /* ABI history.  The BINARY interface has only ever grown: every symbol of an earlier version is still exported with the same
  * signature, so a program linked against version 2 runs against this library.
+ *   5, later additions that change no existing symbol (detect them with dlsym): the binary16 frame calls
+ *     lumahip_encode_frames_device_f16 / _planar_f16, lumahip_decode_frames_device_f16 / _planar_f16,
+ *     lumahip_encode_frame_host_f16, lumahip_decode_frame_host_f16 and the probe lumahip_f16_narrow_probe_device.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -285,6 +288,37 @@ int lumahip_encode_frames_device_planar(lumahip_ctx *ctx, const float *const rgb
 int lumahip_decode_frames_device_planar(lumahip_ctx *ctx, const unsigned char *const planes_dev[3], const int stride[3],
                                         const size_t plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h,
                                         int profile, float sc, float *const rgb_planes_dev[3], size_t frame_stride);
+
+/* Binary16 frames.  The same calls for frames of halves: each element is a uint16_t holding an IEEE binary16 bit pattern
+ * (torch.float16, Imf::Rgba / half, _Float16), and frame_stride and the colour-plane pointers count and address halves.  Frame
+ * layout, plane layout, streams, unordered sections and errors are those of the float forms above.
+ * Encode: the kernels widen every half exactly, so the planes and the statistics equal those of the float call on the widened
+ * frame, for every quantizer setting.  The kernel is chosen from the arguments alone (no probe of the data, no host wait): YCbCr
+ * calls without stats_dev take the half-input table kernels whenever lumahip_ycbcr_half_table_host accepts (sc, maxLum) (and
+ * lumahip_tune("half_table") is not 0); calls with stats_dev, and every other colour space, take the general kernels.
+ * Decode: the decoded floats are narrowed to binary16 exactly as ExrInterface::floatToHalf (and the reference's lumadec, through
+ * Imf::Rgba) does: round to nearest even, denormals, overflow to +-inf, signed zeros, NaN -> sign | 0x7e00 | (mantissa >> 13).
+ * Alignment: each colour-plane base 4-byte aligned and frame_stride even; otherwise LUMAHIP_ERR_ARG before any launch.  8-byte
+ * aligned bases with w and frame_stride multiples of 4 let the kernels move four pixels per access (faster, same results).
+ * The host forms copy 6 bytes per pixel (rgb / rgb_out: 3*w*h halves, LumaFrame layout); mean_lum as in
+ * lumahip_encode_frame_host.  Not provided for halves: the display decode, the rotating / ring layouts, lumahip_multi_*. */
+int lumahip_encode_frames_device_f16(lumahip_ctx *ctx, const uint16_t *rgb_dev, size_t frame_stride, unsigned nframes,
+                                     unsigned w, unsigned h, float sc, int profile, unsigned char *const planes_dev[3],
+                                     const int stride[3], const size_t plane_frame_stride[3], float *stats_dev);
+int lumahip_encode_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t *const rgb_planes_dev[3], size_t frame_stride,
+                                            unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                            unsigned char *const planes_dev[3], const int stride[3],
+                                            const size_t plane_frame_stride[3], float *stats_dev);
+int lumahip_decode_frames_device_f16(lumahip_ctx *ctx, const unsigned char *const planes_dev[3], const int stride[3],
+                                     const size_t plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h,
+                                     int profile, float sc, uint16_t *rgb_dev, size_t frame_stride);
+int lumahip_decode_frames_device_planar_f16(lumahip_ctx *ctx, const unsigned char *const planes_dev[3], const int stride[3],
+                                            const size_t plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h,
+                                            int profile, float sc, uint16_t *const rgb_planes_dev[3], size_t frame_stride);
+int lumahip_encode_frame_host_f16(lumahip_ctx *ctx, const uint16_t *rgb, unsigned w, unsigned h, float sc, int profile,
+                                  unsigned char *const planes[3], const int stride[3], float *mean_lum);
+int lumahip_decode_frame_host_f16(lumahip_ctx *ctx, const unsigned char *const planes[3], const int stride[3],
+                                  unsigned w, unsigned h, int profile, float sc, uint16_t *rgb_out);
 /* Decoded frames in the reference's PACKED layout (include/luma/luma_frame.h:84-87 there: channel c of a frame at base + c*w*h)
  * spread over THREE buffers: frame f of the batch at bases[f % 3] + (f / 3) * frame_stride floats (frame_stride >= 3*w*h).  Every
  * frame is a LumaFrame as LumaDecoder::decode() returns it; what changes is where consecutive frames live.  With the three
@@ -562,6 +596,10 @@ int lumahip_quantize_probe_device(lumahip_ctx *ctx, uint16_t *out_dev, uint32_t 
  * narrow-range powers (y = 1/78.8438f: arguments in [2^-21, 1] only; y = 78.8438f: arguments in [0.7, 1.4) only).  Lets the
  * tests compare the device function with the host libm exhaustively. */
 int lumahip_powf_probe_device(lumahip_ctx *ctx, float *out_dev, uint32_t first_bits, size_t n, float y, int regular);
+
+/* Test probe: out[i] = the binary16 bits that the decode kernels store for the float whose bit pattern is first_bits + i
+ * (f16_narrow, the _f16 decode calls).  n even, out 4-byte aligned. */
+int lumahip_f16_narrow_probe_device(lumahip_ctx *ctx, uint16_t *out_dev, uint32_t first_bits, size_t n);
 
 /* Test probe (YCbCr quantizers): out[i] = the luminance code of a pixel whose t = 219 y + 16 (y = its luma,
  * src/luma_quantizer.cpp:335-337) is the float with bit pattern first_bits + i.  direct = 0: through the composite threshold

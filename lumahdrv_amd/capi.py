@@ -35,6 +35,8 @@ SYMBOLS = [
     "lumahip_multi_create", "lumahip_multi_destroy", "lumahip_multi_shards", "lumahip_multi_ctx", "lumahip_multi_last_error", "lumahip_multi_used_rccl", "lumahip_multi_set_transport", "lumahip_multi_transport_note",
     "lumahip_shard_range", "lumahip_multi_set_quantizer", "lumahip_multi_encode_frames_host", "lumahip_multi_decode_frames_host",
     "lumahip_multi_encode_frames_device", "lumahip_multi_decode_frames_device", "lumahip_multi_sync",
+    "lumahip_encode_frames_device_f16", "lumahip_encode_frames_device_planar_f16", "lumahip_decode_frames_device_f16",
+    "lumahip_decode_frames_device_planar_f16", "lumahip_encode_frame_host_f16", "lumahip_decode_frame_host_f16", "lumahip_f16_narrow_probe_device",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -70,7 +72,8 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 
 # device code + launch geometry + compiler flags (NOT the host plumbing: lumahip_core / _host / _pool / _multi, lumahip_internal.hpp)
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
-                  "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk")
+                  "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
+                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip")
 
 
 def kernel_source_sha() -> str:
@@ -154,6 +157,13 @@ def lib():
     L.lumahip_time_launches.argtypes = [vp, i, i, vp, sz, u, u, u, f, i, pp3, ip3, sp3, C.POINTER(f)]
     L.lumahip_probe_encode_traffic_device.argtypes = [vp, vp, sz, u, u, u, pp3, ip3, sp3, i, C.POINTER(f)]
     L.lumahip_powf_probe_device.argtypes = [vp, vp, C.c_uint32, sz, f, i]
+    L.lumahip_f16_narrow_probe_device.argtypes = [vp, vp, C.c_uint32, sz]
+    L.lumahip_encode_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
+    L.lumahip_encode_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
+    L.lumahip_decode_frames_device_f16.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, vp, sz]
+    L.lumahip_decode_frames_device_planar_f16.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, pp3, sz]
+    L.lumahip_encode_frame_host_f16.argtypes = [vp, vp, u, u, f, i, pp3, ip3, C.POINTER(f)]
+    L.lumahip_decode_frame_host_f16.argtypes = [vp, pp3, ip3, u, u, i, f, vp]
     L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_host_register.argtypes = [vp, vp, sz]
@@ -480,6 +490,31 @@ class Context:
                                                    _arr3(C.c_int, strides), w, h, profile, sc, out.ctypes.data))
         return out
 
+    def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
+        """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
+        mean_lum), equal to encode_frame of the same frame widened to float32."""
+        if np.asarray(rgb).dtype != np.float16:
+            raise LumaHipError(ERR_ARG, "encode_frame_f16 takes np.float16 frames")
+        rgb = np.ascontiguousarray(rgb)
+        _, h, w = rgb.shape
+        _, hs, st, _ = plane_geometry(w, h, profile, align)
+        if strides is not None:
+            st = tuple(strides)
+        planes = [np.zeros((hs[p], st[p]), dtype=np.uint8) for p in range(3)]
+        mean = C.c_float(0)
+        self._chk(self.L.lumahip_encode_frame_host_f16(self.h, rgb.ctypes.data, w, h, sc, profile,
+                                                       _arr3(C.c_void_p, [p.ctypes.data for p in planes]),
+                                                       _arr3(C.c_int, st), C.byref(mean)))
+        return planes, st, float(mean.value)
+
+    def decode_frame_f16(self, planes, strides, w, h, sc=1.0, profile=2) -> np.ndarray:
+        """-> (3,h,w) np.float16: the decoded frame narrowed as ExrInterface::floatToHalf does (6 B per pixel come back)"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        out = np.empty((3, h, w), dtype=np.float16)
+        self._chk(self.L.lumahip_decode_frame_host_f16(self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]),
+                                                       _arr3(C.c_int, strides), w, h, profile, sc, out.ctypes.data))
+        return out
+
     def encode_frames(self, frames, sc=1.0, profile=2, align=32):
         """pipelined batch form of encode_frame: frames = list of (3,h,w) float32 arrays.  Returns
         (list of plane triplets, strides, list of mean luminances)."""
@@ -612,6 +647,36 @@ class Context:
         self._chk(self.L.lumahip_decode_frames_device_planar(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
                                                              _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile, sc,
                                                              _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride))
+
+    # binary16 frames (raw device pointers to halves, e.g. a torch.float16 tensor's data_ptr(); strides count halves)
+    def encode_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                 plane_frame_strides, stats_ptr=None):
+        self._chk(self.L.lumahip_encode_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                          _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                          _arr3(C.c_size_t, plane_frame_strides), stats_ptr))
+
+    def encode_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                        plane_frame_strides, stats_ptr=None):
+        self._chk(self.L.lumahip_encode_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
+                                                                 w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
+                                                                 _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
+                                                                 stats_ptr))
+
+    def decode_frames_device_f16(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, rgb_ptr,
+                                 frame_stride):
+        self._chk(self.L.lumahip_decode_frames_device_f16(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                          _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile,
+                                                          sc, rgb_ptr, frame_stride))
+
+    def decode_frames_device_planar_f16(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc,
+                                        rgb_plane_ptrs, frame_stride):
+        self._chk(self.L.lumahip_decode_frames_device_planar_f16(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                                 _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile,
+                                                                 sc, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride))
+
+    def f16_narrow_probe_device(self, out_ptr, first_bits, n):
+        """uint16 binary16 bits the decode kernels store for the n consecutive fp32 bit patterns from first_bits"""
+        self._chk(self.L.lumahip_f16_narrow_probe_device(self.h, out_ptr, first_bits, n))
 
     def begin_unordered(self, lanes: int = 0):
         """open an unordered section: the following _device encode / decode calls are independent of each other"""

@@ -10,3 +10,4 @@ FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vect
 #   profiles/r06_sched_ab.txt): the HBM-bound encode kernels 1.6 - 1.8 % faster per launch, the decode kernels 0.9 % SLOWER, the
 #   VALU-bound YCbCr kernels unchanged -- so it is the encode unit's only.  ("iterative-ilp" crashes this compiler on these units.)
 FLAGS_lumahip_encode := -mllvm -amdgpu-sched-strategy=max-ilp
+FLAGS_lumahip_encode_f16 := $(FLAGS_lumahip_encode)

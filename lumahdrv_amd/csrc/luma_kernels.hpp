@@ -16,6 +16,7 @@
 
 #include <type_traits>
 
+#include "f16_narrow.hpp"
 #include "luma_device.hpp"
 
 
@@ -325,6 +326,21 @@ LH_DEV void load_px_h(const _Float16 *p, float (&v)[VW])
     } else {
         const lh_v2h t = __builtin_nontemporal_load(reinterpret_cast<const lh_v2h *>(p));
         v[0] = (float)t.x; v[1] = (float)t.y;
+    }
+}
+
+// the same VW pixels narrowed to binary16 (f16_narrow: the bits of ExrInterface::floatToHalf), 8 / 4 bytes non-temporal
+template <int VW>
+LH_DEV void store_px_h(uint16_t *p, const float (&v)[VW])
+{
+    if constexpr (VW == 4) {
+        typedef uint32_t lh_v2u __attribute__((ext_vector_type(2)));
+        const lh_v2u t = {(uint32_t)lh::f16_narrow(v[0]) | ((uint32_t)lh::f16_narrow(v[1]) << 16),
+                          (uint32_t)lh::f16_narrow(v[2]) | ((uint32_t)lh::f16_narrow(v[3]) << 16)};
+        __builtin_nontemporal_store(t, reinterpret_cast<lh_v2u *>(p));
+    } else {
+        const uint32_t t = (uint32_t)lh::f16_narrow(v[0]) | ((uint32_t)lh::f16_narrow(v[1]) << 16);
+        __builtin_nontemporal_store(t, reinterpret_cast<uint32_t *>(p));
     }
 }
 
@@ -938,8 +954,9 @@ LH_DEV bool rb_wave_local(const DecUnit<SUB, VW> &u, int near_y, int near_c)
 struct DecNoHook {
     __device__ __forceinline__ void operator()() const {}
 };
-template <int CS, bool SUB, int VW, bool DISP, bool UVTAB, bool YT = false, bool SCFAST = false, bool RB = false, typename LutPtr, typename K,
-          typename Hook = DecNoHook>
+// OUT16: the frames are binary16 (a.dst[c] points at halves; offsets and strides count elements either way)
+template <int CS, bool SUB, int VW, bool DISP, bool UVTAB, bool YT = false, bool SCFAST = false, bool RB = false, bool OUT16 = false,
+          typename LutPtr, typename K, typename Hook = DecNoHook>
 LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k, LutPtr lut, const float *s_uv, Hook before_stores = Hook())
 {
     bool gathered = false;
@@ -1075,7 +1092,17 @@ LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k,
     }
 
     before_stores();
-    if (!DISP || a.dst[0]) {
+    if constexpr (OUT16) {
+        // (packed and planar frames only: the host never sets rot_on for these kernels, lumahip_decode_frames_device_f16)
+        static_assert(!DISP, "binary16 frames have no display epilogue");
+        const size_t off = (size_t)u.f * a.frame_stride + (size_t)(2 * u.uy) * a.g.w + (size_t)u.ux * VW;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            uint16_t *d = reinterpret_cast<uint16_t *>(a.dst[c]) + off;
+            store_px_h<VW>(d, out[c][0]);
+            store_px_h<VW>(d + a.g.w, out[c][1]);
+        }
+    } else if (!DISP || a.dst[0]) {
         const size_t px = (size_t)(2 * u.uy) * a.g.w + (size_t)u.ux * VW;
         if (a.rot_on) {   // (kernel argument: uniform; u.f is wave-uniform, so the base is a scalar select)
             // (readfirstlane: the frame index IS wave-uniform, and saying so keeps the choice among the three bases a scalar one.
@@ -1142,10 +1169,12 @@ LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k,
 // decoder does not carry the epilogue's registers (it cost 8 % when it was a run-time branch)
 // YT (YCbCr, table in LDS): additionally stage the per-stream y table and skip the first PQ evaluation of every pixel
 // RB (with YT): red and blue from the per-stream (Y', Cr) / (Y', Cb) tables in global memory, green computed (DecArgs::rb)
-template <int CS, bool SUB, int VW, bool GL, bool DISP = false, bool YT = false, bool RB = false>
+// OUT16: binary16 frames (dec_process), packed or planar; never with DISP or the rotating layout
+template <int CS, bool SUB, int VW, bool GL, bool DISP = false, bool YT = false, bool RB = false, bool OUT16 = false>
 __global__ __launch_bounds__(1024) void k_decode(const DecArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(!OUT16 || !DISP, "binary16 frames have no display epilogue");
     static_assert(!YT || (CS == CS_YCBCR && !GL), "the y table belongs to the YCbCr kernels with the table in LDS");
     static_assert(!RB || YT, "the red / blue tables need the y table");
     // GL: transfer-function table or chroma depth beyond 12 bits -- tables stay in global memory / are not built
@@ -1213,19 +1242,19 @@ __global__ __launch_bounds__(1024) void k_decode(const DecArgs a)
                 // two copies of the unit's code, chosen by a kernel argument: see ycbcr_inv_n on why not a run-time choice inside
                 if (k.sc_mode == 1) {
                     if constexpr (GL)
-                        dec_process<CS, SUB, VW, DISP, false, false, true>(cur, a, k, a.q.lut, s_uv, hook);
+                        dec_process<CS, SUB, VW, DISP, false, false, true, false, OUT16>(cur, a, k, a.q.lut, s_uv, hook);
                     else
-                        any_gather |= dec_process<CS, SUB, VW, DISP, UVTAB, YT, true, RB>(cur, a, k, s_lut, s_uv, hook);
+                        any_gather |= dec_process<CS, SUB, VW, DISP, UVTAB, YT, true, RB, OUT16>(cur, a, k, s_lut, s_uv, hook);
                 } else {
                     if constexpr (GL)
-                        dec_process<CS, SUB, VW, DISP, false>(cur, a, k, a.q.lut, s_uv, hook);
+                        dec_process<CS, SUB, VW, DISP, false, false, false, false, OUT16>(cur, a, k, a.q.lut, s_uv, hook);
                     else
-                        any_gather |= dec_process<CS, SUB, VW, DISP, UVTAB, YT, false, RB>(cur, a, k, s_lut, s_uv, hook);
+                        any_gather |= dec_process<CS, SUB, VW, DISP, UVTAB, YT, false, RB, OUT16>(cur, a, k, s_lut, s_uv, hook);
                 }
             } else if constexpr (GL) {
-                dec_process<CS, SUB, VW, DISP, false>(cur, a, k, a.q.lut, s_uv, hook);
+                dec_process<CS, SUB, VW, DISP, false, false, false, false, OUT16>(cur, a, k, a.q.lut, s_uv, hook);
             } else {
-                dec_process<CS, SUB, VW, DISP, UVTAB, YT>(cur, a, k, s_lut, s_uv, hook);
+                dec_process<CS, SUB, VW, DISP, UVTAB, YT, false, false, OUT16>(cur, a, k, s_lut, s_uv, hook);
             }
         } else {
             hook();

@@ -1028,7 +1028,7 @@ void plane_dims(unsigned w, unsigned h, int profile, int p, int &rows, int &row_
 // the device entry points take caller-chosen strides: reject layouts in which rows or frames would overlap or the
 // kernels would write outside a plane (negative / too small strides, frame strides smaller than a frame)
 int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned nframes, const float *const rgb[3],
-                 size_t frame_stride, const int stride[3], const size_t pfs[3])
+                 size_t frame_stride, const int stride[3], const size_t pfs[3], size_t esize)
 {
     for (int p = 0; p < 3; p++) {
         int rows, row_bytes;
@@ -1050,8 +1050,8 @@ int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned n
     const size_t span = (size_t)(nframes - 1) * frame_stride + n;  // floats one plane sequence covers
     for (int i = 0; i < 3; i++)
         for (int j = i + 1; j < 3; j++) {
-            const float *lo = rgb[i] < rgb[j] ? rgb[i] : rgb[j], *hi = rgb[i] < rgb[j] ? rgb[j] : rgb[i];
-            const size_t d = (size_t)(hi - lo);
+            const uintptr_t x = (uintptr_t)rgb[i], y = (uintptr_t)rgb[j];
+            const size_t d = (size_t)(x < y ? y - x : x - y) / esize;   // (elements)
             const bool disjoint = d >= span;
             const bool interleaved = d >= n && (nframes == 1 || d + n <= frame_stride);
             if (!disjoint && !interleaved)

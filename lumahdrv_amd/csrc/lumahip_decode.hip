@@ -87,8 +87,6 @@ __global__ __launch_bounds__(256) void k_build_rb(const RbArgs a)
 
 }  // namespace lh
 
-typedef void (*dec_kernel_t)(const DecArgs);
-
 template <int CS, bool SUB>
 static dec_kernel_t pick_dec2(int vw, bool gl, bool disp, bool yt, bool rb)
 {
@@ -124,9 +122,10 @@ namespace lhost {
 
 // true when no colour plane of the batch starts inside another one's extent: R, G and B are three buffers, not three
 // sections of packed LumaFrames
-static bool planes_are_separate_buffers(float *const rgb[3], size_t frame_stride, unsigned nframes, unsigned w, unsigned h)
+static bool planes_are_separate_buffers(float *const rgb[3], size_t frame_stride, unsigned nframes, unsigned w, unsigned h,
+                                        size_t esize = sizeof(float))
 {
-    const size_t extent = ((size_t)(nframes - 1) * frame_stride + (size_t)w * h) * sizeof(float);
+    const size_t extent = ((size_t)(nframes - 1) * frame_stride + (size_t)w * h) * esize;
     auto apart = [&](const float *p, const float *q) {
         const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
         return (x > y ? x - y : y - x) >= extent;
@@ -194,8 +193,10 @@ int rb_table_for(lumahip_ctx *c, float sc, const float **tab)
 
 int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
                 unsigned nframes, unsigned w, unsigned h, int profile, float sc, float *const rgb_in[3], size_t frame_stride,
-                const DisplayParams &dp, int cs_eff, bool lanes, float *const rot[3])
+                const DisplayParams &dp, int cs_eff, bool lanes, float *const rot[3], bool out16)
 {
+    if (out16 && (rot || dp.rgba))
+        return fail(c, LUMAHIP_ERR_ARG, "binary16 frames: no rotating layout, no display output");
     // rot: packed frames rotating over three buffers (DecArgs::rot); the checks below then look at buffer 0's first frame
     float *rot_planes[3] = {nullptr, nullptr, nullptr};
     if (rot) {
@@ -232,7 +233,8 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     int rc = check_geom(c, w, h, profile, cs_eff);
     if (rc)
         return rc;
-    if ((rc = check_layout(c, w, h, profile, nframes, (have_rgb && !rot) ? rgb : nullptr, frame_stride, stride, pfs)))
+    if ((rc = check_layout(c, w, h, profile, nframes, (have_rgb && !rot) ? rgb : nullptr, frame_stride, stride, pfs,
+                           out16 ? 2 : sizeof(float))))
         return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const bool sub = (profile == 0 || profile == 2);
@@ -240,12 +242,15 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     const bool gl = !c->lut_in_lds;
     float *const none[3] = {nullptr, nullptr, nullptr};
     float *const *out = have_rgb ? rgb : none;
-    const bool al16 = is_aligned(out[0], 16) && is_aligned(out[1], 16) && is_aligned(out[2], 16);
-    int vw = (!gl && (w % 4) == 0 && al16 && (frame_stride % 4) == 0) ? 4 : 2;
+    // the stores of VW pixels need VW-element alignment: VW = 4 where possible, VW = 2 always (float frames 16 / 8 bytes,
+    // binary16 frames 8 / 4 bytes)
+    const size_t esz = out16 ? 2 : 4;
+    const bool al4 = is_aligned(out[0], 4 * esz) && is_aligned(out[1], 4 * esz) && is_aligned(out[2], 4 * esz);
+    int vw = (!gl && (w % 4) == 0 && al4 && (frame_stride % 4) == 0) ? 4 : 2;
     if (c->dec_vw == 2)   // lumahip_tune("dec_vw", 2): two pixels per thread and row even where four are possible (measurements)
         vw = 2;
-    if (!is_aligned(out[0], 8) || !is_aligned(out[1], 8) || !is_aligned(out[2], 8) || (frame_stride % 2) != 0)
-        return fail(c, LUMAHIP_ERR_ARG, "colour planes must be 8-byte aligned and the frame stride even");
+    if (!is_aligned(out[0], 2 * esz) || !is_aligned(out[1], 2 * esz) || !is_aligned(out[2], 2 * esz) || (frame_stride % 2) != 0)
+        return fail(c, LUMAHIP_ERR_ARG, "colour planes must be %d-byte aligned and the frame stride even", (int)(2 * esz));
     if (dp.rgba && (!is_aligned(dp.rgba, 4) || (dp.stride % 4) != 0 || (dp.frame_stride % 4) != 0 || dp.stride < (int)(4 * w)))
         return fail(c, LUMAHIP_ERR_ARG, "display buffer must be 4-byte aligned with stride >= 4*w");
     DecArgs a{};
@@ -305,7 +310,10 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     a.rb_near_c = c->rb_near_c;
     if (rb)
         c->rb_launches++;
-    dec_kernel_t kern = pick_dec(cs_eff, sub, vw, gl, dp.rgba != nullptr, yt, rb != nullptr);
+    dec_kernel_t kern = out16 ? pick_dec_f16(cs_eff, sub, vw, gl, yt, rb != nullptr)
+                              : pick_dec(cs_eff, sub, vw, gl, dp.rgba != nullptr, yt, rb != nullptr);
+    if (!kern)
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no decode kernel for colour space %d%s", cs_eff, out16 ? " with binary16 frames" : "");
     LagLaunchGuard rb_guard{c->rb_pol, rb_flag};   // (a return before the launch takes the word back: the policy must not wait for it)
     if (lds > 64 * 1024)
         HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -313,7 +321,7 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     // colour planes of the batch are separate buffers (no plane starts inside another plane's extent over the batch) -- the layout
     // a caller uses to spread the three write streams over the HBM region groups (lumahip_decode_frames_device_planar)
     int few_writers = (sub && bps == 2 && cs_eff != CS_YCBCR && dp.rgba == nullptr) ? 1 : 0;
-    if (few_writers && have_rgb && (rot || planes_are_separate_buffers(rgb, frame_stride, nframes, w, h)))
+    if (few_writers && have_rgb && (rot || planes_are_separate_buffers(rgb, frame_stride, nframes, w, h, esz)))
         few_writers = 2;
     const int grid = grid_for(c, threads, a.g.totalTiles, 1, few_writers, cs_eff == CS_YCBCR);
     hipStream_t s = launch_stream(c, lanes);

@@ -40,8 +40,6 @@ __global__ __launch_bounds__(256) void k_encode_traffic_probe(const EncArgs a)
 
 }  // namespace lh
 
-typedef void (*enc_kernel_t)(const EncArgs);
-
 template <int CS, bool SUB>
 static enc_kernel_t pick_enc2(int vw, int mode)
 {
@@ -119,15 +117,17 @@ namespace lhost {
 
 int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t frame_stride, unsigned nframes,
                               unsigned w, unsigned h, float sc, int profile, unsigned char *const planes[3],
-                              const int stride[3], const size_t pfs[3], float *stats, int cs_eff, bool lanes, bool in16)
+                              const int stride[3], const size_t pfs[3], float *stats, int cs_eff, bool lanes, int in16)
 {
+    const bool typed16 = in16 == IN16_TYPED;
     if (!c || !rgb || !rgb[0] || !rgb[1] || !rgb[2] || !planes || !stride || !pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     int rc = check_geom(c, w, h, profile, cs_eff);
     if (rc)
         return rc;
     // (binary16 frames come from this library's own staging code: the overlap test of the float planes, which measures in floats, is skipped)
-    if ((rc = check_layout(c, w, h, profile, nframes, in16 ? nullptr : rgb, frame_stride, stride, pfs)))
+    if ((rc = check_layout(c, w, h, profile, nframes, in16 == IN16_UPLOAD ? nullptr : rgb, frame_stride, stride, pfs,
+                           typed16 ? 2 : sizeof(float))))
         return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure_search_index(c)))
@@ -136,26 +136,33 @@ int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t 
     const int bps = profile > 1 ? 2 : 1;
     const int mode = c->q.mode;
     const bool fast_search = (mode == LUT_THRESH_LDS || mode == LUT_THRESH_GLOBAL || mode == LUT_LINKEY_LDS);
-    const bool al16 = is_aligned(rgb[0], 16) && is_aligned(rgb[1], 16) && is_aligned(rgb[2], 16);
-    int vw = (fast_search && (w % 4) == 0 && al16 && (frame_stride % 4) == 0) ? 4 : 2;
-    if (!is_aligned(rgb[0], 8) || !is_aligned(rgb[1], 8) || !is_aligned(rgb[2], 8) || (frame_stride % 2) != 0)
-        return fail(c, LUMAHIP_ERR_ARG, "colour planes must be 8-byte aligned and the frame stride even");
-    if (in16) {   // halves: 8-byte loads of four pixels
+    // the loads of VW pixels need VW-element alignment: VW = 4 where possible, VW = 2 always (float frames 16 / 8 bytes, binary16
+    // frames by type 8 / 4 bytes)
+    const size_t esz = typed16 ? 2 : 4;
+    const bool al4 = is_aligned(rgb[0], 4 * esz) && is_aligned(rgb[1], 4 * esz) && is_aligned(rgb[2], 4 * esz);
+    int vw = (fast_search && (w % 4) == 0 && al4 && (frame_stride % 4) == 0) ? 4 : 2;
+    if (!is_aligned(rgb[0], 2 * esz) || !is_aligned(rgb[1], 2 * esz) || !is_aligned(rgb[2], 2 * esz) || (frame_stride % 2) != 0)
+        return fail(c, LUMAHIP_ERR_ARG, "colour planes must be %d-byte aligned and the frame stride even", (int)(2 * esz));
+    if (in16 == IN16_UPLOAD) {   // halves: 8-byte loads of four pixels
         if (mode != LUT_THRESH_LDS || (w % 4) != 0 || (frame_stride % 4) != 0)
             return fail(c, LUMAHIP_ERR_UNSUPPORTED, "binary16 frames need the luminance records in LDS and rows of a multiple of 4 pixels");
         vw = 4;
     }
     // YCbCr without per-frame statistics (they need the luminance itself): the luminance code comes straight from the luma
-    const bool ycode = !in16 && cs_eff == CS_YCBCR && !stats && ycbcr_composite_ready(c);
+    // (frames that are binary16 by type: only together with the half-input table below, else the general IN16 kernel)
+    bool ycode = (!in16 || typed16) && cs_eff == CS_YCBCR && !stats && ycbcr_composite_ready(c);
     // ... and R', G', B' of binary16 inputs from the half-input table of this call's (sc, Lmax), when table + records fit the LDS
     const float *half = nullptr;
     uint32_t *half_flag = nullptr;   // this launch's feedback word (LagPolicy)
     if (ycode && c->half_mode != 0 && lds_bytes(c, true, cs_eff, true, true) <= LUMAHIP_LDS_PER_WORKGROUP) {
         if ((rc = half_table_for(c, sc, &half)))
             return rc;
-        if (half && c->half_mode == 1 && !lag_policy_next(c->half_pol, &half_flag))   // (mode 2: always, no feedback)
+        // (mode 2, and frames that are halves by type: always, no feedback)
+        if (half && !typed16 && c->half_mode == 1 && !lag_policy_next(c->half_pol, &half_flag))
             half = nullptr;
     }
+    if (typed16 && !half)
+        ycode = false;
     LagLaunchGuard half_guard{c->half_pol, half_flag};   // (a return before the launch takes the word back)
     EncArgs a{};
     a.q = ycode ? c->q_y : c->q;
@@ -187,7 +194,9 @@ int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t 
             a.aligned = 0;
     }
     a.q.cs = cs_eff;
-    enc_kernel_t kern = in16 ? pick_enc_in16(cs_eff, sub) : pick_enc(cs_eff, sub, vw, half ? 6 : ycode ? 5 : mode);
+    const int kmode = half ? 6 : ycode ? 5 : mode;
+    enc_kernel_t kern = in16 == IN16_UPLOAD ? pick_enc_in16(cs_eff, sub) : typed16 ? pick_enc_f16(cs_eff, sub, vw, kmode)
+                                                                                   : pick_enc(cs_eff, sub, vw, kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no encode kernel for colour space %d%s", cs_eff, in16 ? " with binary16 frames" : "");
     if (lds > 64 * 1024)

@@ -946,6 +946,95 @@ extern "C" int lumahip_decode_frame_host(lumahip_ctx *c, const unsigned char *co
     return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, c->q.cs);
 }
 
+// ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the
+// caller's halves go up as they are (no round-trip test, unlike the half upload above) and the decoded halves come down as the
+// kernel wrote them.
+extern "C" int lumahip_encode_frame_host_f16(lumahip_ctx *c, const uint16_t *rgb, unsigned w, unsigned h, float sc, int profile,
+                                             unsigned char *const planes[3], const int stride[3], float *mean_lum)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!rgb || !planes || !stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    const int cs_eff = c->q.cs;
+    int rc = check_geom(c, w, h, profile, cs_eff);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    PlaneLayout L;
+    plane_layout(L, w, h, profile, stride);
+    for (int p = 0; p < 3; p++)
+        if (!planes[p] || stride[p] < L.row_bytes[p])
+            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
+    const size_t nfl = (size_t)3 * w * h, n1 = (size_t)w * h;
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))))   // (float-sized: the buffer is shared)
+        return rc;
+    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
+        return rc;
+    if (!c->d_stats)
+        HIPCHK(c, hipMalloc(&c->d_stats, 3 * sizeof(float)));
+    unsigned char *dp[3] = {c->d_planes + L.off[0], c->d_planes + L.off[1], c->d_planes + L.off[2]};
+    const size_t pfs[3] = {0, 0, 0};
+    uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);
+    if ((rc = xfer_h2d(c, d16, rgb, nfl * sizeof(uint16_t), c->stream)))
+        return rc;
+    const float *const fp[3] = {reinterpret_cast<const float *>(d16), reinterpret_cast<const float *>(d16 + n1),
+                                reinterpret_cast<const float *>(d16 + 2 * n1)};
+    if ((rc = encode_frames_device_impl(c, fp, nfl, 1, w, h, sc, profile, dp, stride, pfs, c->d_stats, cs_eff, false, IN16_TYPED)))
+        return rc;
+    for (int p = 0; p < 3; p++)
+        if ((rc = xfer_d2h_2d(c, planes[p], stride[p], dp[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
+            return rc;
+    float st[3];
+    if ((rc = read_small(c, st, c->d_stats, 3, c->stream)))   // synchronises the stream
+        return rc;
+    if (mean_lum) {
+        *mean_lum = st[0] / (float)((int)w * (int)h);  // avg /= (w*h), src/luma_encoder.cpp:314
+        if (mean_needs_reference_sum(*mean_lum, st[1], w, h))
+            return mean_luminance_reference_impl(c, c->d_frame, w, h, sc, cs_eff, mean_lum, true);
+    }
+    return LUMAHIP_OK;
+}
+
+extern "C" int lumahip_decode_frame_host_f16(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], unsigned w,
+                                             unsigned h, int profile, float sc, uint16_t *rgb_out)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!rgb_out || !planes || !stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    const int cs_eff = c->q.cs;
+    int rc = check_geom(c, w, h, profile, cs_eff);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    PlaneLayout L;
+    plane_layout(L, w, h, profile, stride);
+    for (int p = 0; p < 3; p++)
+        if (!planes[p] || stride[p] < L.row_bytes[p])
+            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
+    const size_t nfl = (size_t)3 * w * h, n1 = (size_t)w * h;
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))))
+        return rc;
+    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
+        return rc;
+    unsigned char *dp[3] = {c->d_planes + L.off[0], c->d_planes + L.off[1], c->d_planes + L.off[2]};
+    const size_t pfs[3] = {0, 0, 0};
+    for (int p = 0; p < 3; p++)
+        if ((rc = xfer_h2d_2d(c, dp[p], stride[p], planes[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
+            return rc;
+    uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);
+    float *const fp[3] = {reinterpret_cast<float *>(d16), reinterpret_cast<float *>(d16 + n1), reinterpret_cast<float *>(d16 + 2 * n1)};
+    if ((rc = decode_impl(c, dp, stride, pfs, 1, w, h, profile, sc, fp, nfl, DisplayParams(), cs_eff, false, nullptr, true)))
+        return rc;
+    if ((rc = xfer_d2h(c, rgb_out, d16, nfl * sizeof(uint16_t), c->stream)))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LUMAHIP_OK;
+}
+
 // ---- batched host entry points: a 3-slot software pipeline over three streams.  Frame i's H2D copy runs while
 // frame i-1's kernel and frame i-2's D2H copies are in flight; with pinned caller memory (lumahip_host_register) the
 // two copy directions overlap as well and the rate approaches the PCIe H2D rate.

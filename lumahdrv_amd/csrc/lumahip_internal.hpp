@@ -3,8 +3,10 @@
 //
 //   lumahip_core.hip    context life cycle, quantizer upload, layout checks, memory helpers               (no kernels)
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
-//   lumahip_encode.hip  every k_encode / encode-side instantiation and its dispatch
-//   lumahip_decode.hip  every k_decode instantiation and its dispatch
+//   lumahip_encode.hip  every float-frame k_encode / encode-side instantiation and its dispatch
+//   lumahip_decode.hip  every float-frame k_decode instantiation and its dispatch
+//   lumahip_encode_f16.hip / lumahip_decode_f16.hip  the binary16-frame k_encode<..., IN16> / k_decode<..., OUT16>
+//                       instantiations, their pick functions and the _f16 device entry points (+ the narrowing probe)
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the 3-slot pipeline   (no kernels)
 //   lumahip_pool.hip    the HBM chunk pool;  lumahip_multi.hip  many GPUs in one process                  (no kernels)
@@ -303,27 +305,39 @@ int check_geom(lumahip_ctx *c, unsigned w, unsigned h, int profile, int cs_eff);
 bool make_geom(FrameGeom &g, unsigned w, unsigned h, int vw, int nw, unsigned nframes);
 hipStream_t launch_stream(lumahip_ctx *c, bool lanes);   // the context's stream, or -- for the entry points that take part in unordered sections -- the next lane of an open one
 void plane_dims(unsigned w, unsigned h, int profile, int p, int &rows, int &row_bytes);
-// rgb: the three colour-plane base pointers of the float frames (nullptr: no float frames in this call)
+// rgb: the three colour-plane base pointers of the float frames (nullptr: no float frames in this call); esize: bytes per
+// element of those frames (2: binary16 frames behind the same pointers, frame_stride counting halves)
 int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned nframes, const float *const rgb[3],
-                 size_t frame_stride, const int stride[3], const size_t pfs[3]);
+                 size_t frame_stride, const int stride[3], const size_t pfs[3], size_t esize = sizeof(float));
 
 // ---- lumahip_encode.hip / lumahip_decode.hip: cs_eff = the colour space the kernels run (the context's, or CS_PACK /
 // CS_RGB for the pack-only entry points)
 // rgb[c]: base of colour plane c; plane c of frame f at rgb[c] + f*frame_stride floats
 int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t frame_stride, unsigned nframes,
                               unsigned w, unsigned h, float sc, int profile, unsigned char *const planes[3],
-                              const int stride[3], const size_t pfs[3], float *stats, int cs_eff, bool lanes = false, bool in16 = false);
-// in16: rgb[] point at binary16 planes (the half upload of the host entry points, lumahip_host.hip); same element offsets and
-// strides; LUMAHIP_ERR_UNSUPPORTED unless encode_supports_in16() (records in LDS, rows of a multiple of 4 pixels)
+                              const int stride[3], const size_t pfs[3], float *stats, int cs_eff, bool lanes = false, int in16 = 0);
+// in16: rgb[] point at binary16 planes; same element offsets and strides.  1: the half upload of the host entry points
+// (lumahip_host.hip), LUMAHIP_ERR_UNSUPPORTED unless encode_supports_in16() (records in LDS, rows of a multiple of 4 pixels);
+// 2: frames that are binary16 by type (the _f16 entry points): every search mode and width, the YCbCr half-input table whenever
+// it exists for (sc, maxLum) and no statistics are asked for -- no probe, no feedback, no host wait
+enum : int { IN16_NONE = 0, IN16_UPLOAD = 1, IN16_TYPED = 2 };
 bool encode_supports_in16(lumahip_ctx *c, unsigned w);
 int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
                 unsigned nframes, unsigned w, unsigned h, int profile, float sc, float *const rgb[3], size_t frame_stride,
-                const DisplayParams &dp, int cs_eff, bool lanes = false, float *const rot[3] = nullptr);
+                const DisplayParams &dp, int cs_eff, bool lanes = false, float *const rot[3] = nullptr, bool out16 = false);
+// out16: rgb[] point at binary16 planes (the _f16 entry points; k_decode<..., OUT16>), same element offsets and strides; not with
+// rot or a display output
 // rot: PACKED frames rotating over three buffers, frame f at rot[f % 3] + (f / 3) * frame_stride (rgb is then ignored)
 // lanes: the call is one of the four _device encode / decode entry points and goes to a lane of an open unordered section;
 // every other caller (the _host entry points with their own upload / kernel / download streams, the stream push / pop, the
 // display decode) stays on c->stream whether a section is open or not, as include/lumahip.h promises
 int array_launch(lumahip_ctx *c, const float *d_in, float *d_out, size_t n, unsigned ch, bool quant);
+// ---- lumahip_encode_f16.hip / lumahip_decode_f16.hip: the binary16-frame instantiations (own translation units: they compile
+// side by side with the float ones).  Same selection as the float kernels' pick_enc / pick_dec; nullptr: none for these arguments
+typedef void (*enc_kernel_t)(const lh::EncArgs);
+typedef void (*dec_kernel_t)(const lh::DecArgs);
+enc_kernel_t pick_enc_f16(int cs, bool sub, int vw, int mode);
+dec_kernel_t pick_dec_f16(int cs, bool sub, int vw, bool gl, bool yt, bool rb);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

@@ -123,3 +123,14 @@ class LumaFrameCodec:
     def decode(self, planes, strides, w, h):
         p = self.params
         return self.quant.ctx.decode_frame(planes, strides, w, h, p.preScaling, p.profile)
+
+    def encode_half(self, frame: np.ndarray):
+        """(3,h,w) float16 -> (planes, strides, mean_luminance): the frame crosses to the GPU as halves; the same result as
+        encode() of the frame widened to float32"""
+        p = self.params
+        return self.quant.ctx.encode_frame_f16(frame, p.preScaling, p.profile)
+
+    def decode_half(self, planes, strides, w, h) -> np.ndarray:
+        """-> (3,h,w) float16, decode() narrowed as an EXR writer narrows it (ExrInterface::floatToHalf)"""
+        p = self.params
+        return self.quant.ctx.decode_frame_f16(planes, strides, w, h, p.preScaling, p.profile)
