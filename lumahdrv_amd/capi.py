@@ -73,7 +73,7 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 # device code + launch geometry + compiler flags (NOT the host plumbing: lumahip_core / _host / _pool / _multi, lumahip_internal.hpp)
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
-                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip")
+                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp")
 
 
 def kernel_source_sha() -> str:

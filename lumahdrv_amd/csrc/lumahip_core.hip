@@ -471,7 +471,7 @@ static int upload_table(lumahip_ctx *c)
 // Every monotone finite table gets threshold records (lut_index.hpp): in LDS when they fit lds_table_max, else in global
 // memory (L2-resident).  Anything else (NaNs, decreasing entries -- a decoder may be handed any attachment-434 table) runs
 // the reference's bisection literally; so does everything after lumahip_tune(ctx, "force_literal", 1) (the tests' hook).
-int lhost::ensure_search_index(lumahip_ctx *c)
+int lhost::ensure_search_index(lumahip_ctx *c, hipStream_t s)
 {
     if (c->index_ready)
         return LUMAHIP_OK;
@@ -486,7 +486,7 @@ int lhost::ensure_search_index(lumahip_ctx *c)
             const ThreshIndex &ix = *c->tix;
             std::vector<uint32_t> r((ix.rec.size() + 3) & ~(size_t)3, 0u);
             memcpy(r.data(), ix.rec.data(), ix.rec.size() * sizeof(uint32_t));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipStreamSynchronize(s));
             (void)hipFree(c->d_rec);
             c->d_rec = nullptr;
             HIPCHK(c, hipMalloc(&c->d_rec, r.size() * sizeof(uint32_t)));
@@ -629,7 +629,7 @@ extern "C" int lumahip_quantizer_info(const lumahip_ctx *c, int info[5])
     if (!c->have_quant)
         return LUMAHIP_ERR_STATE;
     lumahip_ctx *m = const_cast<lumahip_ctx *>(c);  // builds the (lazily built) search index if nothing has yet
-    const int rc = ensure_search_index(m);
+    const int rc = ensure_search_index(m, m->stream);
     if (rc)
         return rc;
     const bool ok = c->tix && c->tix->ok;
@@ -755,7 +755,7 @@ extern "C" int lumahip_half_table_info(lumahip_ctx *c, float sc, int info[6])
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = ensure_search_index(c))
+    if (int rc = ensure_search_index(c, c->stream))
         return rc;
     info[0] = info[1] = 0;
     info[3] = HALF_TABLE_LEN;
@@ -1010,10 +1010,10 @@ bool make_geom(FrameGeom &g, unsigned w, unsigned h, int vw, int nw, unsigned nf
 }
 
 // rows and bytes per row of plane p as vpx_img_alloc lays it out (src/luma_encoder.cpp:121-128)
-hipStream_t launch_stream(lumahip_ctx *c, bool lanes)
+hipStream_t launch_stream(lumahip_ctx *c, hipStream_t s, bool lanes)
 {
     if (!lanes || c->lanes_active == 0)
-        return c->stream;
+        return s;
     return c->lane_stream[c->lane_next++ % (unsigned)c->lanes_active];
 }
 
@@ -1027,9 +1027,10 @@ void plane_dims(unsigned w, unsigned h, int profile, int p, int &rows, int &row_
 
 // the device entry points take caller-chosen strides: reject layouts in which rows or frames would overlap or the
 // kernels would write outside a plane (negative / too small strides, frame strides smaller than a frame)
-int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned nframes, const float *const rgb[3],
-                 size_t frame_stride, const int stride[3], const size_t pfs[3], size_t esize)
+int check_layout(lumahip_ctx *c, const SrcFrames &f, bool overlap_test, const int stride[3], const size_t pfs[3], int profile)
 {
+    const unsigned w = f.w, h = f.h, nframes = f.nframes;
+    const size_t frame_stride = f.frame_stride;
     for (int p = 0; p < 3; p++) {
         int rows, row_bytes;
         plane_dims(w, h, profile, p, rows, row_bytes);
@@ -1038,10 +1039,10 @@ int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned n
         if (nframes > 1 && !c->allow_alias && pfs[p] < (size_t)rows * (size_t)stride[p])
             return fail(c, LUMAHIP_ERR_ARG, "plane %d: frame stride %zu < plane size %zu", p, pfs[p], (size_t)rows * stride[p]);
     }
-    if (!rgb || c->allow_alias)
+    if (!overlap_test || c->allow_alias)
         return LUMAHIP_OK;
-    // float frames: colour plane k of frame f covers [rgb[k] + f*frame_stride, + w*h).  No two of the 3*nframes planes may
-    // overlap.  Plane sequence k is the arithmetic progression rgb[k] + f*frame_stride; two sequences are fine when they are
+    // colour plane k of frame i covers [plane[k] + i*frame_stride, + w*h) elements.  No two of the 3*nframes planes may
+    // overlap.  Plane sequence k is the arithmetic progression plane[k] + i*frame_stride; two sequences are fine when they are
     // disjoint as whole ranges (channel-major layouts) or when they interleave with room for each other inside one frame
     // stride (frame-major layouts, the reference's LumaFrame among them).
     const size_t n = (size_t)w * h;
@@ -1050,8 +1051,8 @@ int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned n
     const size_t span = (size_t)(nframes - 1) * frame_stride + n;  // floats one plane sequence covers
     for (int i = 0; i < 3; i++)
         for (int j = i + 1; j < 3; j++) {
-            const uintptr_t x = (uintptr_t)rgb[i], y = (uintptr_t)rgb[j];
-            const size_t d = (size_t)(x < y ? y - x : x - y) / esize;   // (elements)
+            const uintptr_t x = (uintptr_t)f.plane[i], y = (uintptr_t)f.plane[j];
+            const size_t d = (size_t)(x < y ? y - x : x - y) / elem_size(f.elem);   // (elements)
             const bool disjoint = d >= span;
             const bool interleaved = d >= n && (nframes == 1 || d + n <= frame_stride);
             if (!disjoint && !interleaved)

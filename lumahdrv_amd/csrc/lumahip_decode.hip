@@ -1,6 +1,7 @@
 // lumahip_decode.hip -- dispatch of the fused decode kernels (lh::k_decode, luma_kernels.hpp), with and without the display
 // epilogue, and the array forms of quantize / dequantize.
 #include "lumahip_internal.hpp"
+#include "lumahip_pick.hpp"
 
 using namespace lh;
 using namespace lhost;
@@ -87,50 +88,18 @@ __global__ __launch_bounds__(256) void k_build_rb(const RbArgs a)
 
 }  // namespace lh
 
-template <int CS, bool SUB>
-static dec_kernel_t pick_dec2(int vw, bool gl, bool disp, bool yt, bool rb)
-{
-    if constexpr (CS == CS_YCBCR) {
-        if (yt && rb && !gl && !disp)   // + red and blue from the per-stream tables in global memory
-            return vw == 4 ? k_decode<CS, SUB, 4, false, false, true, true> : k_decode<CS, SUB, 2, false, false, true, true>;
-        if (yt && !gl && !disp)   // per-stream y table in LDS
-            return vw == 4 ? k_decode<CS, SUB, 4, false, false, true> : k_decode<CS, SUB, 2, false, false, true>;
-    }
-    if (disp) {
-        if (gl)
-            return k_decode<CS, SUB, 2, true, true>;
-        return vw == 4 ? k_decode<CS, SUB, 4, false, true> : k_decode<CS, SUB, 2, false, true>;
-    }
-    if (gl)
-        return k_decode<CS, SUB, 2, true>;
-    return vw == 4 ? k_decode<CS, SUB, 4, false> : k_decode<CS, SUB, 2, false>;
-}
-
-static dec_kernel_t pick_dec(int cs, bool sub, int vw, bool gl, bool disp, bool yt, bool rb)
-{
-    switch (cs) {
-    case CS_LUV: return sub ? pick_dec2<CS_LUV, true>(vw, gl, disp, yt, rb) : pick_dec2<CS_LUV, false>(vw, gl, disp, yt, rb);
-    case CS_RGB: return sub ? pick_dec2<CS_RGB, true>(vw, gl, disp, yt, rb) : pick_dec2<CS_RGB, false>(vw, gl, disp, yt, rb);
-    case CS_YCBCR: return sub ? pick_dec2<CS_YCBCR, true>(vw, gl, disp, yt, rb) : pick_dec2<CS_YCBCR, false>(vw, gl, disp, yt, rb);
-    case CS_XYZ: return sub ? pick_dec2<CS_XYZ, true>(vw, gl, disp, yt, rb) : pick_dec2<CS_XYZ, false>(vw, gl, disp, yt, rb);
-    case CS_PACK: return sub ? pick_dec2<CS_PACK, true>(vw, gl, disp, yt, rb) : pick_dec2<CS_PACK, false>(vw, gl, disp, yt, rb);
-    }
-    return nullptr;
-}
-
 namespace lhost {
 
 // true when no colour plane of the batch starts inside another one's extent: R, G and B are three buffers, not three
 // sections of packed LumaFrames
-static bool planes_are_separate_buffers(float *const rgb[3], size_t frame_stride, unsigned nframes, unsigned w, unsigned h,
-                                        size_t esize = sizeof(float))
+static bool planes_are_separate_buffers(const DstFrames &f)
 {
-    const size_t extent = ((size_t)(nframes - 1) * frame_stride + (size_t)w * h) * esize;
-    auto apart = [&](const float *p, const float *q) {
+    const size_t extent = ((size_t)(f.nframes - 1) * f.frame_stride + (size_t)f.w * f.h) * elem_size(f.elem);
+    auto apart = [&](const void *p, const void *q) {
         const uintptr_t x = (uintptr_t)p, y = (uintptr_t)q;
         return (x > y ? x - y : y - x) >= extent;
     };
-    return apart(rgb[0], rgb[1]) && apart(rgb[1], rgb[2]) && apart(rgb[0], rgb[2]);
+    return apart(f.plane[0], f.plane[1]) && apart(f.plane[1], f.plane[2]) && apart(f.plane[0], f.plane[2]);
 }
 
 // The device red / blue tables of this call's preScaling (nullptr: not for this stream).  Built by one launch of k_build_rb the
@@ -140,7 +109,7 @@ static bool planes_are_separate_buffers(float *const rgb[3], size_t frame_stride
 // 12-bit colour (2 x 64 MiB) is read as profitably as the HDR10 recipe's 8 MiB; beyond RB_MAX_BYTES the tables are not built.
 static constexpr size_t RB_MAX_BYTES = (size_t)256 << 20;
 
-int rb_table_for(lumahip_ctx *c, float sc, const float **tab)
+int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab)
 {
     *tab = nullptr;
     const size_t n = (size_t)c->q.lut_len, nc = (size_t)c->q.maxC + 1;
@@ -178,9 +147,9 @@ int rb_table_for(lumahip_ctx *c, float sc, const float **tab)
     a.maxC = c->q.maxC;
     a.sc = sc;
     a.Lmax = c->q.Lmax;
-    hipLaunchKernelGGL(k_build_rb, dim3((unsigned)c->num_cu * 8), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_build_rb, dim3((unsigned)c->num_cu * 8), dim3(256), 0, s, a);
     // done when this returns, whatever stream or lane the decode launch goes to
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         (void)hipGetLastError();
         (void)hipFree(t.d);
         c->rb_unavailable = true;
@@ -191,14 +160,21 @@ int rb_table_for(lumahip_ctx *c, float sc, const float **tab)
     return LUMAHIP_OK;
 }
 
-int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
-                unsigned nframes, unsigned w, unsigned h, int profile, float sc, float *const rgb_in[3], size_t frame_stride,
-                const DisplayParams &dp, int cs_eff, bool lanes, float *const rot[3], bool out16)
+int decode_impl(lumahip_ctx *c, const SrcPlanes &p, float sc, const DstFrames &f, const DecodeLaunch &o)
 {
+    const bool out16 = f.elem == Elem::F16;
+    const unsigned nframes = f.nframes, w = f.w, h = f.h;
+    const size_t frame_stride = f.frame_stride;
+    const int profile = p.profile, cs_eff = o.cs_eff;
+    const unsigned char *const *planes = p.planes;
+    const int *stride = p.stride;
+    const size_t *pfs = p.pfs;
+    float *const *rot = o.rot;
+    const DisplayParams dp = o.display ? *o.display : DisplayParams();
     if (out16 && (rot || dp.rgba))
         return fail(c, LUMAHIP_ERR_ARG, "binary16 frames: no rotating layout, no display output");
     // rot: packed frames rotating over three buffers (DecArgs::rot); the checks below then look at buffer 0's first frame
-    float *rot_planes[3] = {nullptr, nullptr, nullptr};
+    DstFrames fr = f;   // the frames the launch writes
     if (rot) {
         if (!rot[0] || !rot[1] || !rot[2] || dp.rgba)
             return fail(c, LUMAHIP_ERR_ARG, "null argument");
@@ -209,8 +185,8 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
         for (int k = 0; k < 3; k++) {
             if (!is_aligned(rot[k], ((w % 4) == 0 && (frame_stride % 4) == 0) ? 16 : 8))
                 return fail(c, LUMAHIP_ERR_ARG, "the three frame buffers must be %d-byte aligned", ((w % 4) == 0 && (frame_stride % 4) == 0) ? 16 : 8);
-            rot_planes[k] = rot[0] + (size_t)k * w * h;
         }
+        fr = packed_frames(rot[0], frame_stride, nframes, w, h);
         if (rot[0] == rot[1] || rot[1] == rot[2] || rot[0] == rot[2])
             return fail(c, LUMAHIP_ERR_ARG, "the three frame buffers must be distinct");
         // buffer k holds frames k, k + 3, ...: ceil((nframes - k) / 3) frames, the last one 3*w*h floats long
@@ -226,22 +202,21 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
                     return fail(c, LUMAHIP_ERR_ARG, "the three frame buffers must not overlap (buffers %d and %d do over this batch)", i, j);
             }
     }
-    float *const *rgb = rot ? rot_planes : rgb_in;
-    const bool have_rgb = rgb && rgb[0];
+    void *const *rgb = fr.plane;
+    const bool have_rgb = rgb[0] != nullptr;
     if (!c || (!have_rgb && !dp.rgba) || (have_rgb && (!rgb[1] || !rgb[2])) || !planes || !stride || !pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     int rc = check_geom(c, w, h, profile, cs_eff);
     if (rc)
         return rc;
-    if ((rc = check_layout(c, w, h, profile, nframes, (have_rgb && !rot) ? rgb : nullptr, frame_stride, stride, pfs,
-                           out16 ? 2 : sizeof(float))))
+    if ((rc = check_layout(c, readonly(fr), have_rgb && !rot, stride, pfs, profile)))
         return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const bool sub = (profile == 0 || profile == 2);
     const int bps = profile > 1 ? 2 : 1;
     const bool gl = !c->lut_in_lds;
-    float *const none[3] = {nullptr, nullptr, nullptr};
-    float *const *out = have_rgb ? rgb : none;
+    void *const none[3] = {nullptr, nullptr, nullptr};
+    void *const *out = have_rgb ? rgb : none;
     // the stores of VW pixels need VW-element alignment: VW = 4 where possible, VW = 2 always (float frames 16 / 8 bytes,
     // binary16 frames 8 / 4 bytes)
     const size_t esz = out16 ? 2 : 4;
@@ -264,8 +239,10 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     const int threads = block_threads_for(c, lds, false, cs_eff == CS_YCBCR);
     if (!make_geom(a.g, w, h, vw, threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
+    // DecArgs::dst is typed for float frames; the OUT16 kernels store binary16 through the same pointers, and every offset
+    // counts elements.  This is the one place where the element type leaves the pointer: f.elem chooses the kernel table below
     for (int k = 0; k < 3; k++)
-        a.dst[k] = out[k];
+        a.dst[k] = static_cast<float *>(out[k]);
     if (rot) {
         for (int k = 0; k < 3; k++)
             a.rot[k] = rot[k];
@@ -296,7 +273,7 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     a.q.cs = cs_eff;
     const float *rb = nullptr;
     uint32_t *rb_flag = nullptr;   // this launch's feedback word (LagPolicy)
-    if (yt && (rc = rb_table_for(c, sc, &rb)))
+    if (yt && (rc = rb_table_for(c, sc, o.stream, &rb)))
         return rc;
     // mode 1: the kernels with the tables test every wave's codes for locality first (rb_wave_local); on a stream none of whose
     // waves ever passes, that test and the larger kernel cost 3-4 % for nothing, so launches that report no gathers send the
@@ -311,7 +288,7 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     if (rb)
         c->rb_launches++;
     dec_kernel_t kern = out16 ? pick_dec_f16(cs_eff, sub, vw, gl, yt, rb != nullptr)
-                              : pick_dec(cs_eff, sub, vw, gl, dp.rgba != nullptr, yt, rb != nullptr);
+                              : pick_dec<false>(cs_eff, sub, vw, gl, dp.rgba != nullptr, yt, rb != nullptr);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no decode kernel for colour space %d%s", cs_eff, out16 ? " with binary16 frames" : "");
     LagLaunchGuard rb_guard{c->rb_pol, rb_flag};   // (a return before the launch takes the word back: the policy must not wait for it)
@@ -321,10 +298,10 @@ int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int 
     // colour planes of the batch are separate buffers (no plane starts inside another plane's extent over the batch) -- the layout
     // a caller uses to spread the three write streams over the HBM region groups (lumahip_decode_frames_device_planar)
     int few_writers = (sub && bps == 2 && cs_eff != CS_YCBCR && dp.rgba == nullptr) ? 1 : 0;
-    if (few_writers && have_rgb && (rot || planes_are_separate_buffers(rgb, frame_stride, nframes, w, h, esz)))
+    if (few_writers && have_rgb && (rot || planes_are_separate_buffers(fr)))
         few_writers = 2;
     const int grid = grid_for(c, threads, a.g.totalTiles, 1, few_writers, cs_eff == CS_YCBCR);
-    hipStream_t s = launch_stream(c, lanes);
+    hipStream_t s = launch_stream(c, o.stream, o.lanes);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
     rb_guard.launched = true;
     if (rb_flag && (rc = lag_policy_launched(c, c->rb_pol, s)))
@@ -338,7 +315,7 @@ int array_launch(lumahip_ctx *c, const float *d_in, float *d_out, size_t n, unsi
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (quant)
-        if (int rc = ensure_search_index(c))
+        if (int rc = ensure_search_index(c, c->stream))
             return rc;
     QArrArgs a{};
     a.q = c->q;
@@ -381,7 +358,7 @@ extern "C" int lumahip_rb_table_info(lumahip_ctx *c, float sc, int info[4])
     HIPCHK(c, hipSetDevice(c->device));
     const float *t = nullptr;
     if (c->q.cs == CS_YCBCR && c->q.ytab && c->lut_in_lds)
-        if (int rc = lhost::rb_table_for(c, sc, &t))
+        if (int rc = lhost::rb_table_for(c, sc, c->stream, &t))
             return rc;
     info[0] = t != nullptr;
     info[1] = t ? (int)(2 * (size_t)c->q.lut_len * ((size_t)c->q.maxC + 1) * sizeof(float)) : 0;
@@ -398,9 +375,7 @@ extern "C" int lumahip_decode_frames_device(lumahip_ctx *c, const unsigned char 
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     if (!c)
         return LUMAHIP_ERR_ARG;
-    const size_t n = (size_t)w * h;
-    float *const pl[3] = {rgb, rgb + n, rgb + 2 * n};
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, pl, frame_stride, DisplayParams(), c->q.cs, true);
+    return decode_impl(c, {planes, stride, pfs, profile}, sc, packed_frames(rgb, frame_stride, nframes, w, h), {c->q.cs, c->stream, true});
 }
 
 extern "C" int lumahip_decode_frames_device_rotating(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3],
@@ -411,7 +386,8 @@ extern "C" int lumahip_decode_frames_device_rotating(lumahip_ctx *c, const unsig
         return LUMAHIP_ERR_ARG;
     if (!bases)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, nullptr, frame_stride, DisplayParams(), c->q.cs, true, bases);
+    return decode_impl(c, {planes, stride, pfs, profile}, sc, packed_frames<float>(nullptr, frame_stride, nframes, w, h),
+                       {c->q.cs, c->stream, true, bases});
 }
 
 extern "C" int lumahip_decode_frames_device_planar(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3],
@@ -422,7 +398,7 @@ extern "C" int lumahip_decode_frames_device_planar(lumahip_ctx *c, const unsigne
         return LUMAHIP_ERR_ARG;
     if (!rgb_planes || !rgb_planes[0])
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, rgb_planes, frame_stride, DisplayParams(), c->q.cs, true);
+    return decode_impl(c, {planes, stride, pfs, profile}, sc, planar_frames(rgb_planes, frame_stride, nframes, w, h), {c->q.cs, c->stream, true});
 }
 
 // Traffic probe: the loads and stores of k_decode<., 4:2:0, VW=4> for 16-bit planes with NO arithmetic (an xor keeps every
@@ -488,7 +464,7 @@ extern "C" int lumahip_probe_decode_traffic_device(lumahip_ctx *c, const unsigne
         a.stride[p] = stride[p];
         a.src_frame_stride[p] = pfs[p];
     }
-    const int grid = grid_for(c, threads, a.g.totalTiles, 1, planes_are_separate_buffers(rgb_planes, frame_stride, nframes, w, h) ? 2 : 1, false);
+    const int grid = grid_for(c, threads, a.g.totalTiles, 1, planes_are_separate_buffers(planar_frames(rgb_planes, frame_stride, nframes, w, h)) ? 2 : 1, false);
     EventPair ev;
     HIPCHK(c, ev.create());
     HIPCHK(c, hipEventRecord(ev.e0, c->stream));
@@ -522,9 +498,8 @@ extern "C" int lumahip_decode_display_frames_device(lumahip_ctx *c, const unsign
     dp.gamma = gamma;
     dp.do_tmo = do_tmo;
     dp.ldr_sim = ldr_sim;
-    const size_t n = (size_t)w * h;
-    float *const pl[3] = {rgb_or_null, rgb_or_null ? rgb_or_null + n : nullptr, rgb_or_null ? rgb_or_null + 2 * n : nullptr};
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, pl, frame_stride, dp, c->q.cs);
+    return decode_impl(c, {planes, stride, pfs, profile}, sc, packed_frames(rgb_or_null, frame_stride, nframes, w, h),
+                       {c->q.cs, c->stream, false, nullptr, &dp});
 }
 
 extern "C" int lumahip_quantize_array_device(lumahip_ctx *c, const float *in_dev, float *out_dev, size_t n, unsigned ch)

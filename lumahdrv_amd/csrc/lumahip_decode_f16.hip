@@ -2,38 +2,13 @@
 // points lumahip_decode_frames_device_f16 / _planar_f16 and the narrowing probe.  Their own translation unit so that they
 // compile side by side with the float kernels of lumahip_decode.hip.
 #include "lumahip_internal.hpp"
+#include "lumahip_pick.hpp"
 
 using namespace lh;
 using namespace lhost;
 
-// The non-display choices of pick_dec2 (lumahip_decode.hip), with binary16 stores
-template <int CS, bool SUB>
-static dec_kernel_t pick_dec2_f16(int vw, bool gl, bool yt, bool rb)
-{
-    if constexpr (CS == CS_YCBCR) {
-        if (yt && rb && !gl)
-            return vw == 4 ? k_decode<CS, SUB, 4, false, false, true, true, true> : k_decode<CS, SUB, 2, false, false, true, true, true>;
-        if (yt && !gl)
-            return vw == 4 ? k_decode<CS, SUB, 4, false, false, true, false, true> : k_decode<CS, SUB, 2, false, false, true, false, true>;
-    }
-    if (gl)
-        return k_decode<CS, SUB, 2, true, false, false, false, true>;
-    return vw == 4 ? k_decode<CS, SUB, 4, false, false, false, false, true> : k_decode<CS, SUB, 2, false, false, false, false, true>;
-}
-
 namespace lhost {
-
-dec_kernel_t pick_dec_f16(int cs, bool sub, int vw, bool gl, bool yt, bool rb)
-{
-    switch (cs) {
-    case CS_LUV: return sub ? pick_dec2_f16<CS_LUV, true>(vw, gl, yt, rb) : pick_dec2_f16<CS_LUV, false>(vw, gl, yt, rb);
-    case CS_RGB: return sub ? pick_dec2_f16<CS_RGB, true>(vw, gl, yt, rb) : pick_dec2_f16<CS_RGB, false>(vw, gl, yt, rb);
-    case CS_YCBCR: return sub ? pick_dec2_f16<CS_YCBCR, true>(vw, gl, yt, rb) : pick_dec2_f16<CS_YCBCR, false>(vw, gl, yt, rb);
-    case CS_XYZ: return sub ? pick_dec2_f16<CS_XYZ, true>(vw, gl, yt, rb) : pick_dec2_f16<CS_XYZ, false>(vw, gl, yt, rb);
-    }
-    return nullptr;   // (CS_PACK: the unpack-only decode writes dequantized floats; no _f16 entry point runs it)
-}
-
+dec_kernel_t pick_dec_f16(int cs, bool sub, int vw, bool gl, bool yt, bool rb) { return pick_dec<true>(cs, sub, vw, gl, false, yt, rb); }
 }  // namespace lhost
 
 extern "C" int lumahip_decode_frames_device_f16(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3],
@@ -46,10 +21,7 @@ extern "C" int lumahip_decode_frames_device_f16(lumahip_ctx *c, const unsigned c
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
-    const size_t n = (size_t)w * h;
-    // (halves behind float pointers: the kernels store them as binary16, all offsets count elements)
-    float *const pl[3] = {reinterpret_cast<float *>(rgb), reinterpret_cast<float *>(rgb + n), reinterpret_cast<float *>(rgb + 2 * n)};
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, pl, frame_stride, DisplayParams(), c->q.cs, true, nullptr, true);
+    return decode_impl(c, {planes, stride, pfs, profile}, sc, packed_frames(rgb, frame_stride, nframes, w, h), {c->q.cs, c->stream, true});
 }
 
 extern "C" int lumahip_decode_frames_device_planar_f16(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3],
@@ -62,9 +34,7 @@ extern "C" int lumahip_decode_frames_device_planar_f16(lumahip_ctx *c, const uns
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
-    float *const pl[3] = {reinterpret_cast<float *>(rgb_planes[0]), reinterpret_cast<float *>(rgb_planes[1]),
-                          reinterpret_cast<float *>(rgb_planes[2])};
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, pl, frame_stride, DisplayParams(), c->q.cs, true, nullptr, true);
+    return decode_impl(c, {planes, stride, pfs, profile}, sc, planar_frames(rgb_planes, frame_stride, nframes, w, h), {c->q.cs, c->stream, true});
 }
 
 // ---- test probe: the decode kernels' narrowing (f16_narrow) of n consecutive fp32 bit patterns ----

@@ -1,6 +1,7 @@
 // lumahip_encode.hip -- dispatch of the fused encode kernels (lh::k_encode, luma_kernels.hpp) and of the other encode-side
 // instantiations: array quantize, the search probe, the traffic-only probe.
 #include "lumahip_internal.hpp"
+#include "lumahip_pick.hpp"
 
 using namespace lh;
 using namespace lhost;
@@ -40,50 +41,6 @@ __global__ __launch_bounds__(256) void k_encode_traffic_probe(const EncArgs a)
 
 }  // namespace lh
 
-template <int CS, bool SUB>
-static enc_kernel_t pick_enc2(int vw, int mode)
-{
-    if constexpr (CS == CS_YCBCR) {
-        if (mode == 5)   // composite luma -> code records (vw == 4 or 2 as for the records)
-            return vw == 4 ? k_encode<CS, SUB, 4, 5> : k_encode<CS, SUB, 2, 5>;
-        if (mode == 6)   // the same + the half-input table
-            return vw == 4 ? k_encode<CS, SUB, 4, 6> : k_encode<CS, SUB, 2, 6>;
-    }
-    if (mode == LUT_THRESH_LDS)
-        return vw == 4 ? k_encode<CS, SUB, 4, 3> : k_encode<CS, SUB, 2, 3>;
-    if (mode == LUT_THRESH_GLOBAL)
-        return vw == 4 ? k_encode<CS, SUB, 4, 4> : k_encode<CS, SUB, 2, 4>;
-    if (mode == LUT_LINKEY_LDS)
-        return vw == 4 ? k_encode<CS, SUB, 4, 7> : k_encode<CS, SUB, 2, 7>;
-    if (mode == LUT_LITERAL_LDS)
-        return k_encode<CS, SUB, 2, 0>;
-    return k_encode<CS, SUB, 2, 2>;
-}
-
-// binary16 frames: the records-in-LDS kernels at four pixels per thread only (what the host entry points' half upload needs)
-static enc_kernel_t pick_enc_in16(int cs, bool sub)
-{
-    switch (cs) {
-    case CS_LUV: return sub ? k_encode<CS_LUV, true, 4, 3, true> : k_encode<CS_LUV, false, 4, 3, true>;
-    case CS_RGB: return sub ? k_encode<CS_RGB, true, 4, 3, true> : k_encode<CS_RGB, false, 4, 3, true>;
-    case CS_YCBCR: return sub ? k_encode<CS_YCBCR, true, 4, 3, true> : k_encode<CS_YCBCR, false, 4, 3, true>;
-    case CS_XYZ: return sub ? k_encode<CS_XYZ, true, 4, 3, true> : k_encode<CS_XYZ, false, 4, 3, true>;
-    }
-    return nullptr;   // (CS_PACK: frames that are already colour-transformed do not hold halves; never asked for)
-}
-
-static enc_kernel_t pick_enc(int cs, bool sub, int vw, int mode)
-{
-    switch (cs) {
-    case CS_LUV: return sub ? pick_enc2<CS_LUV, true>(vw, mode) : pick_enc2<CS_LUV, false>(vw, mode);
-    case CS_RGB: return sub ? pick_enc2<CS_RGB, true>(vw, mode) : pick_enc2<CS_RGB, false>(vw, mode);
-    case CS_YCBCR: return sub ? pick_enc2<CS_YCBCR, true>(vw, mode) : pick_enc2<CS_YCBCR, false>(vw, mode);
-    case CS_XYZ: return sub ? pick_enc2<CS_XYZ, true>(vw, mode) : pick_enc2<CS_XYZ, false>(vw, mode);
-    case CS_PACK: return sub ? pick_enc2<CS_PACK, true>(vw, mode) : pick_enc2<CS_PACK, false>(vw, mode);
-    }
-    return nullptr;
-}
-
 // partial triples {0, +inf, -inf}: nframes * STATS_SLOTS of them
 __global__ void k_init_stats(float *s, int n)
 {
@@ -115,35 +72,40 @@ __global__ void k_fold_stats(const float *part, float *out, int nframes)
 
 namespace lhost {
 
-int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t frame_stride, unsigned nframes,
-                              unsigned w, unsigned h, float sc, int profile, unsigned char *const planes[3],
-                              const int stride[3], const size_t pfs[3], float *stats, int cs_eff, bool lanes, int in16)
+int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const DstPlanes &p, float *stats, const EncodeLaunch &o)
 {
-    const bool typed16 = in16 == IN16_TYPED;
-    if (!c || !rgb || !rgb[0] || !rgb[1] || !rgb[2] || !planes || !stride || !pfs || nframes == 0)
+    const bool in16 = f.elem == Elem::F16;
+    const bool typed16 = in16 && o.halves == HalfSource::Typed, upload16 = in16 && o.halves == HalfSource::Upload;
+    const unsigned nframes = f.nframes, w = f.w, h = f.h;
+    const size_t frame_stride = f.frame_stride;
+    const int profile = p.profile, cs_eff = o.cs_eff;
+    unsigned char *const *planes = p.planes;
+    const int *stride = p.stride;
+    const size_t *pfs = p.pfs;
+    const void *const *rgb = f.plane;
+    if (!c || !rgb[0] || !rgb[1] || !rgb[2] || !planes || !stride || !pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     int rc = check_geom(c, w, h, profile, cs_eff);
     if (rc)
         return rc;
-    // (binary16 frames come from this library's own staging code: the overlap test of the float planes, which measures in floats, is skipped)
-    if ((rc = check_layout(c, w, h, profile, nframes, in16 == IN16_UPLOAD ? nullptr : rgb, frame_stride, stride, pfs,
-                           typed16 ? 2 : sizeof(float))))
+    // (uploaded halves sit in this library's own staging buffers: the overlap test of the colour planes is skipped)
+    if ((rc = check_layout(c, f, !upload16, stride, pfs, profile)))
         return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_search_index(c)))
+    if ((rc = ensure_search_index(c, o.stream)))
         return rc;
     const bool sub = (profile == 0 || profile == 2);
     const int bps = profile > 1 ? 2 : 1;
     const int mode = c->q.mode;
     const bool fast_search = (mode == LUT_THRESH_LDS || mode == LUT_THRESH_GLOBAL || mode == LUT_LINKEY_LDS);
     // the loads of VW pixels need VW-element alignment: VW = 4 where possible, VW = 2 always (float frames 16 / 8 bytes, binary16
-    // frames by type 8 / 4 bytes)
+    // frames by type 8 / 4 bytes; uploaded halves are held to the float rule: they lie at the float frame's element offsets)
     const size_t esz = typed16 ? 2 : 4;
     const bool al4 = is_aligned(rgb[0], 4 * esz) && is_aligned(rgb[1], 4 * esz) && is_aligned(rgb[2], 4 * esz);
     int vw = (fast_search && (w % 4) == 0 && al4 && (frame_stride % 4) == 0) ? 4 : 2;
     if (!is_aligned(rgb[0], 2 * esz) || !is_aligned(rgb[1], 2 * esz) || !is_aligned(rgb[2], 2 * esz) || (frame_stride % 2) != 0)
         return fail(c, LUMAHIP_ERR_ARG, "colour planes must be %d-byte aligned and the frame stride even", (int)(2 * esz));
-    if (in16 == IN16_UPLOAD) {   // halves: 8-byte loads of four pixels
+    if (upload16) {   // halves: 8-byte loads of four pixels
         if (mode != LUT_THRESH_LDS || (w % 4) != 0 || (frame_stride % 4) != 0)
             return fail(c, LUMAHIP_ERR_UNSUPPORTED, "binary16 frames need the luminance records in LDS and rows of a multiple of 4 pixels");
         vw = 4;
@@ -176,8 +138,10 @@ int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t 
     const int threads = block_threads_for(c, lds, long_launch && cs_eff != CS_YCBCR, cs_eff == CS_YCBCR && !half);
     if (!make_geom(a.g, w, h, vw, threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
+    // EncArgs::src is typed for float frames; the IN16 kernels read the same pointers as _Float16, and every offset counts
+    // elements.  This is the one place where the element type leaves the pointer: f.elem chose the kernel table below
     for (int k = 0; k < 3; k++)
-        a.src[k] = rgb[k];
+        a.src[k] = static_cast<const float *>(rgb[k]);
     a.frame_stride = frame_stride;
     a.sc = sc;
     a.bps = bps;
@@ -195,14 +159,13 @@ int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t 
     }
     a.q.cs = cs_eff;
     const int kmode = half ? 6 : ycode ? 5 : mode;
-    enc_kernel_t kern = in16 == IN16_UPLOAD ? pick_enc_in16(cs_eff, sub) : typed16 ? pick_enc_f16(cs_eff, sub, vw, kmode)
-                                                                                   : pick_enc(cs_eff, sub, vw, kmode);
+    enc_kernel_t kern = in16 ? pick_enc_f16(cs_eff, sub, vw, kmode) : pick_enc<false>(cs_eff, sub, vw, kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no encode kernel for colour space %d%s", cs_eff, in16 ? " with binary16 frames" : "");
     if (lds > 64 * 1024)
         HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int grid = grid_for(c, threads, a.g.totalTiles, 0, 0, half ? 2 : cs_eff == CS_YCBCR ? 1 : 0);
-    hipStream_t s = launch_stream(c, lanes);
+    hipStream_t s = launch_stream(c, o.stream, o.lanes);
     if (stats) {
         // partial triples live in a context-owned scratch buffer; launches with statistics of one context share it, which is
         // safe on one stream (in order) and is why an unordered section with statistics keeps to its first lane
@@ -215,7 +178,7 @@ int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t 
             HIPCHK(c, hipMalloc(&c->d_stats_part, need));
             c->d_stats_part_cap = need;
         }
-        if (lanes && c->lanes_active)
+        if (o.lanes && c->lanes_active)
             s = c->lane_stream[0];
         a.stats = c->d_stats_part;
         const int np = (int)nframes * STATS_SLOTS;
@@ -233,7 +196,7 @@ int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t 
 
 bool encode_supports_in16(lumahip_ctx *c, unsigned w)
 {
-    return ensure_search_index(c) == LUMAHIP_OK && c->q.mode == LUT_THRESH_LDS && (w % 4) == 0;
+    return ensure_search_index(c, c->stream) == LUMAHIP_OK && c->q.mode == LUT_THRESH_LDS && (w % 4) == 0;
 }
 
 }  // namespace lhost
@@ -247,9 +210,8 @@ extern "C" int lumahip_encode_frames_device(lumahip_ctx *c, const float *rgb, si
         return LUMAHIP_ERR_ARG;
     if (!rgb)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const size_t n = (size_t)w * h;
-    const float *const pl[3] = {rgb, rgb + n, rgb + 2 * n};
-    return encode_frames_device_impl(c, pl, frame_stride, nframes, w, h, sc, profile, planes, stride, pfs, stats, c->q.cs, true);
+    return encode_frames_device_impl(c, packed_frames(rgb, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, stats,
+                                     {c->q.cs, c->stream, true});
 }
 
 extern "C" int lumahip_encode_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], size_t frame_stride,
@@ -259,7 +221,8 @@ extern "C" int lumahip_encode_frames_device_planar(lumahip_ctx *c, const float *
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    return encode_frames_device_impl(c, rgb_planes, frame_stride, nframes, w, h, sc, profile, planes, stride, pfs, stats, c->q.cs, true);
+    return encode_frames_device_impl(c, planar_frames(rgb_planes, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, stats,
+                                     {c->q.cs, c->stream, true});
 }
 
 extern "C" int lumahip_probe_encode_traffic_device(lumahip_ctx *c, const float *rgb, size_t frame_stride, unsigned nframes,
@@ -310,7 +273,7 @@ extern "C" int lumahip_quantize_probe_device(lumahip_ctx *c, uint16_t *out_dev, 
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = ensure_search_index(c))
+    if (int rc = ensure_search_index(c, c->stream))
         return rc;
     const size_t lds = lds_bytes(c, true, CS_PACK);
     void (*kern)(const QuantDev, uint16_t *, uint32_t, size_t) = nullptr;
@@ -375,7 +338,7 @@ extern "C" int lumahip_ycbcr_luma_probe_device(lumahip_ctx *c, uint16_t *out_dev
     if (!c->have_quant || c->q.cs != CS_YCBCR)
         return fail(c, LUMAHIP_ERR_STATE, "the probe needs a YCbCr quantizer");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = ensure_search_index(c))
+    if (int rc = ensure_search_index(c, c->stream))
         return rc;
     if (!ycbcr_composite_ready(c))
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no composite luma -> code records for this table");

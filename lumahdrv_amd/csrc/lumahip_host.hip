@@ -10,32 +10,11 @@
 using namespace lh;
 using namespace lhost;
 
-// The fused kernels on packed frames for the entry points of this file: always on c->stream (which the callers point at their
-// kernel stream), never on a lane of an open unordered section -- the uploads and downloads around them are ordered against
-// that stream's events (include/lumahip.h: only the four _device encode / decode entry points take part in a section).
-static int encode_packed(lumahip_ctx *c, const float *rgb, size_t frame_stride, unsigned nframes, unsigned w, unsigned h, float sc,
-                         int profile, unsigned char *const planes[3], const int stride[3], const size_t pfs[3], float *stats)
-{
-    const size_t n = (size_t)w * h;
-    const float *const pl[3] = {rgb, rgb + n, rgb + 2 * n};
-    return encode_frames_device_impl(c, pl, frame_stride, nframes, w, h, sc, profile, planes, stride, pfs, stats, c->q.cs, false);
-}
-// the same for a frame that was uploaded as binary16 (xfer_h2d_f16): planes at the same element offsets behind a pointer to halves
-static int encode_packed16(lumahip_ctx *c, const void *halves, size_t frame_stride, unsigned nframes, unsigned w, unsigned h, float sc,
-                           int profile, unsigned char *const planes[3], const int stride[3], const size_t pfs[3], float *stats)
-{
-    const size_t n = (size_t)w * h;
-    const uint16_t *b = static_cast<const uint16_t *>(halves);
-    const float *const pl[3] = {reinterpret_cast<const float *>(b), reinterpret_cast<const float *>(b + n), reinterpret_cast<const float *>(b + 2 * n)};
-    return encode_frames_device_impl(c, pl, frame_stride, nframes, w, h, sc, profile, planes, stride, pfs, stats, c->q.cs, false, true);
-}
-static int decode_packed(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
-                         unsigned nframes, unsigned w, unsigned h, int profile, float sc, float *rgb, size_t frame_stride)
-{
-    const size_t n = (size_t)w * h;
-    float *const pl[3] = {rgb, rgb + n, rgb + 2 * n};
-    return decode_impl(c, planes, stride, pfs, nframes, w, h, profile, sc, pl, frame_stride, DisplayParams(), c->q.cs, false);
-}
+// The fused kernels run on the stream an entry point of this file names in its launch options -- the context's stream, or the
+// kernel stream of its pipeline -- and never on a lane of an open unordered section: the uploads and downloads around them are
+// ordered against that stream's events (include/lumahip.h: only the four _device encode / decode entry points take part in a
+// section).  Frames in the staging buffers are packed, one per launch, their code planes back to back (no frame stride).
+static const size_t NO_PFS[3] = {0, 0, 0};
 
 // ---- host <-> device transfers of the _host entry points --------------------------------------------------------
 // Caller memory is pageable unless the caller pinned it (hipHostMalloc, hipHostRegister / lumahip_host_register).
@@ -96,7 +75,7 @@ struct lumahip_copy_pool {
     void run_job(const Job &j)
     {
         if (j.to_half) {
-            if (!lh::convert_f32_to_f16_checked(reinterpret_cast<const float *>(j.src), reinterpret_cast<uint16_t *>(j.dst), j.width / 4))
+            if (!lh::convert_f32_to_f16_checked(static_cast<const float *>(static_cast<const void *>(j.src)), static_cast<uint16_t *>(static_cast<void *>(j.dst)), j.width / 4))
                 inexact.store(true, std::memory_order_relaxed);
             return;
         }
@@ -608,6 +587,40 @@ static void plane_layout(PlaneLayout &L, unsigned w, unsigned h, int profile, co
     L.total = off;
 }
 
+// the first plane that is null or whose stride is below its row bytes; -1: none
+static int bad_plane(const PlaneLayout &L, const unsigned char *const planes[3], const int stride[3])
+{
+    for (int p = 0; p < 3; p++)
+        if (!planes[p] || stride[p] < L.row_bytes[p])
+            return p;
+    return -1;
+}
+
+// What the single-frame host calls open with: the arguments checked, the plane layout, the context's staging buffers large
+// enough for one w x h frame of floats (binary16 frames share them) and its planes, dp[] = the device planes
+static int frame_staging(lumahip_ctx *c, const void *frame, const unsigned char *const planes[3], const int stride[3], unsigned w,
+                         unsigned h, int profile, int cs_eff, PlaneLayout &L, unsigned char *dp[3])
+{
+    if (!c || !frame || !planes || !stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    int rc = check_geom(c, w, h, profile, cs_eff);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    plane_layout(L, w, h, profile, stride);
+    const int p = bad_plane(L, planes, stride);
+    if (p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, (size_t)3 * w * h * sizeof(float))))
+        return rc;
+    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
+        return rc;
+    for (int k = 0; k < 3; k++)
+        dp[k] = c->d_planes + L.off[k];
+    return LUMAHIP_OK;
+}
+
 // The reference warns when its (sequentially summed) mean luminance is <= 1.  That fp32 sum is far from the true sum on
 // large frames: once the running sum S is large, addends below ulp(S)/2 vanish and the rest are rounded to multiples of
 // ulp(S) (measured: -0.2 % at 1080p, several % at 4K on wide-range content), whereas the kernels' statistic (per-wave
@@ -676,48 +689,39 @@ static int band_events(lumahip_ctx *c, int nb)
     return LUMAHIP_OK;
 }
 
-static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+// rgb: the caller's frame, floats or -- elem == F16, lumahip_encode_frame_host_f16 -- halves by type.  Halves by type go up as
+// they are, 6 B per pixel, in one piece on the context's stream: no row bands, no round-trip test, none of the half upload's
+// bookkeeping (in16_try / in16_result)
+static int encode_frame_host_impl(lumahip_ctx *c, const void *rgb_any, Elem elem, unsigned w, unsigned h, float sc, int profile,
                                   unsigned char *const planes[3], const int stride[3], float *mean_lum,
                                   float *transformed_out, int cs_eff)
 {
-    if (!c || !rgb || !planes || !stride)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, cs_eff);
-    if (rc)
-        return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    const int bps = profile > 1 ? 2 : 1;
     PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    for (int p = 0; p < 3; p++)
-        if (!planes[p] || stride[p] < L.row_bytes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
-    (void)bps;
-    const size_t nfl = (size_t)3 * w * h;
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))))
-        return rc;
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
+    unsigned char *dp[3];
+    int rc = frame_staging(c, rgb_any, planes, stride, w, h, profile, cs_eff, L, dp);
+    if (rc)
         return rc;
     if (!c->d_stats)
         HIPCHK(c, hipMalloc(&c->d_stats, 3 * sizeof(float)));
-    unsigned char *dp[3] = {c->d_planes + L.off[0], c->d_planes + L.off[1], c->d_planes + L.off[2]};
-    const size_t pfs[3] = {0, 0, 0};
+    const bool typed16 = elem == Elem::F16;
+    const float *const rgb = typed16 ? nullptr : static_cast<const float *>(rgb_any);
+    const size_t nfl = (size_t)3 * w * h;
     const size_t n1 = (size_t)w * h;
     const bool sub = (profile == 0 || profile == 2);
     unsigned band0[lumahip_ctx::MAX_BANDS + 1];
-    const int nb = band_plan(c, w, h, band0);
+    const int nb = typed16 ? 1 : band_plan(c, w, h, band0);
     float st[3] = {0.0f, __builtin_inff(), -__builtin_inff()};
     // Half upload (xfer_h2d_f16): tried unless the caller wants the transformed FLOAT frame back.  frame16: every band so far went
     // up as halves; mixed: some did and then a band held other values -- the device frame is then not usable as a whole.
     // (nor for frames that are already colour-transformed -- lumahip_pack_frame_host: such values are never halves)
-    bool use16 = in16_try(c, w, transformed_out != nullptr || cs_eff == CS_PACK), frame16 = use16, mixed = false;
+    bool use16 = !typed16 && in16_try(c, w, transformed_out != nullptr || cs_eff == CS_PACK), frame16 = use16 || typed16, mixed = false;
     const bool tried16 = use16;
+    uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);   // the staging frame when it holds halves: same element offsets
+    auto staged = [&]() -> SrcFrames { return frame16 ? packed_frames<const uint16_t>(d16, nfl, 1, w, h) : packed_frames<const float>(c->d_frame, nfl, 1, w, h); };
     if (nb > 1) {
         if ((rc = pipe_streams(c)) || (rc = band_events(c, nb)))
             return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));   // the bands run on the pipeline streams: after everything queued so far
-        hipStream_t saved = c->stream;
         DnGuard dn_guard{c, false, 0};   // a failing exit below drops the download chunks still pointing at the caller's planes
         auto fetch = [&](int k) -> int {              // planes rows of band k, after its kernel
             const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
@@ -733,7 +737,6 @@ static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, 
         for (int k = 0; k < nb && rc == LUMAHIP_OK; k++) {
             const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
             const size_t roff = (size_t)r0 * w;
-            uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);
             if (use16) {
                 bool exact = true;
                 for (int ch = 0; ch < 3 && rc == LUMAHIP_OK && exact; ch++)
@@ -756,17 +759,11 @@ static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, 
             }
             HIPCHK(c, hipEventRecord(c->band_h2d[k], c->s_h2d));
             HIPCHK(c, hipStreamWaitEvent(c->s_kern, c->band_h2d[k], 0));
-            // (binary16 planes: the same element offsets behind a pointer to halves)
-            const float *const fp[3] = {use16 ? reinterpret_cast<const float *>(d16 + roff) : c->d_frame + roff,
-                                        use16 ? reinterpret_cast<const float *>(d16 + n1 + roff) : c->d_frame + n1 + roff,
-                                        use16 ? reinterpret_cast<const float *>(d16 + 2 * n1 + roff) : c->d_frame + 2 * n1 + roff};
             unsigned char *bp[3];
             for (int p = 0; p < 3; p++)
                 bp[p] = dp[p] + (size_t)((p && sub) ? r0 / 2 : r0) * stride[p];
-            c->stream = c->s_kern;
-            rc = encode_frames_device_impl(c, fp, nfl, 1, w, rows, sc, profile, bp, stride, pfs, c->d_band_stats + 3 * k, cs_eff, false, use16);
-            c->stream = saved;
-            if (rc)
+            if ((rc = encode_frames_device_impl(c, row_band(staged(), r0, rows), sc, {bp, stride, NO_PFS, profile}, c->d_band_stats + 3 * k,
+                                                {cs_eff, c->s_kern, false, HalfSource::Upload})))
                 break;
             HIPCHK(c, hipEventRecord(c->band_kern[k], c->s_kern));
             if (k >= 1)
@@ -778,7 +775,6 @@ static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, 
             rc = rc ? rc : r;
         else
             dn_guard.armed = false;
-        c->stream = saved;
         HIPCHK(c, hipStreamSynchronize(c->s_h2d));
         HIPCHK(c, hipStreamSynchronize(c->s_kern));
         HIPCHK(c, hipStreamSynchronize(c->s_d2h));
@@ -793,7 +789,8 @@ static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, 
             st[2] = fmaxf(st[2], bs[3 * k + 2]);
         }
     } else {
-        uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);
+        if (typed16 && (rc = xfer_h2d(c, d16, rgb_any, nfl * sizeof(uint16_t), c->stream)))
+            return rc;
         if (use16) {
             bool exact = true;
             if ((rc = xfer_h2d_f16(c, d16, rgb, nfl, c->stream, &exact)))
@@ -801,12 +798,10 @@ static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, 
             if (!exact)
                 use16 = frame16 = false;   // (nothing has been launched on the halves: the floats simply follow on the same stream)
         }
-        if (!use16 && (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))
+        if (!frame16 && (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))
             return rc;
-        const float *const fp[3] = {use16 ? reinterpret_cast<const float *>(d16) : c->d_frame,
-                                    use16 ? reinterpret_cast<const float *>(d16 + n1) : c->d_frame + n1,
-                                    use16 ? reinterpret_cast<const float *>(d16 + 2 * n1) : c->d_frame + 2 * n1};
-        if ((rc = encode_frames_device_impl(c, fp, nfl, 1, w, h, sc, profile, dp, stride, pfs, c->d_stats, cs_eff, false, use16)))
+        if ((rc = encode_frames_device_impl(c, staged(), sc, {dp, stride, NO_PFS, profile}, c->d_stats,
+                                            {cs_eff, c->stream, false, typed16 ? HalfSource::Typed : HalfSource::Upload})))
             return rc;
         for (int p = 0; p < 3; p++)
             if ((rc = xfer_d2h_2d(c, planes[p], stride[p], dp[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
@@ -831,7 +826,7 @@ static int encode_frame_host_impl(lumahip_ctx *c, const float *rgb, unsigned w, 
             if (mixed && (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))   // part halves, part floats: once more, whole
                 return rc;
             return transformed_out ? seq_mean(c, c->d_frame, w, h, mean_lum)
-                                   : mean_luminance_reference_impl(c, c->d_frame, w, h, sc, cs_eff, mean_lum, frame16);
+                                   : mean_luminance_reference_impl(c, c->d_frame, frame16 ? Elem::F16 : Elem::F32, w, h, sc, cs_eff, mean_lum);
         }
     }
     return LUMAHIP_OK;
@@ -843,53 +838,41 @@ extern "C" int lumahip_encode_frame_host(lumahip_ctx *c, const float *rgb, unsig
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    return encode_frame_host_impl(c, rgb, w, h, sc, profile, planes, stride, mean_lum, transformed_out, c->q.cs);
+    return encode_frame_host_impl(c, rgb, Elem::F32, w, h, sc, profile, planes, stride, mean_lum, transformed_out, c->q.cs);
 }
 
+// rgb_out: the caller's frame, floats or -- elem == F16, lumahip_decode_frame_host_f16 -- halves by type, which come down as
+// the kernel wrote them, 6 B per pixel, in one piece on the context's stream
 static int decode_frame_host_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], unsigned w,
-                                  unsigned h, int profile, float sc, float *rgb_out, int cs_eff)
+                                  unsigned h, int profile, float sc, void *rgb_out, Elem elem, int cs_eff)
 {
-    if (!c || !rgb_out || !planes || !stride)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, cs_eff);
+    PlaneLayout L;
+    unsigned char *dp[3];
+    int rc = frame_staging(c, rgb_out, planes, stride, w, h, profile, cs_eff, L, dp);
     if (rc)
         return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    for (int p = 0; p < 3; p++)
-        if (!planes[p] || stride[p] < L.row_bytes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
     const size_t nfl = (size_t)3 * w * h;
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))))
-        return rc;
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
-        return rc;
-    unsigned char *dp[3] = {c->d_planes + L.off[0], c->d_planes + L.off[1], c->d_planes + L.off[2]};
-    const size_t pfs[3] = {0, 0, 0};
     const size_t n1 = (size_t)w * h;
     const bool sub = (profile == 0 || profile == 2);
     unsigned band0[lumahip_ctx::MAX_BANDS + 1];
-    const int nb = band_plan(c, w, h, band0);
+    const int nb = elem == Elem::F16 ? 1 : band_plan(c, w, h, band0);
     if (nb > 1) {
+        float *const rgb_f = static_cast<float *>(rgb_out);
         if ((rc = pipe_streams(c)) || (rc = band_events(c, nb)))
             return rc;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipStream_t saved = c->stream;
         DnGuard dn_guard{c, false, 0};   // a failing exit below drops the download chunks still pointing at the caller's planes
         auto fetch = [&](int k) -> int {              // float rows of band k, after its kernel
             const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
             const size_t roff = (size_t)r0 * w;
             HIPCHK(c, hipStreamWaitEvent(c->s_d2h, c->band_kern[k], 0));
             for (int ch = 0; ch < 3; ch++)
-                if (int r = xfer_d2h_deferred(c, rgb_out + ch * n1 + roff, c->d_frame + ch * n1 + roff, (size_t)rows * w * sizeof(float), c->s_d2h))
+                if (int r = xfer_d2h_deferred(c, rgb_f + ch * n1 + roff, c->d_frame + ch * n1 + roff, (size_t)rows * w * sizeof(float), c->s_d2h))
                     return r;
             return LUMAHIP_OK;
         };
         for (int k = 0; k < nb && rc == LUMAHIP_OK; k++) {
             const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
-            const size_t roff = (size_t)r0 * w;
             const unsigned char *bp[3];
             for (int p = 0; p < 3 && rc == LUMAHIP_OK; p++) {
                 const unsigned pr0 = (p && sub) ? r0 / 2 : r0, prow = (p && sub) ? rows / 2 : rows;
@@ -901,11 +884,7 @@ static int decode_frame_host_impl(lumahip_ctx *c, const unsigned char *const pla
                 break;
             HIPCHK(c, hipEventRecord(c->band_h2d[k], c->s_h2d));
             HIPCHK(c, hipStreamWaitEvent(c->s_kern, c->band_h2d[k], 0));
-            float *const fp[3] = {c->d_frame + roff, c->d_frame + n1 + roff, c->d_frame + 2 * n1 + roff};
-            c->stream = c->s_kern;
-            rc = decode_impl(c, bp, stride, pfs, 1, w, rows, profile, sc, fp, nfl, DisplayParams(), cs_eff);
-            c->stream = saved;
-            if (rc)
+            if ((rc = decode_impl(c, {bp, stride, NO_PFS, profile}, sc, row_band(packed_frames(c->d_frame, nfl, 1, w, h), r0, rows), {cs_eff, c->s_kern})))
                 break;
             HIPCHK(c, hipEventRecord(c->band_kern[k], c->s_kern));
             if (k >= 1)
@@ -917,7 +896,6 @@ static int decode_frame_host_impl(lumahip_ctx *c, const unsigned char *const pla
             rc = rc ? rc : r;
         else
             dn_guard.armed = false;
-        c->stream = saved;
         HIPCHK(c, hipStreamSynchronize(c->s_h2d));
         HIPCHK(c, hipStreamSynchronize(c->s_kern));
         HIPCHK(c, hipStreamSynchronize(c->s_d2h));
@@ -926,13 +904,11 @@ static int decode_frame_host_impl(lumahip_ctx *c, const unsigned char *const pla
     for (int p = 0; p < 3; p++)
         if ((rc = xfer_h2d_2d(c, dp[p], stride[p], planes[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
             return rc;
-    {
-        float *const fp[3] = {c->d_frame, c->d_frame + n1, c->d_frame + 2 * n1};
-        rc = decode_impl(c, dp, stride, pfs, 1, w, h, profile, sc, fp, nfl, DisplayParams(), cs_eff);
-    }
-    if (rc)
+    const DstFrames staged = elem == Elem::F16 ? packed_frames(reinterpret_cast<uint16_t *>(c->d_frame), nfl, 1, w, h)   // (the staging frame holding halves)
+                                               : packed_frames(c->d_frame, nfl, 1, w, h);
+    if ((rc = decode_impl(c, {dp, stride, NO_PFS, profile}, sc, staged, {cs_eff, c->stream})))
         return rc;
-    if ((rc = xfer_d2h(c, rgb_out, c->d_frame, nfl * sizeof(float), c->stream)))
+    if ((rc = xfer_d2h(c, rgb_out, c->d_frame, nfl * elem_size(elem), c->stream)))
         return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LUMAHIP_OK;
@@ -943,7 +919,7 @@ extern "C" int lumahip_decode_frame_host(lumahip_ctx *c, const unsigned char *co
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, c->q.cs);
+    return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, Elem::F32, c->q.cs);
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the
@@ -954,47 +930,7 @@ extern "C" int lumahip_encode_frame_host_f16(lumahip_ctx *c, const uint16_t *rgb
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    if (!rgb || !planes || !stride)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const int cs_eff = c->q.cs;
-    int rc = check_geom(c, w, h, profile, cs_eff);
-    if (rc)
-        return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    for (int p = 0; p < 3; p++)
-        if (!planes[p] || stride[p] < L.row_bytes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
-    const size_t nfl = (size_t)3 * w * h, n1 = (size_t)w * h;
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))))   // (float-sized: the buffer is shared)
-        return rc;
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
-        return rc;
-    if (!c->d_stats)
-        HIPCHK(c, hipMalloc(&c->d_stats, 3 * sizeof(float)));
-    unsigned char *dp[3] = {c->d_planes + L.off[0], c->d_planes + L.off[1], c->d_planes + L.off[2]};
-    const size_t pfs[3] = {0, 0, 0};
-    uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);
-    if ((rc = xfer_h2d(c, d16, rgb, nfl * sizeof(uint16_t), c->stream)))
-        return rc;
-    const float *const fp[3] = {reinterpret_cast<const float *>(d16), reinterpret_cast<const float *>(d16 + n1),
-                                reinterpret_cast<const float *>(d16 + 2 * n1)};
-    if ((rc = encode_frames_device_impl(c, fp, nfl, 1, w, h, sc, profile, dp, stride, pfs, c->d_stats, cs_eff, false, IN16_TYPED)))
-        return rc;
-    for (int p = 0; p < 3; p++)
-        if ((rc = xfer_d2h_2d(c, planes[p], stride[p], dp[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
-            return rc;
-    float st[3];
-    if ((rc = read_small(c, st, c->d_stats, 3, c->stream)))   // synchronises the stream
-        return rc;
-    if (mean_lum) {
-        *mean_lum = st[0] / (float)((int)w * (int)h);  // avg /= (w*h), src/luma_encoder.cpp:314
-        if (mean_needs_reference_sum(*mean_lum, st[1], w, h))
-            return mean_luminance_reference_impl(c, c->d_frame, w, h, sc, cs_eff, mean_lum, true);
-    }
-    return LUMAHIP_OK;
+    return encode_frame_host_impl(c, rgb, Elem::F16, w, h, sc, profile, planes, stride, mean_lum, nullptr, c->q.cs);
 }
 
 extern "C" int lumahip_decode_frame_host_f16(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], unsigned w,
@@ -1002,37 +938,7 @@ extern "C" int lumahip_decode_frame_host_f16(lumahip_ctx *c, const unsigned char
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    if (!rgb_out || !planes || !stride)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const int cs_eff = c->q.cs;
-    int rc = check_geom(c, w, h, profile, cs_eff);
-    if (rc)
-        return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    for (int p = 0; p < 3; p++)
-        if (!planes[p] || stride[p] < L.row_bytes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
-    const size_t nfl = (size_t)3 * w * h, n1 = (size_t)w * h;
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))))
-        return rc;
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
-        return rc;
-    unsigned char *dp[3] = {c->d_planes + L.off[0], c->d_planes + L.off[1], c->d_planes + L.off[2]};
-    const size_t pfs[3] = {0, 0, 0};
-    for (int p = 0; p < 3; p++)
-        if ((rc = xfer_h2d_2d(c, dp[p], stride[p], planes[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
-            return rc;
-    uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);
-    float *const fp[3] = {reinterpret_cast<float *>(d16), reinterpret_cast<float *>(d16 + n1), reinterpret_cast<float *>(d16 + 2 * n1)};
-    if ((rc = decode_impl(c, dp, stride, pfs, 1, w, h, profile, sc, fp, nfl, DisplayParams(), cs_eff, false, nullptr, true)))
-        return rc;
-    if ((rc = xfer_d2h(c, rgb_out, d16, nfl * sizeof(uint16_t), c->stream)))
-        return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LUMAHIP_OK;
+    return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, Elem::F16, c->q.cs);
 }
 
 // ---- batched host entry points: a 3-slot software pipeline over three streams.  Frame i's H2D copy runs while
@@ -1046,6 +952,13 @@ static int pipe_streams(lumahip_ctx *c)
         HIPCHK(c, hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
     }
     return LUMAHIP_OK;
+}
+
+// the packed frame in a slot's device buffer: floats, or the halves the half upload put at the same element offsets
+static SrcFrames slot_frame(const lumahip_ctx::Slot &sl, bool halves, size_t nfl, unsigned w, unsigned h)
+{
+    return halves ? packed_frames<const uint16_t>(reinterpret_cast<const uint16_t *>(sl.d_frame), nfl, 1, w, h)
+                  : packed_frames<const float>(sl.d_frame, nfl, 1, w, h);
 }
 
 static int pipe_prepare(lumahip_ctx *c, size_t frame_bytes, size_t planes_bytes, unsigned nframes)
@@ -1098,9 +1011,9 @@ extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rg
     for (unsigned i = 0; i < nframes; i++) {
         if (!rgb[i])
             return fail(c, LUMAHIP_ERR_ARG, "null frame %u", i);
-        for (int p = 0; p < 3; p++)
-            if (!planes[3 * i + p] || stride[p] < L.row_bytes[p])
-                return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
+        const int p = bad_plane(L, planes + 3 * i, stride);
+        if (p >= 0)
+            return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
     }
     const size_t nfl = (size_t)3 * w * h;
     if (c->es_head != c->es_tail)
@@ -1109,9 +1022,7 @@ extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rg
         return rc;
     if ((rc = dn_chunks_for(c, L.total)))
         return rc;
-    hipStream_t saved = c->stream;
     DnGuard dn_guard{c, false, 0};   // a failing exit drops the download chunks still pointing at the caller's buffers
-    const size_t pfs[3] = {0, 0, 0};
     // Frame i's upload and kernel are queued BEFORE frame i-1's planes are fetched.
     auto fetch = [&](unsigned i) -> int {
         lumahip_ctx::Slot &sl = c->slot[i % 3];
@@ -1150,11 +1061,8 @@ extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rg
             break;
         (void)hipEventRecord(sl.h2d, c->s_h2d);
         (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-        c->stream = c->s_kern;
-        rc = f16 ? encode_packed16(c, sl.d_frame, nfl, 1, w, h, sc, profile, dp, stride, pfs, sl.d_stats)
-                 : encode_packed(c, sl.d_frame, nfl, 1, w, h, sc, profile, dp, stride, pfs, sl.d_stats);
-        c->stream = saved;
-        if (rc)
+        if ((rc = encode_frames_device_impl(c, slot_frame(sl, f16, nfl, w, h), sc, {dp, stride, NO_PFS, profile}, sl.d_stats,
+                                            {c->q.cs, c->s_kern, false, HalfSource::Upload})))
             break;
         (void)hipEventRecord(sl.kern, c->s_kern);
         if (i >= 1)
@@ -1166,7 +1074,6 @@ extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rg
         rc = rc ? rc : r;
     else
         dn_guard.armed = false;
-    c->stream = saved;
     HIPCHK(c, hipStreamSynchronize(c->s_h2d));
     HIPCHK(c, hipStreamSynchronize(c->s_kern));
     HIPCHK(c, hipStreamSynchronize(c->s_d2h));
@@ -1176,7 +1083,7 @@ extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rg
             if (mean_needs_reference_sum(mean_lum[i], c->h_stats[3 * (size_t)i + 1], w, h)) {  // rare: redo this frame's sum in the reference's order
                 if ((rc = xfer_h2d(c, c->slot[0].d_frame, rgb[i], nfl * sizeof(float), c->stream)))
                     return rc;
-                rc = mean_luminance_reference_impl(c, c->slot[0].d_frame, w, h, sc, c->q.cs, &mean_lum[i]);
+                rc = mean_luminance_reference_impl(c, c->slot[0].d_frame, Elem::F32, w, h, sc, c->q.cs, &mean_lum[i]);
             }
         }
     return rc;
@@ -1205,9 +1112,8 @@ extern "C" int lumahip_encode_stream_push(lumahip_ctx *c, const float *rgb, unsi
     HIPCHK(c, hipSetDevice(c->device));
     PlaneLayout L;
     plane_layout(L, w, h, profile, stride);
-    for (int p = 0; p < 3; p++)
-        if (!planes[p] || stride[p] < L.row_bytes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
+    if (const int p = bad_plane(L, planes, stride); p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
     const size_t nfl = (size_t)3 * w * h;
     if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, 1)))   // (reallocates only when nothing is in flight: same geometry otherwise)
         return rc;
@@ -1218,7 +1124,6 @@ extern "C" int lumahip_encode_stream_push(lumahip_ctx *c, const float *rgb, unsi
     const unsigned seq = c->es_head;
     lumahip_ctx::Slot &sl = c->slot[seq % 3];
     unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-    const size_t pfs[3] = {0, 0, 0};
     // the slot's previous occupant (frame seq - 3) was popped long ago; its kernel and downloads are done, but the streams
     // still have to be told (events of that occupancy)
     if (seq >= 3) {
@@ -1243,12 +1148,8 @@ extern "C" int lumahip_encode_stream_push(lumahip_ctx *c, const float *rgb, unsi
     c->slot_in16[seq % 3] = f16;
     (void)hipEventRecord(sl.h2d, c->s_h2d);
     (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-    hipStream_t saved = c->stream;
-    c->stream = c->s_kern;
-    rc = f16 ? encode_packed16(c, sl.d_frame, nfl, 1, w, h, sc, profile, dp, stride, pfs, sl.d_stats)
-             : encode_packed(c, sl.d_frame, nfl, 1, w, h, sc, profile, dp, stride, pfs, sl.d_stats);
-    c->stream = saved;
-    if (rc)
+    if ((rc = encode_frames_device_impl(c, slot_frame(sl, f16, nfl, w, h), sc, {dp, stride, NO_PFS, profile}, sl.d_stats,
+                                        {c->q.cs, c->s_kern, false, HalfSource::Upload})))
         return rc;
     (void)hipEventRecord(sl.kern, c->s_kern);
     // the planes come down behind the kernel; pageable ones are emptied out of the staging chunks by the pop (or earlier,
@@ -1295,7 +1196,7 @@ extern "C" int lumahip_encode_stream_pop(lumahip_ctx *c, float *mean_lum)
         const float *stp = c->h_es_stats + 3 * (seq % 3);
         *mean_lum = stp[0] / (float)((int)c->es_w * (int)c->es_h);
         if (mean_needs_reference_sum(*mean_lum, stp[1], c->es_w, c->es_h))   // the slot still holds the frame as it was uploaded
-            return mean_luminance_reference_impl(c, sl.d_frame, c->es_w, c->es_h, c->es_sc, c->q.cs, mean_lum, c->slot_in16[seq % 3]);
+            return mean_luminance_reference_impl(c, sl.d_frame, c->slot_in16[seq % 3] ? Elem::F16 : Elem::F32, c->es_w, c->es_h, c->es_sc, c->q.cs, mean_lum);
     }
     return LUMAHIP_OK;
 }
@@ -1322,16 +1223,14 @@ extern "C" int lumahip_decode_stream_push(lumahip_ctx *c, const unsigned char *c
     HIPCHK(c, hipSetDevice(c->device));
     PlaneLayout L;
     plane_layout(L, w, h, profile, stride);
-    for (int p = 0; p < 3; p++)
-        if (!planes[p] || stride[p] < L.row_bytes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
+    if (const int p = bad_plane(L, planes, stride); p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
     const size_t nfl = (size_t)3 * w * h;
     if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, 1)))
         return rc;
     const unsigned seq = c->es_head;
     lumahip_ctx::Slot &sl = c->slot[seq % 3];
     unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-    const size_t pfs[3] = {0, 0, 0};
     if (seq >= 3) {
         (void)hipStreamWaitEvent(c->s_h2d, sl.kern, 0);   // planes of the slot's previous occupant consumed
         (void)hipStreamWaitEvent(c->s_kern, sl.d2h, 0);   // its floats downloaded
@@ -1347,11 +1246,7 @@ extern "C" int lumahip_decode_stream_push(lumahip_ctx *c, const unsigned char *c
         return rc;
     (void)hipEventRecord(sl.h2d, c->s_h2d);
     (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-    hipStream_t saved = c->stream;
-    c->stream = c->s_kern;
-    rc = decode_packed(c, dp, stride, pfs, 1, w, h, profile, sc, sl.d_frame, nfl);
-    c->stream = saved;
-    if (rc)
+    if ((rc = decode_impl(c, {dp, stride, NO_PFS, profile}, sc, packed_frames(sl.d_frame, nfl, 1, w, h), {c->q.cs, c->s_kern})))
         return rc;
     (void)hipEventRecord(sl.kern, c->s_kern);
     (void)hipStreamWaitEvent(c->s_d2h, sl.kern, 0);
@@ -1408,18 +1303,16 @@ extern "C" int lumahip_decode_frames_host(lumahip_ctx *c, const unsigned char *c
     for (unsigned i = 0; i < nframes; i++) {
         if (!rgb_out[i])
             return fail(c, LUMAHIP_ERR_ARG, "null output frame %u", i);
-        for (int p = 0; p < 3; p++)
-            if (!planes[3 * i + p] || stride[p] < L.row_bytes[p])
-                return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
+        const int p = bad_plane(L, planes + 3 * i, stride);
+        if (p >= 0)
+            return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
     }
     const size_t nfl = (size_t)3 * w * h;
     if (c->es_head != c->es_tail)
         return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_encode_stream_push / lumahip_decode_stream_push are still pending: pop them first");
     if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, nframes)))
         return rc;
-    hipStream_t saved = c->stream;
     DnGuard dn_guard{c, false, 0};   // a failing exit drops the download chunks still pointing at the caller's buffers
-    const size_t pfs[3] = {0, 0, 0};
     auto fetch = [&](unsigned i) -> int {  // as in lumahip_encode_frames_host: frame i-1 is fetched after frame i is queued
         lumahip_ctx::Slot &sl = c->slot[i % 3];
         (void)hipStreamWaitEvent(c->s_d2h, sl.kern, 0);
@@ -1442,10 +1335,7 @@ extern "C" int lumahip_decode_frames_host(lumahip_ctx *c, const unsigned char *c
             break;
         (void)hipEventRecord(sl.h2d, c->s_h2d);
         (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-        c->stream = c->s_kern;
-        rc = decode_packed(c, dp, stride, pfs, 1, w, h, profile, sc, sl.d_frame, nfl);
-        c->stream = saved;
-        if (rc)
+        if ((rc = decode_impl(c, {dp, stride, NO_PFS, profile}, sc, packed_frames(sl.d_frame, nfl, 1, w, h), {c->q.cs, c->s_kern})))
             break;
         (void)hipEventRecord(sl.kern, c->s_kern);
         if (i >= 1)
@@ -1457,7 +1347,6 @@ extern "C" int lumahip_decode_frames_host(lumahip_ctx *c, const unsigned char *c
         rc = rc ? rc : r;
     else
         dn_guard.armed = false;
-    c->stream = saved;
     HIPCHK(c, hipStreamSynchronize(c->s_h2d));
     HIPCHK(c, hipStreamSynchronize(c->s_kern));
     HIPCHK(c, hipStreamSynchronize(c->s_d2h));
@@ -1551,7 +1440,7 @@ extern "C" int lumahip_pack_frame_host(lumahip_ctx *c, const float *transformed,
         return LUMAHIP_ERR_ARG;
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
-    return encode_frame_host_impl(c, transformed, w, h, 1.0f, profile, planes, stride, mean_lum, nullptr, pack_cs(c));
+    return encode_frame_host_impl(c, transformed, Elem::F32, w, h, 1.0f, profile, planes, stride, mean_lum, nullptr, pack_cs(c));
 }
 
 extern "C" int lumahip_unpack_frame_host(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3],
@@ -1561,6 +1450,6 @@ extern "C" int lumahip_unpack_frame_host(lumahip_ctx *c, const unsigned char *co
         return LUMAHIP_ERR_ARG;
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
-    return decode_frame_host_impl(c, planes, stride, w, h, profile, 1.0f, dequantized_out, pack_cs(c));
+    return decode_frame_host_impl(c, planes, stride, w, h, profile, 1.0f, dequantized_out, Elem::F32, pack_cs(c));
 }
 

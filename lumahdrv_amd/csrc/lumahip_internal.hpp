@@ -3,10 +3,13 @@
 //
 //   lumahip_core.hip    context life cycle, quantizer upload, layout checks, memory helpers               (no kernels)
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
-//   lumahip_encode.hip  every float-frame k_encode / encode-side instantiation and its dispatch
-//   lumahip_decode.hip  every float-frame k_decode instantiation and its dispatch
-//   lumahip_encode_f16.hip / lumahip_decode_f16.hip  the binary16-frame k_encode<..., IN16> / k_decode<..., OUT16>
-//                       instantiations, their pick functions and the _f16 device entry points (+ the narrowing probe)
+//   lumahip_pick.hpp    which k_encode / k_decode instantiation a launch takes: pick_enc<IN16> / pick_dec<OUT16>, included by
+//                       the four kernel units below and by nothing else
+//   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
+//   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels
+//   lumahip_encode_f16.hip / lumahip_decode_f16.hip  pick_enc<true> / pick_dec<true> (the binary16-frame kernels, exported as
+//                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
+//                       narrowing probe)
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the 3-slot pipeline   (no kernels)
 //   lumahip_pool.hip    the HBM chunk pool;  lumahip_multi.hip  many GPUs in one process                  (no kernels)
@@ -22,6 +25,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #define LUMAHIP_EXPERIMENTAL   /* the library defines what the experimental section of the header declares */
@@ -261,6 +265,86 @@ struct EventPair {
 };
 
 
+// ---- what a dispatch call is about: the colour frames, the code planes, how to launch --------------------------------------
+enum class Elem { F32, F16 };   // element type of colour frames: float, or binary16 behind uint16_t
+static inline size_t elem_size(Elem e) { return e == Elem::F16 ? sizeof(uint16_t) : sizeof(float); }
+
+// nframes colour frames of w x h pixels: colour plane k of frame f at plane[k] + f * frame_stride ELEMENTS of type `elem`.
+// The element type is stated here and nowhere else.  V: const void (encode sources) or void (decode destinations)
+template <typename V>
+struct FramesT {
+    V *plane[3];
+    Elem elem;
+    size_t frame_stride;   // elements
+    unsigned nframes, w, h;
+};
+using SrcFrames = FramesT<const void>;
+using DstFrames = FramesT<void>;
+
+template <typename T>
+using frames_of = FramesT<std::conditional_t<std::is_const_v<T>, const void, void>>;
+template <typename T>
+constexpr Elem elem_of()
+{
+    static_assert(std::is_same_v<std::remove_const_t<T>, float> || std::is_same_v<std::remove_const_t<T>, uint16_t>, "float or binary16 frames");
+    return std::is_same_v<std::remove_const_t<T>, float> ? Elem::F32 : Elem::F16;
+}
+// packed frames (the reference's LumaFrame): plane k at base + k * w * h; a null base gives three null planes
+template <typename T>
+frames_of<T> packed_frames(T *base, size_t frame_stride, unsigned nframes, unsigned w, unsigned h)
+{
+    const size_t n = (size_t)w * h;
+    return {{base, base ? base + n : nullptr, base ? base + 2 * n : nullptr}, elem_of<T>(), frame_stride, nframes, w, h};
+}
+// three plane pointers; a null array gives three null planes
+template <typename T>
+frames_of<T> planar_frames(T *const planes[3], size_t frame_stride, unsigned nframes, unsigned w, unsigned h)
+{
+    return {{planes ? planes[0] : nullptr, planes ? planes[1] : nullptr, planes ? planes[2] : nullptr}, elem_of<T>(), frame_stride, nframes, w, h};
+}
+// rows [r0, r0 + rows) of every plane (the row bands of the host entry points)
+template <typename V>
+FramesT<V> row_band(FramesT<V> f, unsigned r0, unsigned rows)
+{
+    using B = std::conditional_t<std::is_const_v<V>, const unsigned char, unsigned char>;
+    for (auto &p : f.plane)
+        p = static_cast<B *>(p) + (size_t)r0 * f.w * elem_size(f.elem);
+    f.h = rows;
+    return f;
+}
+static inline SrcFrames readonly(const DstFrames &f) { return {{f.plane[0], f.plane[1], f.plane[2]}, f.elem, f.frame_stride, f.nframes, f.w, f.h}; }
+
+// the code planes of the same frames, by reference to the caller's arrays (any of them may be null: the dispatch functions
+// check).  B: unsigned char (encode destinations) or const unsigned char (decode sources)
+template <typename B>
+struct CodePlanesT {
+    B *const *planes;      // [3]
+    const int *stride;     // [3], bytes
+    const size_t *pfs;     // [3], bytes from one frame's plane to the next frame's
+    int profile;
+};
+using DstPlanes = CodePlanesT<unsigned char>;
+using SrcPlanes = CodePlanesT<const unsigned char>;
+
+// Where binary16 source frames come from (read only when the frames' element type is F16):
+//   Typed   the caller's frames are binary16 by type (the _f16 entry points): every search mode and width, the YCbCr half-input
+//           table whenever it exists for (sc, maxLum) and no statistics are asked for -- no probe, no feedback, no host wait;
+//   Upload  this library's half upload produced them from float frames (lumahip_host.hip xfer_h2d_f16):
+//           LUMAHIP_ERR_UNSUPPORTED unless encode_supports_in16() (records in LDS, rows of a multiple of 4 pixels)
+enum class HalfSource { Typed, Upload };
+
+// cs_eff: the colour space the kernels run (the context's, or CS_PACK / CS_RGB for the pack-only entry points).
+// stream: where the kernels -- and any table built for them on the way -- are queued: the context's stream, or the kernel
+// stream of a host entry point's pipeline.
+// lanes: the call is one of the _device encode / decode entry points and goes to a lane of an open unordered section instead;
+// every other caller (the _host entry points with their own upload / kernel / download streams, the stream push / pop, the
+// display decode) stays on `stream` whether a section is open or not, as include/lumahip.h promises
+struct EncodeLaunch {
+    int cs_eff;
+    hipStream_t stream;
+    bool lanes = false;
+    HalfSource halves = HalfSource::Typed;
+};
 struct DisplayParams {
     unsigned char *rgba = nullptr;
     int stride = 0;
@@ -268,13 +352,22 @@ struct DisplayParams {
     float exposure = 1.0f, gamma = 2.2f;
     int do_tmo = 0, ldr_sim = 0;
 };
+struct DecodeLaunch {
+    int cs_eff;
+    hipStream_t stream;
+    bool lanes = false;
+    // PACKED float frames rotating over three buffers, frame f at rot[f % 3] + (f / 3) * frame_stride (the frames' planes are
+    // then ignored); not with binary16 frames or a display output
+    float *const *rot = nullptr;
+    const DisplayParams *display = nullptr;   // + the display epilogue; not with binary16 frames
+};
 
 // ---- lumahip_launch.hip
 size_t lds_bytes(const lumahip_ctx *c, bool encode_side, int cs_eff, bool ycode = false, bool half = false);   // ycode: the composite-record encode kernels; half: + the half-input table
 int block_threads_for(const lumahip_ctx *c, size_t lds, bool few_waves = false, bool valu_bound = false);
 int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers = 0, int ycbcr = 0);   // few_writers: 0 no, 1 yes, 2 yes with the colour planes in separate buffers; ycbcr: 0 no, 1 yes, 2 the half-input encode kernels
 // ---- lumahip_core.hip
-int ensure_search_index(lumahip_ctx *c);   // every encode-side launch calls this first (lazy build / process-wide cache)
+int ensure_search_index(lumahip_ctx *c, hipStream_t s);   // every encode-side launch calls this first (lazy build / process-wide cache); s: the stream that launch goes to
 bool ycbcr_composite_ready(const lumahip_ctx *c);   // encode: the composite luma -> code records exist and fit LDS
 int half_table_for(lumahip_ctx *c, float sc, const float **tab);   // *tab = the device half-input table of (sc, the quantizer's Lmax), or nullptr: none
 // this eligible launch: the data-dependent ("fast") kernel (true) or the plain one.  On true, *flag is the launch's feedback
@@ -303,37 +396,19 @@ void lag_policy_destroy(LagPolicy &p);
 void numa_resolve(lumahip_ctx *c);                                 // fills numa_node / numa_cpus once (cheap afterwards)
 int check_geom(lumahip_ctx *c, unsigned w, unsigned h, int profile, int cs_eff);
 bool make_geom(FrameGeom &g, unsigned w, unsigned h, int vw, int nw, unsigned nframes);
-hipStream_t launch_stream(lumahip_ctx *c, bool lanes);   // the context's stream, or -- for the entry points that take part in unordered sections -- the next lane of an open one
+hipStream_t launch_stream(lumahip_ctx *c, hipStream_t s, bool lanes);   // s, or -- for the entry points that take part in unordered sections -- the next lane of an open one
 void plane_dims(unsigned w, unsigned h, int profile, int p, int &rows, int &row_bytes);
-// rgb: the three colour-plane base pointers of the float frames (nullptr: no float frames in this call); esize: bytes per
-// element of those frames (2: binary16 frames behind the same pointers, frame_stride counting halves)
-int check_layout(lumahip_ctx *c, unsigned w, unsigned h, int profile, unsigned nframes, const float *const rgb[3],
-                 size_t frame_stride, const int stride[3], const size_t pfs[3], size_t esize = sizeof(float));
+// the code planes' strides against f's geometry and, with `overlap_test`, that no two colour planes of f overlap
+int check_layout(lumahip_ctx *c, const SrcFrames &f, bool overlap_test, const int stride[3], const size_t pfs[3], int profile);
 
-// ---- lumahip_encode.hip / lumahip_decode.hip: cs_eff = the colour space the kernels run (the context's, or CS_PACK /
-// CS_RGB for the pack-only entry points)
-// rgb[c]: base of colour plane c; plane c of frame f at rgb[c] + f*frame_stride floats
-int encode_frames_device_impl(lumahip_ctx *c, const float *const rgb[3], size_t frame_stride, unsigned nframes,
-                              unsigned w, unsigned h, float sc, int profile, unsigned char *const planes[3],
-                              const int stride[3], const size_t pfs[3], float *stats, int cs_eff, bool lanes = false, int in16 = 0);
-// in16: rgb[] point at binary16 planes; same element offsets and strides.  1: the half upload of the host entry points
-// (lumahip_host.hip), LUMAHIP_ERR_UNSUPPORTED unless encode_supports_in16() (records in LDS, rows of a multiple of 4 pixels);
-// 2: frames that are binary16 by type (the _f16 entry points): every search mode and width, the YCbCr half-input table whenever
-// it exists for (sc, maxLum) and no statistics are asked for -- no probe, no feedback, no host wait
-enum : int { IN16_NONE = 0, IN16_UPLOAD = 1, IN16_TYPED = 2 };
+// ---- lumahip_encode.hip / lumahip_decode.hip
+int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const DstPlanes &p, float *stats, const EncodeLaunch &o);
 bool encode_supports_in16(lumahip_ctx *c, unsigned w);
-int decode_impl(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
-                unsigned nframes, unsigned w, unsigned h, int profile, float sc, float *const rgb[3], size_t frame_stride,
-                const DisplayParams &dp, int cs_eff, bool lanes = false, float *const rot[3] = nullptr, bool out16 = false);
-// out16: rgb[] point at binary16 planes (the _f16 entry points; k_decode<..., OUT16>), same element offsets and strides; not with
-// rot or a display output
-// rot: PACKED frames rotating over three buffers, frame f at rot[f % 3] + (f / 3) * frame_stride (rgb is then ignored)
-// lanes: the call is one of the four _device encode / decode entry points and goes to a lane of an open unordered section;
-// every other caller (the _host entry points with their own upload / kernel / download streams, the stream push / pop, the
-// display decode) stays on c->stream whether a section is open or not, as include/lumahip.h promises
+int decode_impl(lumahip_ctx *c, const SrcPlanes &p, float sc, const DstFrames &f, const DecodeLaunch &o);
+int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab);   // built on s the first time a preScaling is seen
 int array_launch(lumahip_ctx *c, const float *d_in, float *d_out, size_t n, unsigned ch, bool quant);
-// ---- lumahip_encode_f16.hip / lumahip_decode_f16.hip: the binary16-frame instantiations (own translation units: they compile
-// side by side with the float ones).  Same selection as the float kernels' pick_enc / pick_dec; nullptr: none for these arguments
+// ---- lumahip_encode_f16.hip / lumahip_decode_f16.hip: pick_enc<true> / pick_dec<true> of lumahip_pick.hpp (own translation
+// units: the binary16-frame kernels compile side by side with the float ones).  nullptr: none for these arguments
 typedef void (*enc_kernel_t)(const lh::EncArgs);
 typedef void (*dec_kernel_t)(const lh::DecArgs);
 enc_kernel_t pick_enc_f16(int cs, bool sub, int vw, int mode);
@@ -341,8 +416,8 @@ dec_kernel_t pick_dec_f16(int cs, bool sub, int vw, bool gl, bool yt, bool rb);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);
-int mean_luminance_reference_impl(lumahip_ctx *c, const float *rgb_dev, unsigned w, unsigned h, float sc, int cs_eff,
-                                  float *mean_host, bool in16 = false);   // in16: the frame at rgb_dev holds binary16 values
+int mean_luminance_reference_impl(lumahip_ctx *c, const void *rgb_dev, Elem elem, unsigned w, unsigned h, float sc, int cs_eff,
+                                  float *mean_host);   // one packed frame of `elem` at rgb_dev
 
 // ---- lumahip_host.hip
 int xfer_h2d(lumahip_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t s);

@@ -190,9 +190,10 @@ int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, flo
 }
 
 // mean of transformed channel 0 of ONE device-resident (untransformed) frame, summed exactly as the reference does
-int mean_luminance_reference_impl(lumahip_ctx *c, const float *rgb_dev, unsigned w, unsigned h, float sc, int cs_eff,
-                                         float *mean_host, bool in16)
+int mean_luminance_reference_impl(lumahip_ctx *c, const void *rgb_dev, Elem elem, unsigned w, unsigned h, float sc, int cs_eff,
+                                  float *mean_host)
 {
+    const bool in16 = elem == Elem::F16;
     const size_t n = (size_t)w * h;
     int rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, n * sizeof(float));
     if (rc)
@@ -210,7 +211,7 @@ int mean_luminance_reference_impl(lumahip_ctx *c, const float *rgb_dev, unsigned
     long grid = (long)((n + 255) / 256);
     if (grid > (long)c->num_cu * 8)
         grid = (long)c->num_cu * 8;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, c->stream, rgb_dev, n, n, sc, c->q.Lmax, c->d_arr);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, c->stream, static_cast<const float *>(rgb_dev), n, n, sc, c->q.Lmax, c->d_arr);   // (k_channel0<., IN16> reads halves behind it)
     return seq_mean(c, c->d_arr, w, h, mean_host);
 }
 
@@ -224,7 +225,7 @@ extern "C" int lumahip_mean_luminance_reference_device(lumahip_ctx *c, const flo
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set");
     HIPCHK(c, hipSetDevice(c->device));
-    return mean_luminance_reference_impl(c, rgb_dev, w, h, sc, c->q.cs, mean_host);
+    return mean_luminance_reference_impl(c, rgb_dev, Elem::F32, w, h, sc, c->q.cs, mean_host);
 }
 
 extern "C" int lumahip_powf_probe_device(lumahip_ctx *c, float *out_dev, uint32_t first_bits, size_t n, float y, int regular)

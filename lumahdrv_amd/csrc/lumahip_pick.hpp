@@ -1,0 +1,98 @@
+// lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / lh::k_decode, luma_kernels.hpp) a launch takes.
+// Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
+// a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
+// (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
+// export them as pick_enc_f16 / pick_dec_f16.  Included by those four units only.
+#pragma once
+#include "lumahip_internal.hpp"
+
+namespace lhost {
+
+// mode: the search mode of the luminance table (lut_index.hpp LutMode), or for YCbCr 5 = the composite luma -> code records,
+// 6 = the same + the half-input table.  vw == 4 or 2 for the record searches, 2 for the literal ones.
+// IN16: no mode 5 (frames of halves take the table whenever it exists -- encode_frames_device_impl -- else the general kernel)
+template <bool IN16, int CS, bool SUB>
+static enc_kernel_t pick_enc_cs(int vw, int mode)
+{
+    using namespace lh;
+    if constexpr (CS == CS_YCBCR) {
+        if constexpr (!IN16)
+            if (mode == 5)
+                return vw == 4 ? k_encode<CS, SUB, 4, 5> : k_encode<CS, SUB, 2, 5>;
+        if (mode == 6)
+            return vw == 4 ? k_encode<CS, SUB, 4, 6, IN16> : k_encode<CS, SUB, 2, 6, IN16>;
+    }
+    if (mode == LUT_THRESH_LDS)
+        return vw == 4 ? k_encode<CS, SUB, 4, 3, IN16> : k_encode<CS, SUB, 2, 3, IN16>;
+    if (mode == LUT_THRESH_GLOBAL)
+        return vw == 4 ? k_encode<CS, SUB, 4, 4, IN16> : k_encode<CS, SUB, 2, 4, IN16>;
+    if (mode == LUT_LINKEY_LDS)
+        return vw == 4 ? k_encode<CS, SUB, 4, 7, IN16> : k_encode<CS, SUB, 2, 7, IN16>;
+    if (mode == LUT_LITERAL_LDS)
+        return k_encode<CS, SUB, 2, 0, IN16>;
+    if constexpr (IN16)
+        if (mode != LUT_LITERAL_GLOBAL)
+            return nullptr;
+    return k_encode<CS, SUB, 2, 2, IN16>;
+}
+
+template <bool IN16>
+static enc_kernel_t pick_enc(int cs, bool sub, int vw, int mode)
+{
+    using namespace lh;
+    switch (cs) {
+    case CS_LUV: return sub ? pick_enc_cs<IN16, CS_LUV, true>(vw, mode) : pick_enc_cs<IN16, CS_LUV, false>(vw, mode);
+    case CS_RGB: return sub ? pick_enc_cs<IN16, CS_RGB, true>(vw, mode) : pick_enc_cs<IN16, CS_RGB, false>(vw, mode);
+    case CS_YCBCR: return sub ? pick_enc_cs<IN16, CS_YCBCR, true>(vw, mode) : pick_enc_cs<IN16, CS_YCBCR, false>(vw, mode);
+    case CS_XYZ: return sub ? pick_enc_cs<IN16, CS_XYZ, true>(vw, mode) : pick_enc_cs<IN16, CS_XYZ, false>(vw, mode);
+    case CS_PACK:   // (frames that are already colour-transformed are floats)
+        if constexpr (!IN16)
+            return sub ? pick_enc_cs<IN16, CS_PACK, true>(vw, mode) : pick_enc_cs<IN16, CS_PACK, false>(vw, mode);
+        break;
+    }
+    return nullptr;
+}
+
+// gl: the luminance table in global memory; disp: + the display epilogue; yt: the per-stream y table in LDS; rb: + red and
+// blue from the per-stream tables in global memory.  OUT16: no display variants (binary16 stores only)
+template <bool OUT16, int CS, bool SUB>
+static dec_kernel_t pick_dec_cs(int vw, bool gl, bool disp, bool yt, bool rb)
+{
+    using namespace lh;
+    if constexpr (CS == CS_YCBCR) {
+        if (yt && rb && !gl && !disp)
+            return vw == 4 ? k_decode<CS, SUB, 4, false, false, true, true, OUT16> : k_decode<CS, SUB, 2, false, false, true, true, OUT16>;
+        if (yt && !gl && !disp)
+            return vw == 4 ? k_decode<CS, SUB, 4, false, false, true, false, OUT16> : k_decode<CS, SUB, 2, false, false, true, false, OUT16>;
+    }
+    if (disp) {
+        if constexpr (OUT16)
+            return nullptr;
+        else if (gl)
+            return k_decode<CS, SUB, 2, true, true>;
+        else
+            return vw == 4 ? k_decode<CS, SUB, 4, false, true> : k_decode<CS, SUB, 2, false, true>;
+    }
+    if (gl)
+        return k_decode<CS, SUB, 2, true, false, false, false, OUT16>;
+    return vw == 4 ? k_decode<CS, SUB, 4, false, false, false, false, OUT16> : k_decode<CS, SUB, 2, false, false, false, false, OUT16>;
+}
+
+template <bool OUT16>
+static dec_kernel_t pick_dec(int cs, bool sub, int vw, bool gl, bool disp, bool yt, bool rb)
+{
+    using namespace lh;
+    switch (cs) {
+    case CS_LUV: return sub ? pick_dec_cs<OUT16, CS_LUV, true>(vw, gl, disp, yt, rb) : pick_dec_cs<OUT16, CS_LUV, false>(vw, gl, disp, yt, rb);
+    case CS_RGB: return sub ? pick_dec_cs<OUT16, CS_RGB, true>(vw, gl, disp, yt, rb) : pick_dec_cs<OUT16, CS_RGB, false>(vw, gl, disp, yt, rb);
+    case CS_YCBCR: return sub ? pick_dec_cs<OUT16, CS_YCBCR, true>(vw, gl, disp, yt, rb) : pick_dec_cs<OUT16, CS_YCBCR, false>(vw, gl, disp, yt, rb);
+    case CS_XYZ: return sub ? pick_dec_cs<OUT16, CS_XYZ, true>(vw, gl, disp, yt, rb) : pick_dec_cs<OUT16, CS_XYZ, false>(vw, gl, disp, yt, rb);
+    case CS_PACK:   // (the unpack-only decode writes dequantized floats; no _f16 entry point runs it)
+        if constexpr (!OUT16)
+            return sub ? pick_dec_cs<OUT16, CS_PACK, true>(vw, gl, disp, yt, rb) : pick_dec_cs<OUT16, CS_PACK, false>(vw, gl, disp, yt, rb);
+        break;
+    }
+    return nullptr;
+}
+
+}  // namespace lhost
