@@ -1,5 +1,5 @@
-// lumahip_host.hip -- the _host entry points of include/lumahip.h: staging buffers, host <-> device transfers, the 3-slot
-// pipeline of the batched forms.  No kernels here.
+// lumahip_host.hip -- the _host entry points of include/lumahip.h: staging buffers, host <-> device transfers, and the one
+// 3-stage pipeline (upload | kernel | download) behind the banded, batched and stream push / pop forms.  No kernels here.
 #include "lumahip_internal.hpp"
 #include "half_stage.hpp"
 
@@ -113,6 +113,26 @@ struct lumahip_copy_pool {
             pending.fetch_sub(1, std::memory_order_release);
         }
     }
+    // One generation of work: part(k + 1) goes to worker k, part(0) is done here, and the call returns when every part is done
+    // (a part of width 0 is nothing to do).  The jobs are published by the generation bump; the lock around it is what a
+    // worker about to sleep re-checks the generation under.
+    template <typename Part>
+    __attribute__((visibility("hidden"))) void dispatch(Part part)
+    {
+        for (size_t k = 0; k < workers.size(); k++)
+            jobs[k] = part(k + 1);
+        pending.store((int)workers.size(), std::memory_order_relaxed);
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            generation.fetch_add(1, std::memory_order_release);
+        }
+        cv_go.notify_all();
+        const Job mine = part(0);
+        if (mine.width)
+            run_job(mine);
+        while (pending.load(std::memory_order_acquire) != 0)
+            __builtin_ia32_pause();
+    }
     // rows x width bytes from src (pitch sp) to dst (pitch dp), split over the workers and the calling thread
     void copy(unsigned char *dst, size_t dp, const unsigned char *src, size_t sp, size_t width, size_t rows)
     {
@@ -127,25 +147,12 @@ struct lumahip_copy_pool {
         size_t per = (total + parts - 1) / parts;
         if (flat)
             per = (per + 4095) & ~(size_t)4095;
-        auto part = [&](size_t k) -> Job {
+        dispatch([&](size_t k) -> Job {
             const size_t a = std::min(total, k * per), b = std::min(total, (k + 1) * per);
             if (a >= b)
                 return Job{nullptr, nullptr, 0, 0, 0, 0};
             return flat ? Job{dst + a, src + a, b - a, 1, 0, 0} : Job{dst + a * dp, src + a * sp, width, b - a, dp, sp};
-        };
-        for (size_t k = 0; k < workers.size(); k++)
-            jobs[k] = part(k + 1);
-        pending.store((int)workers.size(), std::memory_order_relaxed);
-        {
-            std::lock_guard<std::mutex> lk(mu);   // (a worker about to sleep re-checks the generation under this lock)
-            generation.fetch_add(1, std::memory_order_release);
-        }
-        cv_go.notify_all();
-        const Job mine = part(0);
-        if (mine.width)
-            run(mine);
-        while (pending.load(std::memory_order_acquire) != 0)
-            __builtin_ia32_pause();
+        });
     }
     // n floats at src -> n halves at dst, split over the workers and the calling thread (spans cut at multiples of 2048 floats);
     // false when some value is not a half (dst is then useless)
@@ -155,46 +162,33 @@ struct lumahip_copy_pool {
         const size_t parts = workers.size() + 1;
         if (n < ((size_t)64 << 10) || n < parts)
             return lh::convert_f32_to_f16_checked(src, dst, n);
-        size_t per = ((n + parts - 1) / parts + 2047) & ~(size_t)2047;
-        auto part = [&](size_t k) -> Job {
+        const size_t per = ((n + parts - 1) / parts + 2047) & ~(size_t)2047;
+        dispatch([&](size_t k) -> Job {
             const size_t a = std::min(n, k * per), b = std::min(n, (k + 1) * per);
-            Job j{nullptr, nullptr, 0, 0, 0, 0};
-            if (a < b) {
-                j.dst = reinterpret_cast<unsigned char *>(dst + a);
-                j.src = reinterpret_cast<const unsigned char *>(src + a);
-                j.width = (b - a) * 4;
-                j.rows = 1;
-                j.to_half = true;
-            }
-            return j;
-        };
-        for (size_t k = 0; k < workers.size(); k++)
-            jobs[k] = part(k + 1);
-        pending.store((int)workers.size(), std::memory_order_relaxed);
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            generation.fetch_add(1, std::memory_order_release);
-        }
-        cv_go.notify_all();
-        const Job mine = part(0);
-        if (mine.width)
-            run_job(mine);
-        while (pending.load(std::memory_order_acquire) != 0)
-            __builtin_ia32_pause();
+            if (a >= b)
+                return Job{nullptr, nullptr, 0, 0, 0, 0};
+            return Job{reinterpret_cast<unsigned char *>(dst + a), reinterpret_cast<const unsigned char *>(src + a), (b - a) * 4, 1, 0, 0, true};
+        });
         return !inexact.load(std::memory_order_relaxed);
     }
 };
 
 void lumahip_copy_pool_destroy(lumahip_copy_pool *p) { delete p; }
 
-static void staged_copy(lumahip_ctx *c, unsigned char *dst, size_t dp, const unsigned char *src, size_t sp, size_t width, size_t rows)
+// the context's copy threads, started on first use; nullptr: none ("copy_threads" 0), the calling thread copies alone
+static lumahip_copy_pool *copy_pool(lumahip_ctx *c)
 {
     if (c->copy_threads > 0 && !c->copy_pool) {
         numa_resolve(c);
         c->copy_pool = new lumahip_copy_pool(c->copy_threads, c->copy_spin, c->numa_mode == 2 ? std::vector<int>() : c->numa_cpus);
     }
-    if (c->copy_pool)
-        c->copy_pool->copy(dst, dp, src, sp, width, rows);
+    return c->copy_pool;
+}
+
+static void staged_copy(lumahip_ctx *c, unsigned char *dst, size_t dp, const unsigned char *src, size_t sp, size_t width, size_t rows)
+{
+    if (lumahip_copy_pool *pool = copy_pool(c))
+        pool->copy(dst, dp, src, sp, width, rows);
     else
         lumahip_copy_pool::run(lumahip_copy_pool::Job{dst, src, width, rows, dp, sp});
 }
@@ -250,18 +244,7 @@ static int stage_alloc(lumahip_ctx *c, lumahip_ctx::Stage &st, size_t bytes = XF
     return LUMAHIP_OK;
 }
 
-// an upload chunk is free again once the DMA that read it has completed
-static int stage_ready(lumahip_ctx *c, lumahip_ctx::Stage &st)
-{
-    if (int rc = stage_alloc(c, st))
-        return rc;
-    if (st.pending) {
-        HIPCHK(c, hipEventSynchronize(st.ev));
-        st.pending = false;
-    }
-    return LUMAHIP_OK;
-}
-
+// An upload chunk is free again once the DMA that read it has completed.
 // A download chunk is free again once its DMA has landed AND its bytes have been copied out to the caller's pageable
 // memory; the copy happens here, i.e. lazily, when the ring comes round to the chunk again or when a call drains what is
 // still in flight (d2h_flush).  The calling thread therefore never waits for a download it has only just queued: it goes
@@ -269,26 +252,29 @@ static int stage_ready(lumahip_ctx *c, lumahip_ctx::Stage &st)
 // 3.1 -> 4.1 Gpixel/s once the fetch of frame i-1 stopped blocking the staging of frame i+1).  A context-owned thread that
 // empties the chunks concurrently was built and measured as well: +2 % on that path, -5 % on the download-heavy decode
 // calls (it copies single-threaded where this thread uses the copy threads), so it was not kept (profiles/r03_hostfed_sweep.txt).
-static int stage_dn_ready(lumahip_ctx *c, lumahip_ctx::Stage &st)
+static int stage_ready(lumahip_ctx *c, lumahip_ctx::Stage &st, size_t bytes = XFER_CHUNK)
 {
-    if (int rc = stage_alloc(c, st, c->dn_chunk))
+    if (int rc = stage_alloc(c, st, bytes))
         return rc;
     if (st.pending) {
         HIPCHK(c, hipEventSynchronize(st.ev));
         st.pending = false;
-        staged_copy(c, st.out, st.out_pitch, st.h, st.chunk_pitch, st.width, st.rows);
-        st.out = nullptr;
+        if (st.out) {   // (a pending download chunk; upload chunks have nowhere to go)
+            staged_copy(c, st.out, st.out_pitch, st.h, st.chunk_pitch, st.width, st.rows);
+            st.out = nullptr;
+        }
     }
     return LUMAHIP_OK;
 }
 
-// every device -> host chunk still in flight: wait for it and copy it out (oldest first)
-static int d2h_flush(lumahip_ctx *c)
+// Every device -> host chunk still in flight: wait for it and copy it out (chunks are in issue order, oldest first).  With
+// `upto` (the pop of a pushed frame): only the chunks of pushed frames up to that sequence number and those of plain calls
+static int d2h_flush(lumahip_ctx *c, const unsigned *upto = nullptr)
 {
     for (int i = 0; i < lumahip_ctx::N_STAGE_DN; i++) {
         lumahip_ctx::Stage &st = c->stage_dn[(c->dn_next + i) % lumahip_ctx::N_STAGE_DN];
-        if (st.h && st.pending)
-            if (int rc = stage_dn_ready(c, st))
+        if (st.h && st.pending && (!upto || (int)(st.tag - (*upto + 1)) <= 0))   // (tags are sequence number + 1; 0 = a chunk of a plain call: always due)
+            if (int rc = stage_ready(c, st, c->dn_chunk))
                 return rc;
     }
     return LUMAHIP_OK;
@@ -346,15 +332,26 @@ static int dn_chunks_for(lumahip_ctx *c, size_t planes_bytes)
     return LUMAHIP_OK;
 }
 
-// the chunks of pushed frames up to sequence number `seq` (stream entry points; chunks are in issue order, oldest first)
-static int d2h_flush_upto(lumahip_ctx *c, unsigned seq)
+// The two ends of a staged upload.  up_chunk_take: the next upload chunk of the ring, free again, and *cap = how many bytes of it
+// this call fills.  The first chunks of a call are small (1, 2, 4 MiB, then whole chunks): the copy engine starts after 15 us of
+// staging instead of after the 110 us a whole chunk takes to fill, and nothing of that lead is lost later because the
+// DMA of a chunk (150 us) takes longer than filling the next one.
+static int up_chunk_take(lumahip_ctx *c, lumahip_ctx::Stage **st, size_t *cap)
 {
-    for (int i = 0; i < lumahip_ctx::N_STAGE_DN; i++) {
-        lumahip_ctx::Stage &st = c->stage_dn[(c->dn_next + i) % lumahip_ctx::N_STAGE_DN];
-        if (st.h && st.pending && (int)(st.tag - (seq + 1)) <= 0)   // (tags are sequence number + 1; 0 = a chunk of a plain call: always due)
-            if (int rc = stage_dn_ready(c, st))
-                return rc;
-    }
+    *st = &c->stage_up[c->up_next++ % lumahip_ctx::N_STAGE];
+    if (int rc = stage_ready(c, **st))
+        return rc;
+    *cap = XFER_CHUNK;
+    if (c->up_ramp < 3)
+        *cap = std::min(*cap, (size_t)1 << (20 + c->up_ramp++));
+    return LUMAHIP_OK;
+}
+// up_chunk_queue: the DMA of the chunk's first `bytes` bytes to `dst` on `s`, and the event that frees the chunk
+static int up_chunk_queue(lumahip_ctx *c, lumahip_ctx::Stage &st, void *dst, size_t bytes, hipStream_t s)
+{
+    HIPCHK(c, hipMemcpyAsync(dst, st.h, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(st.ev, s));
+    st.pending = true;
     return LUMAHIP_OK;
 }
 
@@ -378,29 +375,22 @@ static int xfer_h2d_2d(lumahip_ctx *c, void *dst, size_t dp, const void *src, si
         return fail(c, LUMAHIP_ERR_ARG, "row pitch %zu exceeds the staging chunk", dp);
     const size_t total = flat ? width * rows : rows;                 // bytes or rows
     for (size_t done = 0; done < total;) {
-        lumahip_ctx::Stage &st = c->stage_up[c->up_next++ % lumahip_ctx::N_STAGE];
-        int rc = stage_ready(c, st);
-        if (rc)
+        lumahip_ctx::Stage *st;
+        size_t cap;
+        if (int rc = up_chunk_take(c, &st, &cap))
             return rc;
-        // The first chunks of a call are small (1, 2, 4 MiB, then whole chunks): the copy engine starts after 15 us of
-        // staging instead of after the 110 us a whole chunk takes to fill, and nothing of that lead is lost later because the
-        // DMA of a chunk (150 us) takes longer than filling the next one.
-        size_t cap = XFER_CHUNK;
-        if (c->up_ramp < 3)
-            cap = std::min(cap, (size_t)1 << (20 + c->up_ramp++));
         const size_t per = flat ? cap : std::max<size_t>(1, cap / dp);   // bytes or rows per chunk
         const size_t n = total - done < per ? total - done : per;
         size_t bytes;
         if (flat) {
-            staged_copy(c, st.h, 0, (const unsigned char *)src + done, 0, n, 1);
+            staged_copy(c, st->h, 0, (const unsigned char *)src + done, 0, n, 1);
             bytes = n;
         } else {
-            staged_copy(c, st.h, dp, (const unsigned char *)src + done * hp, hp, width, n);
+            staged_copy(c, st->h, dp, (const unsigned char *)src + done * hp, hp, width, n);
             bytes = (n - 1) * dp + width;
         }
-        HIPCHK(c, hipMemcpyAsync((unsigned char *)dst + done * (flat ? 1 : dp), st.h, bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipEventRecord(st.ev, s));
-        st.pending = true;
+        if (int rc = up_chunk_queue(c, *st, (unsigned char *)dst + done * (flat ? 1 : dp), bytes, s))
+            return rc;
         done += n;
     }
     return LUMAHIP_OK;
@@ -424,27 +414,21 @@ int xfer_h2d(lumahip_ctx *c, void *dst, const void *src, size_t bytes, hipStream
 static int xfer_h2d_f16(lumahip_ctx *c, void *dst_halves, const float *src, size_t nfloats, hipStream_t s, bool *exact)
 {
     *exact = true;
-    if (c->copy_threads > 0 && !c->copy_pool) {
-        numa_resolve(c);
-        c->copy_pool = new lumahip_copy_pool(c->copy_threads, c->copy_spin, c->numa_mode == 2 ? std::vector<int>() : c->numa_cpus);
-    }
+    lumahip_copy_pool *const pool = copy_pool(c);
     for (size_t done = 0; done < nfloats;) {
-        lumahip_ctx::Stage &st = c->stage_up[c->up_next++ % lumahip_ctx::N_STAGE];
-        if (int rc = stage_ready(c, st))
+        lumahip_ctx::Stage *st;
+        size_t cap;   // bytes of halves
+        if (int rc = up_chunk_take(c, &st, &cap))
             return rc;
-        size_t cap = XFER_CHUNK;   // bytes of halves per chunk; the first chunks of a call are small (see xfer_h2d_2d)
-        if (c->up_ramp < 3)
-            cap = std::min(cap, (size_t)1 << (20 + c->up_ramp++));
         const size_t n = std::min(nfloats - done, cap / 2);
-        const bool ok = c->copy_pool ? c->copy_pool->copy_to_half(reinterpret_cast<uint16_t *>(st.h), src + done, n)
-                                     : lh::convert_f32_to_f16_checked(src + done, reinterpret_cast<uint16_t *>(st.h), n);
+        const bool ok = pool ? pool->copy_to_half(reinterpret_cast<uint16_t *>(st->h), src + done, n)
+                             : lh::convert_f32_to_f16_checked(src + done, reinterpret_cast<uint16_t *>(st->h), n);
         if (!ok) {
             *exact = false;
             return LUMAHIP_OK;
         }
-        HIPCHK(c, hipMemcpyAsync((unsigned char *)dst_halves + done * 2, st.h, n * 2, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipEventRecord(st.ev, s));
-        st.pending = true;
+        if (int rc = up_chunk_queue(c, *st, (unsigned char *)dst_halves + done * 2, n * 2, s))
+            return rc;
         done += n;
     }
     return LUMAHIP_OK;
@@ -477,6 +461,29 @@ static void in16_result(lumahip_ctx *c, bool exact)
     }
 }
 
+// `count` spans of n floats each, span i at element off + i * stride of BOTH the caller's frame `src` and the device frame `dst`
+// (one whole packed frame: one span; a row band: the band's rows of each of the three channels)
+struct FloatSpans { float *dst; const float *src; size_t off, n, count, stride; };
+
+// The spans go up on `s`: as halves -- at the same element offsets of dst read as uint16_t -- if `try16` and every value is one,
+// else as floats; *as16 says which.  A span that holds other values ends the attempt (nothing of its chunk has been queued) and
+// ALL spans go up as floats, after before_floats(): what the caller has to do before floats overwrite the halves already queued.
+template <typename BeforeFloats>
+static int upload_floats(lumahip_ctx *c, const FloatSpans &sp, hipStream_t s, bool try16, bool *as16, BeforeFloats before_floats)
+{
+    int rc = LUMAHIP_OK;
+    *as16 = try16;
+    for (size_t i = 0; i < sp.count && rc == LUMAHIP_OK && *as16; i++)
+        rc = xfer_h2d_f16(c, reinterpret_cast<uint16_t *>(sp.dst) + sp.off + i * sp.stride, sp.src + sp.off + i * sp.stride, sp.n, s, as16);
+    if (rc || *as16)
+        return rc;
+    if (try16 && (rc = before_floats()))
+        return rc;
+    for (size_t i = 0; i < sp.count && rc == LUMAHIP_OK; i++)
+        rc = xfer_h2d(c, sp.dst + sp.off + i * sp.stride, sp.src + sp.off + i * sp.stride, sp.n * sizeof(float), s);
+    return rc;
+}
+
 // Device -> host.  Pinned destination: queued on `s`, the caller synchronises.  Pageable destination: the data goes through
 // the ring of pinned chunks; with `deferred` false it is in `dst` when the call returns (everything queued on `s` before it has
 // completed by then), with `deferred` true the last chunks may still be in flight and d2h_flush() completes them -- which lets
@@ -500,25 +507,17 @@ static int xfer_d2h_2d(lumahip_ctx *c, void *dst, size_t hp, const void *src, si
     const size_t per = flat ? c->dn_chunk : c->dn_chunk / dp;
     for (size_t done = 0; done < total;) {
         lumahip_ctx::Stage &st = c->stage_dn[c->dn_next++ % lumahip_ctx::N_STAGE_DN];
-        int rc = stage_dn_ready(c, st);   // the chunk this ring slot carried N_STAGE_DN chunks ago has been emptied
-        if (rc)
+        if (int rc = stage_ready(c, st, c->dn_chunk))   // the chunk this ring slot carried N_STAGE_DN chunks ago has been emptied
             return rc;
         const size_t n = total - done < per ? total - done : per;
         const size_t bytes = flat ? n : (n - 1) * dp + width;
         HIPCHK(c, hipMemcpyAsync(st.h, (const unsigned char *)src + done * (flat ? 1 : dp), bytes, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(st.ev, s));
-        if (flat) {
-            st.out = (unsigned char *)dst + done;
-            st.out_pitch = st.chunk_pitch = 0;
-            st.width = n;
-            st.rows = 1;
-        } else {
-            st.out = (unsigned char *)dst + done * hp;
-            st.out_pitch = hp;
-            st.chunk_pitch = dp;
-            st.width = width;
-            st.rows = n;
-        }
+        st.out = (unsigned char *)dst + done * (flat ? 1 : hp);   // what stage_ready copies out: one span of n bytes, or n rows
+        st.out_pitch = flat ? 0 : hp;
+        st.chunk_pitch = flat ? 0 : dp;
+        st.width = flat ? n : width;
+        st.rows = flat ? 1 : n;
         st.tag = c->d2h_tag;
         st.pending = true;
         done += n;
@@ -565,6 +564,7 @@ int ensure(lumahip_ctx *c, void **p, size_t *cap, size_t need)
 }  // namespace lhost
 
 struct PlaneLayout {
+    bool sub;           // 4:2:0: the colour planes have half the rows and half the columns
     int rows[3];
     int row_bytes[3];
     size_t off[3];
@@ -576,6 +576,7 @@ static void plane_layout(PlaneLayout &L, unsigned w, unsigned h, int profile, co
     const bool sub = (profile == 0 || profile == 2);
     const int bps = profile > 1 ? 2 : 1;
     size_t off = 0;
+    L.sub = sub;
     for (int p = 0; p < 3; p++) {
         const int pw = (p && sub) ? (int)(w + 1) / 2 : (int)w;
         const int ph = (p && sub) ? (int)(h + 1) / 2 : (int)h;
@@ -596,6 +597,35 @@ static int bad_plane(const PlaneLayout &L, const unsigned char *const planes[3],
     return -1;
 }
 
+// frame rows -> rows of plane p (frames have even heights and bands start at multiples of 16 rows: nothing is cut off)
+static unsigned plane_row(const PlaneLayout &L, int p, unsigned r) { return (p && L.sub) ? r / 2 : r; }
+
+// dp[] = the three code planes in the device buffer `base` (the context's or a slot's), from frame row r0 on
+static void device_planes(unsigned char *dp[3], unsigned char *base, const PlaneLayout &L, const int stride[3], unsigned r0 = 0)
+{
+    for (int p = 0; p < 3; p++)
+        dp[p] = base + L.off[p] + (size_t)plane_row(L, p, r0) * stride[p];
+}
+
+// Rows [r0, r0 + rows) of the frame, code plane p: caller's plane -> device plane (dp[]: the whole planes) ...
+static int plane_h2d(lumahip_ctx *c, unsigned char *const dp[3], const unsigned char *const planes[3], const int stride[3], const PlaneLayout &L,
+                     int p, unsigned r0, unsigned rows, hipStream_t s)
+{
+    const size_t off = (size_t)plane_row(L, p, r0) * stride[p];
+    return xfer_h2d_2d(c, dp[p] + off, stride[p], planes[p] + off, stride[p], L.row_bytes[p], plane_row(L, p, rows), s);
+}
+// ... and the three device planes -> the caller's (deferred: see xfer_d2h_2d)
+static int planes_d2h(lumahip_ctx *c, unsigned char *const planes[3], unsigned char *const dp[3], const int stride[3], const PlaneLayout &L,
+                      unsigned r0, unsigned rows, hipStream_t s, bool deferred)
+{
+    for (int p = 0; p < 3; p++) {
+        const size_t off = (size_t)plane_row(L, p, r0) * stride[p];
+        if (int rc = xfer_d2h_2d(c, planes[p] + off, stride[p], dp[p] + off, stride[p], L.row_bytes[p], plane_row(L, p, rows), s, deferred))
+            return rc;
+    }
+    return LUMAHIP_OK;
+}
+
 // What the single-frame host calls open with: the arguments checked, the plane layout, the context's staging buffers large
 // enough for one w x h frame of floats (binary16 frames share them) and its planes, dp[] = the device planes
 static int frame_staging(lumahip_ctx *c, const void *frame, const unsigned char *const planes[3], const int stride[3], unsigned w,
@@ -607,7 +637,7 @@ static int frame_staging(lumahip_ctx *c, const void *frame, const unsigned char 
     if (rc)
         return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
+    c->up_ramp = 0;   // (per call, like the push; the frames of a batched call share one ramp)
     plane_layout(L, w, h, profile, stride);
     const int p = bad_plane(L, planes, stride);
     if (p >= 0)
@@ -616,8 +646,7 @@ static int frame_staging(lumahip_ctx *c, const void *frame, const unsigned char 
         return rc;
     if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)))
         return rc;
-    for (int k = 0; k < 3; k++)
-        dp[k] = c->d_planes + L.off[k];
+    device_planes(dp, c->d_planes, L, stride);
     return LUMAHIP_OK;
 }
 
@@ -636,7 +665,106 @@ static bool mean_needs_reference_sum(float mean, float minimum, unsigned w, unsi
     return mean >= 0.25f && mean <= 4.0f;
 }
 
-static int pipe_streams(lumahip_ctx *c);
+// ---- the 3-stage pipeline every host-fed loop runs ------------------------------------------------------------------------
+// Three streams: stage t goes up on s_h2d | stage t's kernel runs on s_kern behind the upload's event | stage t-1 comes down on
+// s_d2h behind its kernel's event.  A stage is a frame in one of the three device slots (the batched calls; the stream push /
+// pop, where the loop is carried across calls) or a row band of one frame in the context's staging buffers.  With pinned caller
+// memory (lumahip_host_register) the two copy directions overlap as well and the rate approaches the PCIe H2D rate.
+static int pipe_streams(lumahip_ctx *c)
+{
+    if (!c->s_h2d) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
+        HIPCHK(c, hipStreamCreateWithFlags(&c->s_kern, hipStreamNonBlocking));
+        HIPCHK(c, hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
+    }
+    return LUMAHIP_OK;
+}
+
+struct PipeStage {
+    hipEvent_t h2d, kern;
+    hipEvent_t d2h;    // null for a row band: nothing waits for a band's download but the end of the call
+    float *d_stats;    // where the stage's encode kernel leaves its statistics triple
+    bool reuses;       // its device buffers were those of the stage three before it (slots, from the fourth frame on)
+};
+static PipeStage slot_stage(const lumahip_ctx::Slot &sl, unsigned seq) { return {sl.h2d, sl.kern, sl.d2h, sl.d_stats, seq >= 3}; }
+static PipeStage band_stage(lumahip_ctx *c, unsigned k) { return {c->band_h2d[k], c->band_kern[k], nullptr, c->d_band_stats + 3 * k, false}; }
+
+// The front half of a stage: upload() queues the stage's input on s_h2d, launch() its kernel on s_kern.  A failing event call
+// is reported like a failing transfer or launch (the batched and push forms used to discard those results).
+template <typename Upload, typename Launch>
+static int pipe_issue(lumahip_ctx *c, const PipeStage &st, Upload &&upload, Launch &&launch)
+{
+    if (st.reuses) {
+        // The previous occupant's kernel must have consumed the stage's input buffer, its download must have drained the output
+        // buffer.  (Stream push: that frame was popped long ago and both are done, but the streams still have to be told.)
+        HIPCHK(c, hipStreamWaitEvent(c->s_h2d, st.kern, 0));
+        HIPCHK(c, hipStreamWaitEvent(c->s_kern, st.d2h, 0));
+    }
+    if (int rc = upload())
+        return rc;
+    HIPCHK(c, hipEventRecord(st.h2d, c->s_h2d));
+    HIPCHK(c, hipStreamWaitEvent(c->s_kern, st.h2d, 0));
+    if (int rc = launch())
+        return rc;
+    HIPCHK(c, hipEventRecord(st.kern, c->s_kern));
+    return LUMAHIP_OK;
+}
+
+// The back half: download() queues the stage's output on s_d2h, behind its kernel.  The downloads are DEFERRED: pageable
+// destinations are copied out of the staging chunks when the ring comes round to them, by pipe_drain or by the pop -- not here,
+// where it would hold up the staging of the next stage's upload (see stage_ready).  h_stats: pinned, where the statistics
+// triple goes along (nullptr: not wanted).
+template <typename Download>
+static int pipe_fetch(lumahip_ctx *c, const PipeStage &st, Download &&download, float *h_stats)
+{
+    HIPCHK(c, hipStreamWaitEvent(c->s_d2h, st.kern, 0));
+    if (int rc = download())
+        return rc;
+    if (h_stats)
+        HIPCHK(c, hipMemcpyAsync(h_stats, st.d_stats, 3 * sizeof(float), hipMemcpyDeviceToHost, c->s_d2h));
+    if (st.d2h)
+        HIPCHK(c, hipEventRecord(st.d2h, c->s_d2h));
+    return LUMAHIP_OK;
+}
+
+// The end of a pipelined call, after an error as well (rc: the error so far; nothing may stay pending): the download chunks
+// still in flight are copied out -- only then is the guard told that nothing points into the caller's memory any more -- and the
+// three streams run dry.  Returns the first error.
+static int pipe_drain(lumahip_ctx *c, DnGuard &guard, int rc)
+{
+    if (int r = d2h_flush(c))
+        rc = rc ? rc : r;
+    else
+        guard.armed = false;
+    for (hipStream_t s : {c->s_h2d, c->s_kern, c->s_d2h}) {
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess && rc == LUMAHIP_OK)
+            rc = fail(c, LUMAHIP_ERR_HIP, "hipStreamSynchronize failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+    }
+    return rc;
+}
+
+// n stages, one behind: stage t is uploaded and launched BEFORE stage t-1 is fetched, the last one is fetched after the loop.
+// stage_of(t): its events; upload(t), launch(t, stage), download(t): its bodies; h_stats as in pipe_fetch, 3 floats per stage.
+// Every failure ends the loop and goes through the drain; if the drain itself cannot empty the chunks, the guard drops them.
+template <typename StageOf, typename Upload, typename Launch, typename Download>
+static int pipe_run(lumahip_ctx *c, unsigned n, StageOf stage_of, Upload upload, Launch launch, Download download, float *h_stats = nullptr)
+{
+    DnGuard guard{c, false, 0};   // a failing exit drops the download chunks still pointing at the caller's buffers
+    auto fetch_stage = [&](unsigned t) {
+        return pipe_fetch(c, stage_of(t), [&] { return download(t); }, h_stats ? h_stats + 3 * (size_t)t : nullptr);
+    };
+    int rc = LUMAHIP_OK;
+    for (unsigned t = 0; t < n && rc == LUMAHIP_OK; t++) {
+        const PipeStage st = stage_of(t);
+        rc = pipe_issue(c, st, [&] { return upload(t); }, [&] { return launch(t, st); });
+        if (rc == LUMAHIP_OK && t >= 1)
+            rc = fetch_stage(t - 1);
+    }
+    if (rc == LUMAHIP_OK)
+        rc = fetch_stage(n - 1);
+    return pipe_drain(c, guard, rc);
+}
 
 // ---- row bands ------------------------------------------------------------------------------------------------------------
 // One host frame per call is PCIe time: 99.5 MB up at ~56 GB/s (1.76 ms), 30 us of kernel, 24.9 MB down (0.45 ms); done one
@@ -677,8 +805,12 @@ static int band_plan(const lumahip_ctx *c, unsigned w, unsigned h, unsigned r0[l
     return k;   // number of bands; band i = rows [r0[i], r0[i+1])
 }
 
-static int band_events(lumahip_ctx *c, int nb)
+// what a banded call opens with: the pipeline's streams, the bands' events and statistics, and the context's stream run dry --
+// the bands run on the pipeline streams, after everything queued so far
+static int band_prepare(lumahip_ctx *c, int nb)
 {
+    if (int rc = pipe_streams(c))
+        return rc;
     for (int k = 0; k < nb; k++)
         if (!c->band_h2d[k]) {
             HIPCHK(c, hipEventCreateWithFlags(&c->band_h2d[k], hipEventDisableTiming));
@@ -686,6 +818,7 @@ static int band_events(lumahip_ctx *c, int nb)
         }
     if (!c->d_band_stats)
         HIPCHK(c, hipMalloc(&c->d_band_stats, lumahip_ctx::MAX_BANDS * 3 * sizeof(float)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return LUMAHIP_OK;
 }
 
@@ -707,7 +840,6 @@ static int encode_frame_host_impl(lumahip_ctx *c, const void *rgb_any, Elem elem
     const float *const rgb = typed16 ? nullptr : static_cast<const float *>(rgb_any);
     const size_t nfl = (size_t)3 * w * h;
     const size_t n1 = (size_t)w * h;
-    const bool sub = (profile == 0 || profile == 2);
     unsigned band0[lumahip_ctx::MAX_BANDS + 1];
     const int nb = typed16 ? 1 : band_plan(c, w, h, band0);
     float st[3] = {0.0f, __builtin_inff(), -__builtin_inff()};
@@ -718,66 +850,36 @@ static int encode_frame_host_impl(lumahip_ctx *c, const void *rgb_any, Elem elem
     const bool tried16 = use16;
     uint16_t *const d16 = reinterpret_cast<uint16_t *>(c->d_frame);   // the staging frame when it holds halves: same element offsets
     auto staged = [&]() -> SrcFrames { return frame16 ? packed_frames<const uint16_t>(d16, nfl, 1, w, h) : packed_frames<const float>(c->d_frame, nfl, 1, w, h); };
+    // the caller's floats (the whole frame, or a band of it) into the staging frame; once a piece has gone up as floats, so do the rest
+    auto upload = [&](const FloatSpans &sp, hipStream_t s, auto before_floats) {
+        bool as16;
+        const int r = upload_floats(c, sp, s, use16, &as16, before_floats);
+        use16 = frame16 = use16 && as16;
+        return r;
+    };
     if (nb > 1) {
-        if ((rc = pipe_streams(c)) || (rc = band_events(c, nb)))
+        if ((rc = band_prepare(c, nb)))
             return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // the bands run on the pipeline streams: after everything queued so far
-        DnGuard dn_guard{c, false, 0};   // a failing exit below drops the download chunks still pointing at the caller's planes
-        auto fetch = [&](int k) -> int {              // planes rows of band k, after its kernel
-            const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
-            HIPCHK(c, hipStreamWaitEvent(c->s_d2h, c->band_kern[k], 0));
-            for (int p = 0; p < 3; p++) {
-                const unsigned pr0 = (p && sub) ? r0 / 2 : r0, prow = (p && sub) ? rows / 2 : rows;
-                const size_t off = (size_t)pr0 * stride[p];
-                if (int r = xfer_d2h_2d(c, planes[p] + off, stride[p], dp[p] + off, stride[p], L.row_bytes[p], prow, c->s_d2h, true))
-                    return r;
-            }
-            return LUMAHIP_OK;
-        };
-        for (int k = 0; k < nb && rc == LUMAHIP_OK; k++) {
-            const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
-            const size_t roff = (size_t)r0 * w;
-            if (use16) {
-                bool exact = true;
-                for (int ch = 0; ch < 3 && rc == LUMAHIP_OK && exact; ch++)
-                    rc = xfer_h2d_f16(c, d16 + ch * n1 + roff, rgb + ch * n1 + roff, (size_t)rows * w, c->s_h2d, &exact);
-                if (rc)
-                    break;
-                if (!exact) {
+        rc = pipe_run(
+            c, nb, [&](unsigned k) { return band_stage(c, k); },
+            [&](unsigned k) {
+                const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
+                return upload({c->d_frame, rgb, (size_t)r0 * w, (size_t)rows * w, 3, n1}, c->s_h2d, [&] {
                     // this band holds values that are not halves: it and the rest of the frame go up as floats -- into the same
                     // buffer, at float offsets, which the kernels of the earlier bands may still be reading as halves: wait for them
-                    use16 = frame16 = false;
                     mixed = k > 0;
                     HIPCHK(c, hipStreamSynchronize(c->s_kern));
-                }
-            }
-            if (!use16) {
-                for (int ch = 0; ch < 3 && rc == LUMAHIP_OK; ch++)
-                    rc = xfer_h2d(c, c->d_frame + ch * n1 + roff, rgb + ch * n1 + roff, (size_t)rows * w * sizeof(float), c->s_h2d);
-                if (rc)
-                    break;
-            }
-            HIPCHK(c, hipEventRecord(c->band_h2d[k], c->s_h2d));
-            HIPCHK(c, hipStreamWaitEvent(c->s_kern, c->band_h2d[k], 0));
-            unsigned char *bp[3];
-            for (int p = 0; p < 3; p++)
-                bp[p] = dp[p] + (size_t)((p && sub) ? r0 / 2 : r0) * stride[p];
-            if ((rc = encode_frames_device_impl(c, row_band(staged(), r0, rows), sc, {bp, stride, NO_PFS, profile}, c->d_band_stats + 3 * k,
-                                                {cs_eff, c->s_kern, false, HalfSource::Upload})))
-                break;
-            HIPCHK(c, hipEventRecord(c->band_kern[k], c->s_kern));
-            if (k >= 1)
-                rc = fetch(k - 1);
-        }
-        if (rc == LUMAHIP_OK)
-            rc = fetch(nb - 1);
-        if (int r = d2h_flush(c))   // the chunks still in flight (also after an error: nothing may stay pending)
-            rc = rc ? rc : r;
-        else
-            dn_guard.armed = false;
-        HIPCHK(c, hipStreamSynchronize(c->s_h2d));
-        HIPCHK(c, hipStreamSynchronize(c->s_kern));
-        HIPCHK(c, hipStreamSynchronize(c->s_d2h));
+                    return (int)LUMAHIP_OK;
+                });
+            },
+            [&](unsigned k, const PipeStage &bs) {
+                const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
+                unsigned char *bp[3];
+                device_planes(bp, c->d_planes, L, stride, r0);
+                return encode_frames_device_impl(c, row_band(staged(), r0, rows), sc, {bp, stride, NO_PFS, profile}, bs.d_stats,
+                                                 {cs_eff, c->s_kern, false, HalfSource::Upload});
+            },
+            [&](unsigned k) { return planes_d2h(c, planes, dp, stride, L, band0[k], band0[k + 1] - band0[k], c->s_d2h, true); });
         if (rc)
             return rc;
         float bs[lumahip_ctx::MAX_BANDS * 3];
@@ -789,23 +891,15 @@ static int encode_frame_host_impl(lumahip_ctx *c, const void *rgb_any, Elem elem
             st[2] = fmaxf(st[2], bs[3 * k + 2]);
         }
     } else {
-        if (typed16 && (rc = xfer_h2d(c, d16, rgb_any, nfl * sizeof(uint16_t), c->stream)))
-            return rc;
-        if (use16) {
-            bool exact = true;
-            if ((rc = xfer_h2d_f16(c, d16, rgb, nfl, c->stream, &exact)))
-                return rc;
-            if (!exact)
-                use16 = frame16 = false;   // (nothing has been launched on the halves: the floats simply follow on the same stream)
-        }
-        if (!frame16 && (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))
+        // (a frame that turns out not to hold halves: nothing has been launched on them, the floats simply follow on the same stream)
+        if ((rc = typed16 ? xfer_h2d(c, d16, rgb_any, nfl * sizeof(uint16_t), c->stream)
+                          : upload({c->d_frame, rgb, 0, nfl, 1, 0}, c->stream, [] { return (int)LUMAHIP_OK; })))
             return rc;
         if ((rc = encode_frames_device_impl(c, staged(), sc, {dp, stride, NO_PFS, profile}, c->d_stats,
                                             {cs_eff, c->stream, false, typed16 ? HalfSource::Typed : HalfSource::Upload})))
             return rc;
-        for (int p = 0; p < 3; p++)
-            if ((rc = xfer_d2h_2d(c, planes[p], stride[p], dp[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
-                return rc;
+        if ((rc = planes_d2h(c, planes, dp, stride, L, 0, h, c->stream, false)))
+            return rc;
     }
     if (transformed_out) {
         rc = lumahip_transform_color_space_device(c, c->d_frame, nfl, 1, w, h, 1, sc);
@@ -853,56 +947,36 @@ static int decode_frame_host_impl(lumahip_ctx *c, const unsigned char *const pla
         return rc;
     const size_t nfl = (size_t)3 * w * h;
     const size_t n1 = (size_t)w * h;
-    const bool sub = (profile == 0 || profile == 2);
     unsigned band0[lumahip_ctx::MAX_BANDS + 1];
     const int nb = elem == Elem::F16 ? 1 : band_plan(c, w, h, band0);
     if (nb > 1) {
         float *const rgb_f = static_cast<float *>(rgb_out);
-        if ((rc = pipe_streams(c)) || (rc = band_events(c, nb)))
+        if ((rc = band_prepare(c, nb)))
             return rc;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        DnGuard dn_guard{c, false, 0};   // a failing exit below drops the download chunks still pointing at the caller's planes
-        auto fetch = [&](int k) -> int {              // float rows of band k, after its kernel
-            const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
-            const size_t roff = (size_t)r0 * w;
-            HIPCHK(c, hipStreamWaitEvent(c->s_d2h, c->band_kern[k], 0));
-            for (int ch = 0; ch < 3; ch++)
-                if (int r = xfer_d2h_deferred(c, rgb_f + ch * n1 + roff, c->d_frame + ch * n1 + roff, (size_t)rows * w * sizeof(float), c->s_d2h))
-                    return r;
-            return LUMAHIP_OK;
-        };
-        for (int k = 0; k < nb && rc == LUMAHIP_OK; k++) {
-            const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
-            const unsigned char *bp[3];
-            for (int p = 0; p < 3 && rc == LUMAHIP_OK; p++) {
-                const unsigned pr0 = (p && sub) ? r0 / 2 : r0, prow = (p && sub) ? rows / 2 : rows;
-                const size_t off = (size_t)pr0 * stride[p];
-                bp[p] = dp[p] + off;
-                rc = xfer_h2d_2d(c, dp[p] + off, stride[p], planes[p] + off, stride[p], L.row_bytes[p], prow, c->s_h2d);
-            }
-            if (rc)
-                break;
-            HIPCHK(c, hipEventRecord(c->band_h2d[k], c->s_h2d));
-            HIPCHK(c, hipStreamWaitEvent(c->s_kern, c->band_h2d[k], 0));
-            if ((rc = decode_impl(c, {bp, stride, NO_PFS, profile}, sc, row_band(packed_frames(c->d_frame, nfl, 1, w, h), r0, rows), {cs_eff, c->s_kern})))
-                break;
-            HIPCHK(c, hipEventRecord(c->band_kern[k], c->s_kern));
-            if (k >= 1)
-                rc = fetch(k - 1);
-        }
-        if (rc == LUMAHIP_OK)
-            rc = fetch(nb - 1);
-        if (int r = d2h_flush(c))   // the chunks still in flight (also after an error: nothing may stay pending)
-            rc = rc ? rc : r;
-        else
-            dn_guard.armed = false;
-        HIPCHK(c, hipStreamSynchronize(c->s_h2d));
-        HIPCHK(c, hipStreamSynchronize(c->s_kern));
-        HIPCHK(c, hipStreamSynchronize(c->s_d2h));
-        return rc;
+        return pipe_run(
+            c, nb, [&](unsigned k) { return band_stage(c, k); },
+            [&](unsigned k) {
+                int r = LUMAHIP_OK;
+                for (int p = 0; p < 3 && r == LUMAHIP_OK; p++)
+                    r = plane_h2d(c, dp, planes, stride, L, p, band0[k], band0[k + 1] - band0[k], c->s_h2d);
+                return r;
+            },
+            [&](unsigned k, const PipeStage &) {
+                const unsigned r0 = band0[k], rows = band0[k + 1] - r0;
+                unsigned char *bp[3];
+                device_planes(bp, c->d_planes, L, stride, r0);
+                return decode_impl(c, {bp, stride, NO_PFS, profile}, sc, row_band(packed_frames(c->d_frame, nfl, 1, w, h), r0, rows), {cs_eff, c->s_kern});
+            },
+            [&](unsigned k) {   // the band's rows of each channel; floats come down with the default chunk size (no dn_chunks_for)
+                const size_t roff = (size_t)band0[k] * w, n = (size_t)(band0[k + 1] - band0[k]) * w;
+                int r = LUMAHIP_OK;
+                for (int ch = 0; ch < 3 && r == LUMAHIP_OK; ch++)
+                    r = xfer_d2h_deferred(c, rgb_f + ch * n1 + roff, c->d_frame + ch * n1 + roff, n * sizeof(float), c->s_d2h);
+                return r;
+            });
     }
     for (int p = 0; p < 3; p++)
-        if ((rc = xfer_h2d_2d(c, dp[p], stride[p], planes[p], stride[p], L.row_bytes[p], L.rows[p], c->stream)))
+        if ((rc = plane_h2d(c, dp, planes, stride, L, p, 0, h, c->stream)))
             return rc;
     const DstFrames staged = elem == Elem::F16 ? packed_frames(reinterpret_cast<uint16_t *>(c->d_frame), nfl, 1, w, h)   // (the staging frame holding halves)
                                                : packed_frames(c->d_frame, nfl, 1, w, h);
@@ -941,26 +1015,7 @@ extern "C" int lumahip_decode_frame_host_f16(lumahip_ctx *c, const unsigned char
     return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, Elem::F16, c->q.cs);
 }
 
-// ---- batched host entry points: a 3-slot software pipeline over three streams.  Frame i's H2D copy runs while
-// frame i-1's kernel and frame i-2's D2H copies are in flight; with pinned caller memory (lumahip_host_register) the
-// two copy directions overlap as well and the rate approaches the PCIe H2D rate.
-static int pipe_streams(lumahip_ctx *c)
-{
-    if (!c->s_h2d) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&c->s_kern, hipStreamNonBlocking));
-        HIPCHK(c, hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
-    }
-    return LUMAHIP_OK;
-}
-
-// the packed frame in a slot's device buffer: floats, or the halves the half upload put at the same element offsets
-static SrcFrames slot_frame(const lumahip_ctx::Slot &sl, bool halves, size_t nfl, unsigned w, unsigned h)
-{
-    return halves ? packed_frames<const uint16_t>(reinterpret_cast<const uint16_t *>(sl.d_frame), nfl, 1, w, h)
-                  : packed_frames<const float>(sl.d_frame, nfl, 1, w, h);
-}
-
+// ---- frames in the three device slots: the batched calls and the stream push / pop ---------------------------------------------
 static int pipe_prepare(lumahip_ctx *c, size_t frame_bytes, size_t planes_bytes, unsigned nframes)
 {
     if (int rc = pipe_streams(c))
@@ -996,92 +1051,121 @@ static int pipe_prepare(lumahip_ctx *c, size_t frame_bytes, size_t planes_bytes,
     return LUMAHIP_OK;
 }
 
+// What a slot stage does to one frame, in either direction; the batched loops and the pushes differ in where the frames come
+// from and in what happens around the steps, not in the steps
+namespace {
+struct SlotFrame {
+    lumahip_ctx *c;
+    PlaneLayout L;
+    const int *stride;
+    unsigned w, h;
+    int profile;
+    float sc;
+    size_t nfl() const { return (size_t)3 * w * h; }
+
+    // encode: the caller's floats into the slot -- as halves (*as16) where the context wants to try and the frame holds halves,
+    // with the half upload's bookkeeping; a frame that does not goes up as floats behind whatever part of it went up as halves
+    // (same stream, same slot, nothing launched on it yet)
+    int floats_up(lumahip_ctx::Slot &sl, const float *rgb, bool *as16) const
+    {
+        const bool try16 = in16_try(c, w, false);
+        const int rc = upload_floats(c, {sl.d_frame, rgb, 0, nfl(), 1, 0}, c->s_h2d, try16, as16, [&] {
+            in16_result(c, false);
+            return (int)LUMAHIP_OK;
+        });
+        if (rc == LUMAHIP_OK && *as16)
+            in16_result(c, true);
+        return rc;
+    }
+    int encode(lumahip_ctx::Slot &sl, bool halves) const
+    {
+        unsigned char *dp[3];
+        device_planes(dp, sl.d_planes, L, stride);
+        const SrcFrames f = halves ? packed_frames<const uint16_t>(reinterpret_cast<const uint16_t *>(sl.d_frame), nfl(), 1, w, h)   // same element offsets
+                                   : packed_frames<const float>(sl.d_frame, nfl(), 1, w, h);
+        return encode_frames_device_impl(c, f, sc, {dp, stride, NO_PFS, profile}, sl.d_stats, {c->q.cs, c->s_kern, false, HalfSource::Upload});
+    }
+    int planes_down(lumahip_ctx::Slot &sl, unsigned char *const planes[3]) const
+    {
+        unsigned char *dp[3];
+        device_planes(dp, sl.d_planes, L, stride);
+        return planes_d2h(c, planes, dp, stride, L, 0, h, c->s_d2h, true);
+    }
+    // decode: the caller's planes into the slot.  all_pinned (the push asks): whether the copy engine reads every plane directly
+    int planes_up(lumahip_ctx::Slot &sl, const unsigned char *const planes[3], bool *all_pinned = nullptr) const
+    {
+        unsigned char *dp[3];
+        device_planes(dp, sl.d_planes, L, stride);
+        int rc = LUMAHIP_OK;
+        if (all_pinned)
+            *all_pinned = true;
+        for (int p = 0; p < 3 && rc == LUMAHIP_OK; p++) {
+            if (all_pinned)
+                *all_pinned = *all_pinned && host_range_is_pinned(planes[p], (size_t)(L.rows[p] - 1) * stride[p] + L.row_bytes[p]);
+            rc = plane_h2d(c, dp, planes, stride, L, p, 0, h, c->s_h2d);
+        }
+        return rc;
+    }
+    int decode(lumahip_ctx::Slot &sl) const
+    {
+        unsigned char *dp[3];
+        device_planes(dp, sl.d_planes, L, stride);
+        return decode_impl(c, {dp, stride, NO_PFS, profile}, sc, packed_frames(sl.d_frame, nfl(), 1, w, h), {c->q.cs, c->s_kern});
+    }
+    int floats_down(lumahip_ctx::Slot &sl, float *rgb_out) const { return xfer_d2h_deferred(c, rgb_out, sl.d_frame, nfl() * sizeof(float), c->s_d2h); }
+};
+}  // namespace
+
+// What the two batched calls open with: the arguments checked (frames[i]: frame i on the host, `what` names it), no pushed frame
+// pending, the slots large enough.
+template <typename T>
+static int batch_begin(lumahip_ctx *c, T *const *frames, const char *what, const unsigned char *const *planes, const int stride[3], unsigned nframes,
+                       unsigned w, unsigned h, int profile, float sc, SlotFrame &f)
+{
+    if (!c || !frames || !planes || !stride || nframes == 0)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (int rc = check_geom(c, w, h, profile, c->q.cs))
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    f = SlotFrame{c, {}, stride, w, h, profile, sc};
+    plane_layout(f.L, w, h, profile, stride);
+    for (unsigned i = 0; i < nframes; i++) {
+        if (!frames[i])
+            return fail(c, LUMAHIP_ERR_ARG, "null %s %u", what, i);
+        const int p = bad_plane(f.L, planes + 3 * i, stride);
+        if (p >= 0)
+            return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
+    }
+    if (c->es_head != c->es_tail)
+        return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_encode_stream_push / lumahip_decode_stream_push are still pending: pop them first");
+    return pipe_prepare(c, f.nfl() * sizeof(float), f.L.total, nframes);
+}
+
 extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rgb, unsigned nframes, unsigned w, unsigned h,
                                           float sc, int profile, unsigned char *const *planes, const int stride[3],
                                           float *mean_lum)
 {
-    if (!c || !rgb || !planes || !stride || nframes == 0)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, c->q.cs);
+    SlotFrame f;
+    int rc = batch_begin(c, rgb, "frame", planes, stride, nframes, w, h, profile, sc, f);
     if (rc)
         return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    for (unsigned i = 0; i < nframes; i++) {
-        if (!rgb[i])
-            return fail(c, LUMAHIP_ERR_ARG, "null frame %u", i);
-        const int p = bad_plane(L, planes + 3 * i, stride);
-        if (p >= 0)
-            return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
-    }
-    const size_t nfl = (size_t)3 * w * h;
-    if (c->es_head != c->es_tail)
-        return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_encode_stream_push / lumahip_decode_stream_push are still pending: pop them first");
-    if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, nframes)))
+    // Download chunks sized for these planes: the pipelined ENCODE paths only (this call and the encode push).  The decode
+    // pipelines download floats with the default chunk.
+    if ((rc = dn_chunks_for(c, f.L.total)))
         return rc;
-    if ((rc = dn_chunks_for(c, L.total)))
-        return rc;
-    DnGuard dn_guard{c, false, 0};   // a failing exit drops the download chunks still pointing at the caller's buffers
-    // Frame i's upload and kernel are queued BEFORE frame i-1's planes are fetched.
-    auto fetch = [&](unsigned i) -> int {
-        lumahip_ctx::Slot &sl = c->slot[i % 3];
-        unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-        (void)hipStreamWaitEvent(c->s_d2h, sl.kern, 0);
-        int r = LUMAHIP_OK;
-        // (deferred: pageable planes are copied out of the staging chunks when the ring comes round to them or by the
-        // d2h_flush below -- not here, where it would hold up the staging of the next frame's upload)
-        for (int p = 0; p < 3 && r == LUMAHIP_OK; p++)
-            r = xfer_d2h_2d(c, planes[3 * i + p], stride[p], dp[p], stride[p], L.row_bytes[p], L.rows[p], c->s_d2h, true);
-        if (r)
-            return r;
-        (void)hipMemcpyAsync(c->h_stats + 3 * (size_t)i, sl.d_stats, 3 * sizeof(float), hipMemcpyDeviceToHost, c->s_d2h);
-        (void)hipEventRecord(sl.d2h, c->s_d2h);
-        return LUMAHIP_OK;
-    };
-    for (unsigned i = 0; i < nframes && rc == LUMAHIP_OK; i++) {
-        lumahip_ctx::Slot &sl = c->slot[i % 3];
-        unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-        if (i >= 3) {
-            // slot reuse: the kernel of frame i-3 must have consumed d_frame, its D2H must have drained d_planes
-            (void)hipStreamWaitEvent(c->s_h2d, sl.kern, 0);
-            (void)hipStreamWaitEvent(c->s_kern, sl.d2h, 0);
-        }
-        // half upload (xfer_h2d_f16) where the frame holds halves; a frame that does not goes up as floats behind whatever part
-        // of it went up as halves (same stream, same slot, nothing launched on it yet)
-        bool f16 = in16_try(c, w, false);
-        if (f16) {
-            bool exact = true;
-            if ((rc = xfer_h2d_f16(c, sl.d_frame, rgb[i], nfl, c->s_h2d, &exact)))
-                break;
-            in16_result(c, exact);
-            f16 = exact;
-        }
-        if (!f16 && (rc = xfer_h2d(c, sl.d_frame, rgb[i], nfl * sizeof(float), c->s_h2d)))
-            break;
-        (void)hipEventRecord(sl.h2d, c->s_h2d);
-        (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-        if ((rc = encode_frames_device_impl(c, slot_frame(sl, f16, nfl, w, h), sc, {dp, stride, NO_PFS, profile}, sl.d_stats,
-                                            {c->q.cs, c->s_kern, false, HalfSource::Upload})))
-            break;
-        (void)hipEventRecord(sl.kern, c->s_kern);
-        if (i >= 1)
-            rc = fetch(i - 1);
-    }
-    if (rc == LUMAHIP_OK)
-        rc = fetch(nframes - 1);
-    if (int r = d2h_flush(c))   // (also after an error: nothing may stay pending)
-        rc = rc ? rc : r;
-    else
-        dn_guard.armed = false;
-    HIPCHK(c, hipStreamSynchronize(c->s_h2d));
-    HIPCHK(c, hipStreamSynchronize(c->s_kern));
-    HIPCHK(c, hipStreamSynchronize(c->s_d2h));
+    bool as16 = false;   // of the frame being issued
+    rc = pipe_run(
+        c, nframes, [&](unsigned i) { return slot_stage(c->slot[i % 3], i); },
+        [&](unsigned i) { return f.floats_up(c->slot[i % 3], rgb[i], &as16); },
+        [&](unsigned i, const PipeStage &) { return f.encode(c->slot[i % 3], as16); },
+        [&](unsigned i) { return f.planes_down(c->slot[i % 3], planes + 3 * i); }, c->h_stats);
     if (rc == LUMAHIP_OK && mean_lum)
         for (unsigned i = 0; i < nframes && rc == LUMAHIP_OK; i++) {
             mean_lum[i] = c->h_stats[3 * (size_t)i] / (float)((int)w * (int)h);
-            if (mean_needs_reference_sum(mean_lum[i], c->h_stats[3 * (size_t)i + 1], w, h)) {  // rare: redo this frame's sum in the reference's order
-                if ((rc = xfer_h2d(c, c->slot[0].d_frame, rgb[i], nfl * sizeof(float), c->stream)))
+            // rare: redo this frame's sum in the reference's order.  The slots have been reused by later frames, so the frame goes
+            // up once more, into slot 0, on the context's stream (the pop of a pushed frame still finds it in its slot)
+            if (mean_needs_reference_sum(mean_lum[i], c->h_stats[3 * (size_t)i + 1], w, h)) {
+                if ((rc = xfer_h2d(c, c->slot[0].d_frame, rgb[i], f.nfl() * sizeof(float), c->stream)))
                     return rc;
                 rc = mean_luminance_reference_impl(c, c->slot[0].d_frame, Elem::F32, w, h, sc, c->q.cs, &mean_lum[i]);
             }
@@ -1089,269 +1173,180 @@ extern "C" int lumahip_encode_frames_host(lumahip_ctx *c, const float *const *rg
     return rc;
 }
 
-// ---- streaming form of the batched encode: frames arrive one at a time ------------------------------------------------------
+extern "C" int lumahip_decode_frames_host(lumahip_ctx *c, const unsigned char *const *planes, const int stride[3],
+                                          unsigned nframes, unsigned w, unsigned h, int profile, float sc,
+                                          float *const *rgb_out)
+{
+    SlotFrame f;
+    if (int rc = batch_begin(c, rgb_out, "output frame", planes, stride, nframes, w, h, profile, sc, f))
+        return rc;
+    return pipe_run(
+        c, nframes, [&](unsigned i) { return slot_stage(c->slot[i % 3], i); },
+        [&](unsigned i) { return f.planes_up(c->slot[i % 3], planes + 3 * i); },
+        [&](unsigned i, const PipeStage &) { return f.decode(c->slot[i % 3]); },
+        [&](unsigned i) { return f.floats_down(c->slot[i % 3], rgb_out[i]); });
+}
+
+// ---- streaming form of the batched calls: frames arrive one at a time ---------------------------------------------------------
 // lumahip_encode_frames_host needs the whole batch in hand.  A caller that gets its frames one by one (the reference's
 // `for (...) encoder.encode(&frame)` loop, lumaenc.cpp:205-243) can still overlap the tail of frame i (kernel, download,
 // copy out of the staging chunks) with the upload of frame i+1 by accepting ONE frame of latency: push(i+1), then pop(i).
-// Same three device slots and three streams as the batched form; at most two frames in flight.
+// Same three device slots and three streams as the batched form; at most two frames in flight.  The decode counterpart
+// (LumaDecoder::decode() in a loop, lumadec.cpp:112-160): the download of frame i (12 B/pixel, the heavy direction here) keeps
+// the copy engine busy while the planes of frame i+1 go up and its kernel runs.
+// The pipeline's loop is carried across the calls: a push is pipe_issue and pipe_fetch of the SAME frame, its download queued
+// behind its kernel; the pop completes that download.
+static const char *const PUSH_NAME[2] = {"lumahip_encode_stream_push", "lumahip_decode_stream_push"};
+static const char *const POP_NAME[2] = {"lumahip_encode_stream_pop", "lumahip_decode_stream_pop"};
+
+// What a push opens with (dir 0: encode, 1: decode; frame: the caller's colour frame): the arguments and the state of the
+// stream checked, the slots large enough (reallocated only when nothing is in flight: same geometry otherwise)
+static int push_begin(lumahip_ctx *c, int dir, const void *frame, const unsigned char *const planes[3], const int stride[3], unsigned w,
+                      unsigned h, int profile, float sc, SlotFrame &f)
+{
+    if (!c || !frame || !planes || !stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (int rc = check_geom(c, w, h, profile, c->q.cs))
+        return rc;
+    const bool in_flight = c->es_head != c->es_tail;
+    if (in_flight && c->es_dir != dir)
+        return fail(c, LUMAHIP_ERR_STATE, "frames pushed with %s are in flight: pop them first", PUSH_NAME[1 - dir]);
+    if (c->es_head - c->es_tail >= 2)
+        return fail(c, LUMAHIP_ERR_STATE, "two frames are in flight already: %s the oldest first", POP_NAME[dir]);
+    if (in_flight && (w != c->es_w || h != c->es_h || profile != c->es_profile || stride[0] != c->es_stride[0] ||
+                      stride[1] != c->es_stride[1] || stride[2] != c->es_stride[2]))
+        return fail(c, LUMAHIP_ERR_STATE, "frame geometry (size, profile or plane strides) changed while a frame is in flight: pop it first");
+    HIPCHK(c, hipSetDevice(c->device));
+    f = SlotFrame{c, {}, stride, w, h, profile, sc};
+    plane_layout(f.L, w, h, profile, stride);
+    if (const int p = bad_plane(f.L, planes, stride); p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
+    return pipe_prepare(c, f.nfl() * sizeof(float), f.L.total, 1);
+}
+
+// The frame with the next sequence number through its slot.  upload(slot, &pinned_in) also says whether the copy engine reads
+// the caller's memory directly; h_stats as in pipe_fetch.
+template <typename Upload, typename Launch, typename Download>
+static int push_frame(const SlotFrame &f, int dir, Upload upload, Launch launch, Download download, float *h_stats)
+{
+    lumahip_ctx *const c = f.c;
+    const unsigned seq = c->es_head;
+    lumahip_ctx::Slot &sl = c->slot[seq % 3];
+    const PipeStage st = slot_stage(sl, seq);
+    c->up_ramp = 0;   // (per push, as per single-frame call)
+    // Until the frame counts as pushed, a failure drops the download chunks queued for it: they carry the tag seq + 1 (0: the
+    // chunks of the plain calls), which is set only while this frame's downloads are queued
+    DnGuard guard{c, false, seq + 1};
+    bool pinned_in = false;
+    int rc = pipe_issue(c, st, [&] { return upload(sl, &pinned_in); }, [&] { return launch(sl); });
+    if (rc)
+        return rc;
+    // the output comes down behind the kernel; pageable destinations are emptied out of the staging chunks by the pop (or
+    // earlier, when the ring comes round)
+    rc = pipe_fetch(c, st, [&] {
+        c->d2h_tag = seq + 1;
+        const int r = download(sl);
+        c->d2h_tag = 0;
+        return r;
+    }, h_stats);
+    if (rc)
+        return rc;
+    // The copy engine read the caller's pinned memory directly: it must be done with it when the push returns.  (The batched
+    // forms rely on the stream syncs of their drain instead.)
+    if (pinned_in)
+        HIPCHK(c, hipEventSynchronize(st.h2d));
+    c->es_w = f.w;
+    c->es_h = f.h;
+    c->es_profile = f.profile;
+    c->es_sc = f.sc;
+    for (int p = 0; p < 3; p++)
+        c->es_stride[p] = f.stride[p];
+    c->es_dir = dir;
+    c->es_head = seq + 1;
+    guard.armed = false;   // the pop completes them
+    return LUMAHIP_OK;
+}
+
+// the oldest pushed frame: its download chunks copied out, its slot's downloads done.  *seq: its sequence number
+static int pop_frame(lumahip_ctx *c, int dir, unsigned *seq)
+{
+    if (c->es_head == c->es_tail || c->es_dir != dir)
+        return fail(c, LUMAHIP_ERR_STATE, dir ? "no decode frame is in flight" : "no encode frame is in flight");
+    HIPCHK(c, hipSetDevice(c->device));
+    *seq = c->es_tail;
+    c->es_tail = *seq + 1;                        // (popped even if something below fails: nothing may stay half-finished)
+    const int rc = d2h_flush(c, seq);
+    HIPCHK(c, hipEventSynchronize(c->slot[*seq % 3].d2h));      // downloads into pinned memory (no chunks to flush), and the statistics
+    return rc;
+}
+
 extern "C" int lumahip_encode_stream_push(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                           unsigned char *const planes[3], const int stride[3])
 {
-    if (!c || !rgb || !planes || !stride)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, c->q.cs);
+    SlotFrame f;
+    int rc = push_begin(c, 0, rgb, planes, stride, w, h, profile, sc, f);
     if (rc)
         return rc;
-    if (c->es_head != c->es_tail && c->es_dir != 0)
-        return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_decode_stream_push are in flight: pop them first");
-    if (c->es_head - c->es_tail >= 2)
-        return fail(c, LUMAHIP_ERR_STATE, "two frames are in flight already: lumahip_encode_stream_pop the oldest first");
-    if (c->es_head != c->es_tail && (w != c->es_w || h != c->es_h || profile != c->es_profile || stride[0] != c->es_stride[0] ||
-                                     stride[1] != c->es_stride[1] || stride[2] != c->es_stride[2]))
-        return fail(c, LUMAHIP_ERR_STATE, "frame geometry (size, profile or plane strides) changed while a frame is in flight: pop it first");
-    HIPCHK(c, hipSetDevice(c->device));
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    if (const int p = bad_plane(L, planes, stride); p >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
-    const size_t nfl = (size_t)3 * w * h;
-    if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, 1)))   // (reallocates only when nothing is in flight: same geometry otherwise)
-        return rc;
-    if (c->es_head == c->es_tail && (rc = dn_chunks_for(c, L.total)))
+    // download chunks sized for these planes, as in lumahip_encode_frames_host; they can only be re-allocated while nothing is in flight
+    if (c->es_head == c->es_tail && (rc = dn_chunks_for(c, f.L.total)))
         return rc;
     if (!c->h_es_stats)
         HIPCHK(c, hipHostMalloc((void **)&c->h_es_stats, 3 * 3 * sizeof(float), hipHostMallocDefault));
-    const unsigned seq = c->es_head;
-    lumahip_ctx::Slot &sl = c->slot[seq % 3];
-    unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-    // the slot's previous occupant (frame seq - 3) was popped long ago; its kernel and downloads are done, but the streams
-    // still have to be told (events of that occupancy)
-    if (seq >= 3) {
-        (void)hipStreamWaitEvent(c->s_h2d, sl.kern, 0);
-        (void)hipStreamWaitEvent(c->s_kern, sl.d2h, 0);
-    }
-    c->up_ramp = 0;
-    DnGuard dn_guard{c, false, seq + 1};   // until the frame counts as pushed, a failure drops the download chunks queued for it
-    bool pinned_in = host_range_is_pinned(rgb, nfl * sizeof(float));
-    bool f16 = in16_try(c, w, false);
-    if (f16) {   // half upload: the CPU converts out of the caller's memory (pinned or not), so it is free again when this returns
-        bool exact = true;
-        if ((rc = xfer_h2d_f16(c, sl.d_frame, rgb, nfl, c->s_h2d, &exact)))
-            return rc;
-        in16_result(c, exact);
-        f16 = exact;
-    }
-    if (f16)
-        pinned_in = false;
-    else if ((rc = xfer_h2d(c, sl.d_frame, rgb, nfl * sizeof(float), c->s_h2d)))
-        return rc;
-    c->slot_in16[seq % 3] = f16;
-    (void)hipEventRecord(sl.h2d, c->s_h2d);
-    (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-    if ((rc = encode_frames_device_impl(c, slot_frame(sl, f16, nfl, w, h), sc, {dp, stride, NO_PFS, profile}, sl.d_stats,
-                                        {c->q.cs, c->s_kern, false, HalfSource::Upload})))
-        return rc;
-    (void)hipEventRecord(sl.kern, c->s_kern);
-    // the planes come down behind the kernel; pageable ones are emptied out of the staging chunks by the pop (or earlier,
-    // when the ring comes round)
-    (void)hipStreamWaitEvent(c->s_d2h, sl.kern, 0);
-    c->d2h_tag = seq + 1;   // (0 = not a pushed frame)
-    for (int p = 0; p < 3 && rc == LUMAHIP_OK; p++)
-        rc = xfer_d2h_2d(c, planes[p], stride[p], dp[p], stride[p], L.row_bytes[p], L.rows[p], c->s_d2h, true);
-    c->d2h_tag = 0;
-    if (rc)
-        return rc;
-    (void)hipMemcpyAsync(c->h_es_stats + 3 * (seq % 3), sl.d_stats, 3 * sizeof(float), hipMemcpyDeviceToHost, c->s_d2h);
-    (void)hipEventRecord(sl.d2h, c->s_d2h);
-    if (pinned_in)
-        HIPCHK(c, hipEventSynchronize(sl.h2d));   // the copy engine read the caller's memory directly: it must be done with it
-    c->es_w = w;
-    c->es_h = h;
-    c->es_profile = profile;
-    c->es_sc = sc;
-    c->es_total = L.total;
-    for (int p = 0; p < 3; p++)
-        c->es_stride[p] = stride[p];
-    c->es_dir = 0;
-    c->es_head = seq + 1;
-    dn_guard.armed = false;   // the pop completes them
-    return LUMAHIP_OK;
+    const unsigned slot = c->es_head % 3;
+    return push_frame(
+        f, 0,
+        [&](lumahip_ctx::Slot &sl, bool *pinned_in) {
+            *pinned_in = host_range_is_pinned(rgb, f.nfl() * sizeof(float));
+            bool as16 = false;
+            if (int r = f.floats_up(sl, rgb, &as16))
+                return r;
+            if (as16)   // half upload: the CPU converted out of the caller's memory (pinned or not), so it is free again already
+                *pinned_in = false;
+            c->slot_in16[slot] = as16;
+            return (int)LUMAHIP_OK;
+        },
+        [&](lumahip_ctx::Slot &sl) { return f.encode(sl, c->slot_in16[slot]); },
+        [&](lumahip_ctx::Slot &sl) { return f.planes_down(sl, planes); }, c->h_es_stats + 3 * slot);
 }
 
 extern "C" int lumahip_encode_stream_pop(lumahip_ctx *c, float *mean_lum)
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    if (c->es_head == c->es_tail || c->es_dir != 0)
-        return fail(c, LUMAHIP_ERR_STATE, "no encode frame is in flight");
-    HIPCHK(c, hipSetDevice(c->device));
-    const unsigned seq = c->es_tail;
-    lumahip_ctx::Slot &sl = c->slot[seq % 3];
-    c->es_tail = seq + 1;                        // (popped even if something below fails: nothing may stay half-finished)
-    int rc = d2h_flush_upto(c, seq);
-    HIPCHK(c, hipEventSynchronize(sl.d2h));      // downloads into pinned planes, and the statistics
-    if (rc)
+    unsigned seq;
+    if (int rc = pop_frame(c, 0, &seq))
         return rc;
     if (mean_lum) {
         const float *stp = c->h_es_stats + 3 * (seq % 3);
         *mean_lum = stp[0] / (float)((int)c->es_w * (int)c->es_h);
         if (mean_needs_reference_sum(*mean_lum, stp[1], c->es_w, c->es_h))   // the slot still holds the frame as it was uploaded
-            return mean_luminance_reference_impl(c, sl.d_frame, c->slot_in16[seq % 3] ? Elem::F16 : Elem::F32, c->es_w, c->es_h, c->es_sc, c->q.cs, mean_lum);
+            return mean_luminance_reference_impl(c, c->slot[seq % 3].d_frame, c->slot_in16[seq % 3] ? Elem::F16 : Elem::F32, c->es_w, c->es_h, c->es_sc, c->q.cs, mean_lum);
     }
     return LUMAHIP_OK;
 }
 
 extern "C" int lumahip_encode_stream_pending(const lumahip_ctx *c) { return (c && c->es_dir == 0) ? (int)(c->es_head - c->es_tail) : 0; }
 
-// The decode counterpart (LumaDecoder::decode() in a loop, lumadec.cpp:112-160): the download of frame i (12 B/pixel, the heavy
-// direction here) keeps the copy engine busy while the planes of frame i+1 go up and its kernel runs.
 extern "C" int lumahip_decode_stream_push(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], unsigned w,
                                           unsigned h, int profile, float sc, float *rgb_out)
 {
-    if (!c || !rgb_out || !planes || !stride)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, c->q.cs);
-    if (rc)
+    SlotFrame f;
+    if (int rc = push_begin(c, 1, rgb_out, planes, stride, w, h, profile, sc, f))
         return rc;
-    if (c->es_head != c->es_tail && c->es_dir != 1)
-        return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_encode_stream_push are in flight: pop them first");
-    if (c->es_head - c->es_tail >= 2)
-        return fail(c, LUMAHIP_ERR_STATE, "two frames are in flight already: lumahip_decode_stream_pop the oldest first");
-    if (c->es_head != c->es_tail && (w != c->es_w || h != c->es_h || profile != c->es_profile || stride[0] != c->es_stride[0] ||
-                                     stride[1] != c->es_stride[1] || stride[2] != c->es_stride[2]))
-        return fail(c, LUMAHIP_ERR_STATE, "frame geometry (size, profile or plane strides) changed while a frame is in flight: pop it first");
-    HIPCHK(c, hipSetDevice(c->device));
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    if (const int p = bad_plane(L, planes, stride); p >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride too small", p);
-    const size_t nfl = (size_t)3 * w * h;
-    if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, 1)))
-        return rc;
-    const unsigned seq = c->es_head;
-    lumahip_ctx::Slot &sl = c->slot[seq % 3];
-    unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-    if (seq >= 3) {
-        (void)hipStreamWaitEvent(c->s_h2d, sl.kern, 0);   // planes of the slot's previous occupant consumed
-        (void)hipStreamWaitEvent(c->s_kern, sl.d2h, 0);   // its floats downloaded
-    }
-    c->up_ramp = 0;
-    DnGuard dn_guard{c, false, seq + 1};   // until the frame counts as pushed, a failure drops the download chunks queued for it
-    bool pinned_in = true;
-    for (int p = 0; p < 3 && rc == LUMAHIP_OK; p++) {
-        pinned_in = pinned_in && host_range_is_pinned(planes[p], (size_t)(L.rows[p] - 1) * stride[p] + L.row_bytes[p]);
-        rc = xfer_h2d_2d(c, dp[p], stride[p], planes[p], stride[p], L.row_bytes[p], L.rows[p], c->s_h2d);
-    }
-    if (rc)
-        return rc;
-    (void)hipEventRecord(sl.h2d, c->s_h2d);
-    (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-    if ((rc = decode_impl(c, {dp, stride, NO_PFS, profile}, sc, packed_frames(sl.d_frame, nfl, 1, w, h), {c->q.cs, c->s_kern})))
-        return rc;
-    (void)hipEventRecord(sl.kern, c->s_kern);
-    (void)hipStreamWaitEvent(c->s_d2h, sl.kern, 0);
-    c->d2h_tag = seq + 1;   // (0 = not a pushed frame)
-    rc = xfer_d2h_deferred(c, rgb_out, sl.d_frame, nfl * sizeof(float), c->s_d2h);
-    c->d2h_tag = 0;
-    if (rc)
-        return rc;
-    (void)hipEventRecord(sl.d2h, c->s_d2h);
-    if (pinned_in)   // (any pinned plane was read by the copy engine directly: it must be done with the caller's memory)
-        HIPCHK(c, hipEventSynchronize(sl.h2d));
-    c->es_w = w;
-    c->es_h = h;
-    c->es_profile = profile;
-    c->es_sc = sc;
-    c->es_total = L.total;
-    for (int p = 0; p < 3; p++)
-        c->es_stride[p] = stride[p];
-    c->es_dir = 1;
-    c->es_head = seq + 1;
-    dn_guard.armed = false;   // the pop completes them
-    return LUMAHIP_OK;
+    return push_frame(
+        f, 1, [&](lumahip_ctx::Slot &sl, bool *pinned_in) { return f.planes_up(sl, planes, pinned_in); },
+        [&](lumahip_ctx::Slot &sl) { return f.decode(sl); }, [&](lumahip_ctx::Slot &sl) { return f.floats_down(sl, rgb_out); }, nullptr);
 }
 
 extern "C" int lumahip_decode_stream_pop(lumahip_ctx *c)
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    if (c->es_head == c->es_tail || c->es_dir != 1)
-        return fail(c, LUMAHIP_ERR_STATE, "no decode frame is in flight");
-    HIPCHK(c, hipSetDevice(c->device));
-    const unsigned seq = c->es_tail;
-    lumahip_ctx::Slot &sl = c->slot[seq % 3];
-    c->es_tail = seq + 1;
-    const int rc = d2h_flush_upto(c, seq);
-    HIPCHK(c, hipEventSynchronize(sl.d2h));      // (a download into pinned memory has no chunks to flush)
-    return rc;
+    unsigned seq;
+    return pop_frame(c, 1, &seq);
 }
 
 extern "C" int lumahip_decode_stream_pending(const lumahip_ctx *c) { return (c && c->es_dir == 1) ? (int)(c->es_head - c->es_tail) : 0; }
-
-extern "C" int lumahip_decode_frames_host(lumahip_ctx *c, const unsigned char *const *planes, const int stride[3],
-                                          unsigned nframes, unsigned w, unsigned h, int profile, float sc,
-                                          float *const *rgb_out)
-{
-    if (!c || !rgb_out || !planes || !stride || nframes == 0)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, c->q.cs);
-    if (rc)
-        return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    for (unsigned i = 0; i < nframes; i++) {
-        if (!rgb_out[i])
-            return fail(c, LUMAHIP_ERR_ARG, "null output frame %u", i);
-        const int p = bad_plane(L, planes + 3 * i, stride);
-        if (p >= 0)
-            return fail(c, LUMAHIP_ERR_ARG, "frame %u plane %d: null or stride too small", i, p);
-    }
-    const size_t nfl = (size_t)3 * w * h;
-    if (c->es_head != c->es_tail)
-        return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_encode_stream_push / lumahip_decode_stream_push are still pending: pop them first");
-    if ((rc = pipe_prepare(c, nfl * sizeof(float), L.total, nframes)))
-        return rc;
-    DnGuard dn_guard{c, false, 0};   // a failing exit drops the download chunks still pointing at the caller's buffers
-    auto fetch = [&](unsigned i) -> int {  // as in lumahip_encode_frames_host: frame i-1 is fetched after frame i is queued
-        lumahip_ctx::Slot &sl = c->slot[i % 3];
-        (void)hipStreamWaitEvent(c->s_d2h, sl.kern, 0);
-        int r = xfer_d2h_deferred(c, rgb_out[i], sl.d_frame, nfl * sizeof(float), c->s_d2h);   // (drained lazily, see stage_dn_ready)
-        if (r)
-            return r;
-        (void)hipEventRecord(sl.d2h, c->s_d2h);
-        return LUMAHIP_OK;
-    };
-    for (unsigned i = 0; i < nframes && rc == LUMAHIP_OK; i++) {
-        lumahip_ctx::Slot &sl = c->slot[i % 3];
-        unsigned char *dp[3] = {sl.d_planes + L.off[0], sl.d_planes + L.off[1], sl.d_planes + L.off[2]};
-        if (i >= 3) {
-            (void)hipStreamWaitEvent(c->s_h2d, sl.kern, 0);   // planes of frame i-3 consumed
-            (void)hipStreamWaitEvent(c->s_kern, sl.d2h, 0);   // floats of frame i-3 copied out
-        }
-        for (int p = 0; p < 3 && rc == LUMAHIP_OK; p++)
-            rc = xfer_h2d_2d(c, dp[p], stride[p], planes[3 * i + p], stride[p], L.row_bytes[p], L.rows[p], c->s_h2d);
-        if (rc)
-            break;
-        (void)hipEventRecord(sl.h2d, c->s_h2d);
-        (void)hipStreamWaitEvent(c->s_kern, sl.h2d, 0);
-        if ((rc = decode_impl(c, {dp, stride, NO_PFS, profile}, sc, packed_frames(sl.d_frame, nfl, 1, w, h), {c->q.cs, c->s_kern})))
-            break;
-        (void)hipEventRecord(sl.kern, c->s_kern);
-        if (i >= 1)
-            rc = fetch(i - 1);
-    }
-    if (rc == LUMAHIP_OK)
-        rc = fetch(nframes - 1);
-    if (int r = d2h_flush(c))   // (also after an error: nothing may stay pending)
-        rc = rc ? rc : r;
-    else
-        dn_guard.armed = false;
-    HIPCHK(c, hipStreamSynchronize(c->s_h2d));
-    HIPCHK(c, hipStreamSynchronize(c->s_kern));
-    HIPCHK(c, hipStreamSynchronize(c->s_d2h));
-    return rc;
-}
 
 extern "C" int lumahip_transform_color_space_host(lumahip_ctx *c, float *frame, unsigned w, unsigned h, int toCs, float sc)
 {

@@ -11,7 +11,8 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
-//   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the 3-slot pipeline   (no kernels)
+//   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
+//                       batched and stream push / pop forms                                               (no kernels)
 //   lumahip_pool.hip    the HBM chunk pool;  lumahip_multi.hip  many GPUs in one process                  (no kernels)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -148,7 +149,8 @@ struct lumahip_ctx {
     float *d_arr = nullptr;
     size_t d_arr_cap = 0;
 
-    // 3-slot pipeline of the batched host entry points (H2D / kernel / D2H on three streams)
+    // the three device slots of the batched host entry points and of the stream push / pop, and the pipeline's three streams
+    // (H2D / kernel / D2H; lumahip_host.hip pipe_run)
     struct Slot {
         float *d_frame = nullptr;
         unsigned char *d_planes = nullptr;
@@ -167,7 +169,7 @@ struct lumahip_ctx {
     int up_ramp = 0;                // staged uploads: how many of the small leading chunks of this call have been used
     size_t h_stats_cap = 0;
 
-    // Pinned staging for pageable caller memory (see xfer_h2d): two chunks per direction, ping-pong
+    // Pinned staging for pageable caller memory (see xfer_h2d): a ring of chunks per direction, N_STAGE up and N_STAGE_DN down
     struct Stage {
         unsigned char *h = nullptr;
         hipEvent_t ev = nullptr;
@@ -188,8 +190,7 @@ struct lumahip_ctx {
     unsigned es_w = 0, es_h = 0;
     int es_profile = 0;
     float es_sc = 1.0f;
-    size_t es_total = 0;           // plane bytes and strides of the frames in flight (a push with other strides is refused)
-    int es_stride[3] = {0, 0, 0};
+    int es_stride[3] = {0, 0, 0};  // plane strides of the frames in flight (a push with other strides is refused)
     float *h_es_stats = nullptr;   // pinned, 3 floats per slot
     unsigned d2h_tag = 0;          // tag given to download chunks queued now
     float *h_small = nullptr;  // pinned scratch for the few-float readbacks
