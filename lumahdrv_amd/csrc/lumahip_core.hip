@@ -83,14 +83,6 @@ extern "C" void lumahip_destroy(lumahip_ctx *c)
         return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_lut);
-    (void)hipFree(c->d_rec);
-    (void)hipFree(c->d_rec_y);
-    (void)hipFree(c->d_ytab);
-    for (auto &t : c->half_tabs)
-        (void)hipFree(t.d);
-    for (auto &t : c->rb_tabs)
-        (void)hipFree(t.d);
     lag_policy_destroy(c->half_pol);
     lag_policy_destroy(c->rb_pol);
     (void)hipFree(c->d_frame);
@@ -134,7 +126,7 @@ extern "C" void lumahip_destroy(lumahip_ctx *c)
     if (c->lane_fork) (void)hipEventDestroy(c->lane_fork);
     if (c->own_stream)
         (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;   // (+ the quantizer's device tables, which free themselves: still on the context's device)
 }
 
 extern "C" const char *lumahip_last_error(const lumahip_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -337,110 +329,75 @@ extern "C" int lumahip_tune(lumahip_ctx *c, const char *key, long v)
 
 // ---------------------------------------------------------------------------------------- quantizer
 
-// The search index of a table is a pure function of the table, and several contexts of one process usually hold the same
-// table (one per GPU in the multi-device layer, encoder + decoder of a transcoder): built once, shared.
+// The host-side builds behind the tables, each a pure function of its key and kept per process (KeyedCache says why)
 namespace {
-struct IndexCacheEntry {
-    std::vector<float> lut;
-    std::shared_ptr<const ThreshIndex> ix;
-};
-std::mutex g_index_mutex;
-std::vector<IndexCacheEntry> g_index_cache;  // a handful of entries, most recent last
+using Lut = std::vector<float>;
 
-std::shared_ptr<const ThreshIndex> cached_thresh_index(const std::vector<float> &lut)
+std::shared_ptr<const ThreshIndex> cached_thresh_index(const Lut &lut)
 {
-    std::lock_guard<std::mutex> lk(g_index_mutex);
-    for (auto &e : g_index_cache)
-        if (e.lut.size() == lut.size() && memcmp(e.lut.data(), lut.data(), lut.size() * sizeof(float)) == 0)
-            return e.ix;
-    IndexCacheEntry e;
-    e.lut = lut;
-    e.ix = std::make_shared<const ThreshIndex>(build_thresh_index(lut.data(), (int)lut.size(), 1 << 19));
-    if (g_index_cache.size() >= 8)
-        g_index_cache.erase(g_index_cache.begin());
-    g_index_cache.push_back(e);
-    return e.ix;
+    static KeyedCache<Lut, std::shared_ptr<const ThreshIndex>> cache;
+    return cache.get(lut, [&] { return std::make_shared<const ThreshIndex>(build_thresh_index(lut.data(), (int)lut.size(), 1 << 19)); });
 }
-struct LinCacheEntry {
-    std::vector<float> lut;
-    std::shared_ptr<const LinIndex> ix;
-};
-std::vector<LinCacheEntry> g_lin_cache;
 
 // value-keyed records (lut_index.hpp LinIndex) of a table whose float-bit records do not fit LDS
-std::shared_ptr<const LinIndex> cached_lin_index(const std::vector<float> &lut)
+std::shared_ptr<const LinIndex> cached_lin_index(const Lut &lut)
 {
-    std::lock_guard<std::mutex> lk(g_index_mutex);
-    for (auto &e : g_lin_cache)
-        if (e.lut.size() == lut.size() && memcmp(e.lut.data(), lut.data(), lut.size() * sizeof(float)) == 0)
-            return e.ix;
-    LinCacheEntry e;
-    e.lut = lut;
-    e.ix = std::make_shared<const LinIndex>(build_lin_index(lut.data(), (int)lut.size(), 1 << 15));
-    if (g_lin_cache.size() >= 8)
-        g_lin_cache.erase(g_lin_cache.begin());
-    g_lin_cache.push_back(e);
-    return e.ix;
+    static KeyedCache<Lut, std::shared_ptr<const LinIndex>> cache;
+    return cache.get(lut, [&] { return std::make_shared<const LinIndex>(build_lin_index(lut.data(), (int)lut.size(), 1 << 15)); });
 }
-struct YIndexCacheEntry {
-    std::vector<float> lut;
-    float Lmax;
-    std::shared_ptr<const ThreshIndex> ix;
-};
-std::vector<YIndexCacheEntry> g_yindex_cache;
 
 // records of the YCbCr composite  t -> search(PQdec(t / 255)), t = 219 y + 16  (host_lut.cpp ycbcr_luma_code_host), per (table, Lmax)
-std::shared_ptr<const ThreshIndex> cached_ycbcr_index(const std::vector<float> &lut, float Lmax)
+ThreshIndex build_ycbcr_index(const float *lut, size_t n, float Lmax)
 {
-    std::lock_guard<std::mutex> lk(g_index_mutex);
-    for (auto &e : g_yindex_cache)
-        if (e.lut.size() == lut.size() && memcmp(&e.Lmax, &Lmax, sizeof(float)) == 0 &&
-            memcmp(e.lut.data(), lut.data(), lut.size() * sizeof(float)) == 0)
-            return e.ix;
-    YIndexCacheEntry e;
-    e.lut = lut;
-    e.Lmax = Lmax;
-    const int maxVal = (int)lut.size() - 1;
-    e.ix = std::make_shared<const ThreshIndex>(build_thresh_index_fn(
-        [&](float t) { return ycbcr_luma_code_host(t, lut.data(), maxVal, Lmax); }, maxVal, 1 << 16, true));
-    if (g_yindex_cache.size() >= 8)
-        g_yindex_cache.erase(g_yindex_cache.begin());
-    g_yindex_cache.push_back(e);
-    return e.ix;
+    const int maxVal = (int)n - 1;
+    return build_thresh_index_fn([&](float t) { return ycbcr_luma_code_host(t, lut, maxVal, Lmax); }, maxVal, 1 << 16, true);
 }
+std::shared_ptr<const ThreshIndex> cached_ycbcr_index(const Lut &lut, float Lmax)
+{
+    static KeyedCache<Lut, std::shared_ptr<const ThreshIndex>> cache;
+    Lut key(lut);   // the table's bits + Lmax's
+    key.push_back(Lmax);
+    return cache.get(key, [&] { return std::make_shared<const ThreshIndex>(build_ycbcr_index(lut.data(), lut.size(), Lmax)); });
+}
+
+// The half-input table of the YCbCr encode kernels: a pure function of (sc, Lmax), 124 KiB, built with the host libm in about a
+// millisecond.  nullptr: this pair has none
+std::shared_ptr<const Lut> cached_half_table(float sc, float Lmax)
+{
+    static KeyedCache<lumahip_ctx::ScLmax, std::shared_ptr<const Lut>> cache;
+    return cache.get({sc, Lmax}, [&]() -> std::shared_ptr<const Lut> {
+        auto t = std::make_shared<Lut>((size_t)lds_half_bytes() / sizeof(float), 0.0f);
+        if (!ycbcr_half_table_host(sc, Lmax, t->data()))
+            return nullptr;
+        return t;
+    });
+}
+
+// search records staged in LDS by a kernel that also stages `powf_b` bytes of powf tables
+bool records_fit_lds(const lumahip_ctx *c, const std::vector<uint32_t> &rec, size_t powf_b)
+{
+    return rec.size() * 4 <= c->lds_table_max && rec.size() * 4 + 16 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP;
+}
+hipError_t upload_records(DevTable<uint32_t> &d, const std::vector<uint32_t> &rec)
+{
+    return d.upload(rec.data(), rec.size(), (rec.size() + 3) & ~(size_t)3, 0u);
+}
+size_t powf_lds_bytes(const QuantDev &q) { return q.cs == CS_YCBCR ? sizeof(PowfTablesWide) : 0; }
 }  // namespace
 
-// device copy of the table + the decode-side decisions: everything a decoder needs
+// device copy of the table + the decode-side decisions: everything a decoder needs.  Nothing of the context changes before
+// both uploads have succeeded; then the tables derived from the old table go with it.
 static int upload_table(lumahip_ctx *c)
 {
     const size_t n = c->h_lut.size();
-    const size_t powf_b = (c->q.cs == CS_YCBCR) ? sizeof(PowfTablesWide) : 0;
+    const size_t powf_b = powf_lds_bytes(c->q);
     // decode side: luminance table (+ Lu'v' chroma table, + the powf tables for YCbCr) staged in LDS
-    c->lut_in_lds = c->bitdepthC <= 12 && (n + 4) * sizeof(float) <= std::max<size_t>(c->lds_table_max, 16 * 1024 + 16) &&
-                    (n + 4) * sizeof(float) + ((size_t)4 << c->bitdepthC) + 64 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP;
+    const bool lut_in_lds = c->bitdepthC <= 12 && (n + 4) * sizeof(float) <= std::max<size_t>(c->lds_table_max, 16 * 1024 + 16) &&
+                            (n + 4) * sizeof(float) + ((size_t)4 << c->bitdepthC) + 64 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP;
     const size_t lut_floats = (n + 1 + 3) & ~(size_t)3;  // NaN padding up to a multiple of 16 bytes
-    std::vector<float> padded(lut_floats, __builtin_nanf(""));
-    memcpy(padded.data(), c->h_lut.data(), n * sizeof(float));
-    (void)hipFree(c->d_lut);
-    (void)hipFree(c->d_rec);
-    (void)hipFree(c->d_rec_y);
-    (void)hipFree(c->d_ytab);
-    c->d_lut = nullptr;
-    c->d_rec = nullptr;
-    c->d_rec_y = nullptr;
-    c->d_ytab = nullptr;
-    for (auto &t : c->rb_tabs)     // (the red / blue tables of the YCbCr decode kernels were built from the old y table)
-        (void)hipFree(t.d);
-    c->rb_tabs.clear();
-    c->rb_unavailable = false;
-    c->tix_y.reset();
-    HIPCHK(c, hipMalloc(&c->d_lut, lut_floats * sizeof(float)));
-    HIPCHK(c, hipMemcpy(c->d_lut, padded.data(), lut_floats * sizeof(float), hipMemcpyHostToDevice));
-    QuantDev &q = c->q;
-    q.lut = c->d_lut;
-    q.rec = nullptr;
-    q.ytab = nullptr;
-    if (c->q.cs == CS_YCBCR && c->use_ycbcr_tables && c->lut_in_lds) {
+    DevTable<float> lut, ytab;
+    HIPCHK(c, lut.upload(c->h_lut.data(), n, lut_floats, __builtin_nanf("")));
+    if (c->q.cs == CS_YCBCR && c->use_ycbcr_tables && lut_in_lds) {
         // YCbCr decode: the first PQ evaluation of a pixel depends on its luminance code only -- one table per stream, built
         // with the host libm (the function the reference calls).  Only for tables of finite non-negative values: the
         // kernels' range analysis of what follows (luma_device.hpp ycbcr_inv) assumes them.
@@ -449,20 +406,29 @@ static int upload_table(lumahip_ctx *c)
             ok = c->h_lut[i] >= 0.0f && c->h_lut[i] <= 3.0e38f;
         const size_t both = 2 * (((n + 4) * sizeof(float) + 15) & ~(size_t)15) + ((size_t)8 << c->bitdepthC) + 64 + powf_b;   // + the two chroma-term tables
         if (ok && both <= LUMAHIP_LDS_PER_WORKGROUP) {
-            std::vector<float> yt(lut_floats, 0.0f);
+            Lut yt(n);
             ycbcr_ytab_host(c->h_lut.data(), n, c->q.Lmax, yt.data());
-            HIPCHK(c, hipMalloc(&c->d_ytab, lut_floats * sizeof(float)));
-            HIPCHK(c, hipMemcpy(c->d_ytab, yt.data(), lut_floats * sizeof(float), hipMemcpyHostToDevice));
-            q.ytab = c->d_ytab;
+            HIPCHK(c, ytab.upload(yt.data(), n, lut_floats, 0.0f));
         }
     }
+    c->lut_in_lds = lut_in_lds;
+    c->d_lut = std::move(lut);
+    c->d_ytab = std::move(ytab);
+    c->d_rec.reset();
+    c->d_rec_y.reset();
+    c->rb_tabs.clear();     // (the red / blue tables of the YCbCr decode kernels were built from the old y table)
+    c->rb_unavailable = false;
+    c->tix.reset();
+    c->index_ready = false;
+    QuantDev &q = c->q;
+    q.lut = c->d_lut.get();
+    q.rec = nullptr;
+    q.ytab = c->d_ytab.get();
     q.lut_len = (int)n;
     q.pad = (int)(lut_floats - n);
     q.maxVal = (int)n - 1;                                   // (int)pow(2,bitdepth)-1, src/luma_quantizer.cpp:180
     q.mode = n <= 4096 ? LUT_LITERAL_LDS : LUT_LITERAL_GLOBAL;
     q.shift = q.kmin = q.nbuckets = 0;
-    c->tix.reset();
-    c->index_ready = false;
     return LUMAHIP_OK;
 }
 
@@ -471,6 +437,7 @@ static int upload_table(lumahip_ctx *c)
 // Every monotone finite table gets threshold records (lut_index.hpp): in LDS when they fit lds_table_max, else in global
 // memory (L2-resident).  Anything else (NaNs, decreasing entries -- a decoder may be handed any attachment-434 table) runs
 // the reference's bisection literally; so does everything after lumahip_tune(ctx, "force_literal", 1) (the tests' hook).
+// The records are prepared beside the context and published at the end: an error return leaves the context as it was.
 int lhost::ensure_search_index(lumahip_ctx *c, hipStream_t s)
 {
     if (c->index_ready)
@@ -478,67 +445,53 @@ int lhost::ensure_search_index(lumahip_ctx *c, hipStream_t s)
     if (!c->have_quant)
         return fail(c, LUMAHIP_ERR_STATE, "quantizer not set (call lumahip_set_quantizer first)");
     HIPCHK(c, hipSetDevice(c->device));
-    QuantDev &q = c->q;
-    if (!c->force_literal) {
-        c->tix = cached_thresh_index(c->h_lut);
-        if (c->tix->ok) {
-            const size_t powf_b = (q.cs == CS_YCBCR) ? sizeof(PowfTablesWide) : 0;
-            const ThreshIndex &ix = *c->tix;
-            std::vector<uint32_t> r((ix.rec.size() + 3) & ~(size_t)3, 0u);
-            memcpy(r.data(), ix.rec.data(), ix.rec.size() * sizeof(uint32_t));
-            HIPCHK(c, hipStreamSynchronize(s));
-            (void)hipFree(c->d_rec);
-            c->d_rec = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_rec, r.size() * sizeof(uint32_t)));
-            HIPCHK(c, hipMemcpy(c->d_rec, r.data(), r.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            q.rec = c->d_rec;
-            q.mode = (ix.rec.size() * 4 <= c->lds_table_max && ix.rec.size() * 4 + 16 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP)
-                         ? LUT_THRESH_LDS
-                         : LUT_THRESH_GLOBAL;
-            q.shift = ix.shift;
-            q.kmin = ix.kmin;
-            q.nbuckets = ix.nbuckets;
+    QuantDev q = c->q, q_y = c->q_y;
+    DevTable<uint32_t> rec, rec_y;
+    std::shared_ptr<const ThreshIndex> tix;
+    const size_t powf_b = powf_lds_bytes(q);
+    if (!c->force_literal && (tix = cached_thresh_index(c->h_lut))->ok) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        // 1. float-bit records, in LDS when they fit
+        const bool in_lds = records_fit_lds(c, tix->rec, powf_b);
+        // 2. when they do not: an evenly spaced table (PTF_LINEAR) fits when its records are keyed by VALUE instead
+        //    (lut_index.hpp LinIndex: LINEAR-12 32 KiB against 229 KiB)
+        std::shared_ptr<const LinIndex> lix;
+        if (!in_lds && c->use_lin_index)
+            lix = cached_lin_index(c->h_lut);
+        if (lix && lix->ok && records_fit_lds(c, lix->rec, powf_b)) {
+            HIPCHK(c, upload_records(rec, lix->rec));
+            q.mode = LUT_LINKEY_LDS;
+            q.shift = 0;
+            q.kmin = 0;
+            q.nbuckets = lix->nbuckets;
+            q.kscale = lix->kscale;
+        } else {
+            HIPCHK(c, upload_records(rec, tix->rec));
+            q.mode = in_lds ? LUT_THRESH_LDS : LUT_THRESH_GLOBAL;
+            q.shift = tix->shift;
+            q.kmin = tix->kmin;
+            q.nbuckets = tix->nbuckets;
             q.kscale = 0.0f;
-            if (q.mode == LUT_THRESH_GLOBAL && c->use_lin_index) {
-                // float-bit records too large for LDS: an evenly spaced table (PTF_LINEAR) fits when its records are keyed by
-                // VALUE instead (lut_index.hpp LinIndex: LINEAR-12 32 KiB against 229 KiB)
-                c->lix = cached_lin_index(c->h_lut);
-                const LinIndex &lx = *c->lix;
-                if (lx.ok && lx.rec.size() * 4 <= c->lds_table_max && lx.rec.size() * 4 + 16 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP) {
-                    std::vector<uint32_t> rl((lx.rec.size() + 3) & ~(size_t)3, 0u);
-                    memcpy(rl.data(), lx.rec.data(), lx.rec.size() * sizeof(uint32_t));
-                    (void)hipFree(c->d_rec);
-                    c->d_rec = nullptr;
-                    HIPCHK(c, hipMalloc(&c->d_rec, rl.size() * sizeof(uint32_t)));
-                    HIPCHK(c, hipMemcpy(c->d_rec, rl.data(), rl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                    q.rec = c->d_rec;
-                    q.mode = LUT_LINKEY_LDS;
-                    q.shift = 0;
-                    q.kmin = 0;
-                    q.nbuckets = lx.nbuckets;
-                    q.kscale = lx.kscale;
-                }
-            }
-            // YCbCr encode: the luminance code straight from the luma y (composite records; luma_device.hpp ycbcr_fwd<., YCODE>)
-            if (q.cs == CS_YCBCR && c->use_ycbcr_tables && q.mode == LUT_THRESH_LDS) {
-                c->tix_y = cached_ycbcr_index(c->h_lut, q.Lmax);
-                const ThreshIndex &iy = *c->tix_y;
-                if (iy.ok && iy.rec.size() * 4 <= c->lds_table_max && iy.rec.size() * 4 + 16 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP) {
-                    std::vector<uint32_t> ry((iy.rec.size() + 3) & ~(size_t)3, 0u);
-                    memcpy(ry.data(), iy.rec.data(), iy.rec.size() * sizeof(uint32_t));
-                    (void)hipFree(c->d_rec_y);
-                    c->d_rec_y = nullptr;
-                    HIPCHK(c, hipMalloc(&c->d_rec_y, ry.size() * sizeof(uint32_t)));
-                    HIPCHK(c, hipMemcpy(c->d_rec_y, ry.data(), ry.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-                    c->q_y = q;
-                    c->q_y.rec = c->d_rec_y;
-                    c->q_y.shift = iy.shift;
-                    c->q_y.kmin = iy.kmin;
-                    c->q_y.nbuckets = iy.nbuckets;
-                }
+        }
+        q.rec = rec.get();
+        // 3. YCbCr encode: the luminance code straight from the luma y (composite records; luma_device.hpp ycbcr_fwd<., YCODE>)
+        if (q.cs == CS_YCBCR && c->use_ycbcr_tables && q.mode == LUT_THRESH_LDS) {
+            const auto tix_y = cached_ycbcr_index(c->h_lut, q.Lmax);
+            if (tix_y->ok && records_fit_lds(c, tix_y->rec, powf_b)) {
+                HIPCHK(c, upload_records(rec_y, tix_y->rec));
+                q_y = q;
+                q_y.rec = rec_y.get();
+                q_y.shift = tix_y->shift;
+                q_y.kmin = tix_y->kmin;
+                q_y.nbuckets = tix_y->nbuckets;
             }
         }
     }
+    c->q = q;
+    c->q_y = q_y;
+    c->d_rec = std::move(rec);
+    c->d_rec_y = std::move(rec_y);
+    c->tix = tix;
     c->index_ready = true;
     return LUMAHIP_OK;
 }
@@ -586,17 +539,11 @@ extern "C" int lumahip_set_quantizer(lumahip_ctx *c, int ptf, unsigned bitdepth,
     return LUMAHIP_OK;
 }
 
-// host-only view of the threshold records (no GPU, no context): info = {ok, mant_bits, shift, kmin, nbuckets}
-extern "C" int lumahip_thresh_index_host(const float *lut, size_t n, int info[5], uint32_t *rec_out, size_t rec_cap)
+// The host-only views of the records (no GPU, no context), for the CPU tests.  The records of a usable index go to rec_out,
+// when the caller gave one, if it holds them
+template <typename Index>
+static int records_out(const Index &ix, uint32_t *rec_out, size_t rec_cap)
 {
-    if (!lut || !info || n < 2 || n > 65536)
-        return LUMAHIP_ERR_ARG;
-    const ThreshIndex ix = build_thresh_index(lut, (int)n, 1 << 19);
-    info[0] = ix.ok ? 1 : 0;
-    info[1] = ix.mant_bits;
-    info[2] = ix.shift;
-    info[3] = ix.kmin;
-    info[4] = ix.nbuckets;
     if (rec_out && ix.ok) {
         if (rec_cap < ix.rec.size())
             return LUMAHIP_ERR_ARG;
@@ -604,8 +551,25 @@ extern "C" int lumahip_thresh_index_host(const float *lut, size_t n, int info[5]
     }
     return LUMAHIP_OK;
 }
+// info = {ok, mant_bits, shift, kmin, nbuckets}
+static int thresh_index_view(const ThreshIndex &ix, int info[5], uint32_t *rec_out, size_t rec_cap)
+{
+    info[0] = ix.ok ? 1 : 0;
+    info[1] = ix.mant_bits;
+    info[2] = ix.shift;
+    info[3] = ix.kmin;
+    info[4] = ix.nbuckets;
+    return records_out(ix, rec_out, rec_cap);
+}
 
-// host-only view of the value-keyed records (no GPU, no context): info = {ok, nbuckets, bits of kscale}; rec_out: 2 words per bucket
+extern "C" int lumahip_thresh_index_host(const float *lut, size_t n, int info[5], uint32_t *rec_out, size_t rec_cap)
+{
+    if (!lut || !info || n < 2 || n > 65536)
+        return LUMAHIP_ERR_ARG;
+    return thresh_index_view(build_thresh_index(lut, (int)n, 1 << 19), info, rec_out, rec_cap);
+}
+
+// the value-keyed records: info = {ok, nbuckets, bits of kscale}; rec_out: 2 words per bucket
 extern "C" int lumahip_lin_index_host(const float *lut, size_t n, int info[3], uint32_t *rec_out, size_t rec_cap)
 {
     if (!lut || !info || n < 2 || n > 65536)
@@ -614,12 +578,7 @@ extern "C" int lumahip_lin_index_host(const float *lut, size_t n, int info[3], u
     info[0] = ix.ok ? 1 : 0;
     info[1] = ix.nbuckets;
     memcpy(&info[2], &ix.kscale, sizeof(float));
-    if (rec_out && ix.ok) {
-        if (rec_cap < ix.rec.size())
-            return LUMAHIP_ERR_ARG;
-        memcpy(rec_out, ix.rec.data(), ix.rec.size() * sizeof(uint32_t));
-    }
-    return LUMAHIP_OK;
+    return records_out(ix, rec_out, rec_cap);
 }
 
 extern "C" int lumahip_quantizer_info(const lumahip_ctx *c, int info[5])
@@ -648,19 +607,7 @@ extern "C" int lumahip_ycbcr_luma_index_host(const float *lut, size_t n, float L
 {
     if (!lut || !info || n < 2 || n > 65536)
         return LUMAHIP_ERR_ARG;
-    const int maxVal = (int)n - 1;
-    const ThreshIndex ix = build_thresh_index_fn([&](float t) { return ycbcr_luma_code_host(t, lut, maxVal, Lmax); }, maxVal, 1 << 16, true);
-    info[0] = ix.ok ? 1 : 0;
-    info[1] = ix.mant_bits;
-    info[2] = ix.shift;
-    info[3] = ix.kmin;
-    info[4] = ix.nbuckets;
-    if (rec_out && ix.ok) {
-        if (rec_cap < ix.rec.size())
-            return LUMAHIP_ERR_ARG;
-        memcpy(rec_out, ix.rec.data(), ix.rec.size() * sizeof(uint32_t));
-    }
-    return LUMAHIP_OK;
+    return thresh_index_view(build_ycbcr_index(lut, n, Lmax), info, rec_out, rec_cap);
 }
 
 extern "C" int lumahip_ycbcr_ytab_host(const float *lut, size_t n, float Lmax, float *out)
@@ -671,73 +618,28 @@ extern "C" int lumahip_ycbcr_ytab_host(const float *lut, size_t n, float Lmax, f
     return LUMAHIP_OK;
 }
 
-// The half-input table of the YCbCr encode kernels for this call's preScaling: a pure function of (sc, Lmax), 124 KiB, built
-// with the host libm in about a millisecond and kept -- per process on the host, per context on the device -- because a stream
-// encodes every frame with the same pair.  A context holds up to four device copies; launches that read an older copy may
-// still be queued on any stream or lane when a fifth pair turns up, so making room waits for the device first.
-namespace {
-struct HalfHostEntry {
-    float sc, Lmax;
-    bool ok;
-    std::shared_ptr<const std::vector<float>> tab;
-};
-std::mutex g_half_mutex;
-std::vector<HalfHostEntry> g_half_cache;
-
-HalfHostEntry cached_half_table(float sc, float Lmax)
-{
-    std::lock_guard<std::mutex> lk(g_half_mutex);
-    for (auto &e : g_half_cache)
-        if (memcmp(&e.sc, &sc, 4) == 0 && memcmp(&e.Lmax, &Lmax, 4) == 0)
-            return e;
-    HalfHostEntry e;
-    e.sc = sc;
-    e.Lmax = Lmax;
-    auto t = std::make_shared<std::vector<float>>((size_t)lds_half_bytes() / sizeof(float), 0.0f);
-    e.ok = ycbcr_half_table_host(sc, Lmax, t->data());
-    if (e.ok)
-        e.tab = t;
-    if (g_half_cache.size() >= 8)
-        g_half_cache.erase(g_half_cache.begin());
-    g_half_cache.push_back(e);
-    return e;
-}
-}  // namespace
-
+// The half-input table of the YCbCr encode kernels for this call's preScaling, kept -- per process on the host, per context on
+// the device (up to four copies) -- because a stream encodes every frame with the same pair
 int half_table_for(lumahip_ctx *c, float sc, const float **tab)
 {
     *tab = nullptr;
-    const float Lmax = c->q.Lmax;
-    for (auto &t : c->half_tabs)
-        if (memcmp(&t.sc, &sc, 4) == 0 && memcmp(&t.Lmax, &Lmax, 4) == 0) {
-            t.last_use = ++c->half_clock;
-            *tab = t.d;
-            return LUMAHIP_OK;
-        }
-    const HalfHostEntry h = cached_half_table(sc, Lmax);
-    if (c->half_tabs.size() >= 4) {
-        HIPCHK(c, hipDeviceSynchronize());
-        size_t old = 0;
-        for (size_t i = 1; i < c->half_tabs.size(); i++)
-            if (c->half_tabs[i].last_use < c->half_tabs[old].last_use)
-                old = i;
-        (void)hipFree(c->half_tabs[old].d);
-        c->half_tabs.erase(c->half_tabs.begin() + (long)old);
+    const lumahip_ctx::ScLmax key{sc, c->q.Lmax};
+    if (const DevTable<float> *t = c->half_tabs.find(key)) {
+        *tab = t->get();
+        return LUMAHIP_OK;
     }
-    lumahip_ctx::HalfTab t;
-    t.sc = sc;
-    t.Lmax = Lmax;
-    t.last_use = ++c->half_clock;
-    if (h.ok) {
-        HIPCHK(c, hipMalloc(&t.d, (size_t)lds_half_bytes()));
+    const auto h = cached_half_table(key.sc, key.Lmax);
+    HIPCHK(c, c->half_tabs.make_room());
+    DevTable<float> d;   // stays empty for a pair without a table
+    if (h) {
+        HIPCHK(c, d.alloc(h->size()));
         // a blocking copy into memory nothing else knows yet: done when it returns, whatever stream the launch goes to
-        if (hipMemcpy(t.d, h.tab->data(), (size_t)lds_half_bytes(), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(t.d);
+        if (hipMemcpy(d.get(), h->data(), h->size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             return fail(c, LUMAHIP_ERR_HIP, "upload of the half-input table failed");
-        }
     }
-    c->half_tabs.push_back(t);
-    *tab = t.d;
+    const float *p = d.get();
+    HIPCHK(c, c->half_tabs.insert(key, std::move(d)));
+    *tab = p;
     return LUMAHIP_OK;
 }
 
@@ -766,9 +668,7 @@ extern "C" int lumahip_half_table_info(lumahip_ctx *c, float sc, int info[6])
         info[0] = t != nullptr;
         info[1] = t ? (int)lds_bytes(c, true, CS_YCBCR, true, true) : 0;
     }
-    info[2] = 0;
-    for (const auto &t : c->half_tabs)
-        info[2] += t.d != nullptr;
+    info[2] = c->half_tabs.resident();
     info[4] = (int)std::min<unsigned long>(c->half_launches, 0x7fffffffUL);
     info[5] = (int)std::min<unsigned long>(c->half_pol.backoff_launches, 0x7fffffffUL);
     return LUMAHIP_OK;
@@ -976,7 +876,7 @@ int lag_policy_launched(lumahip_ctx *c, LagPolicy &p, hipStream_t s)
 }
 
 // dynamic LDS of the encode-side kernels (search tables) and of the decode-side kernels (the table itself)
-bool ycbcr_composite_ready(const lumahip_ctx *c) { return c->q.cs == CS_YCBCR && c->d_rec_y != nullptr && c->index_ready; }
+bool ycbcr_composite_ready(const lumahip_ctx *c) { return c->q.cs == CS_YCBCR && c->d_rec_y && c->index_ready; }
 
 int check_geom(lumahip_ctx *c, unsigned w, unsigned h, int profile, int cs_eff)
 {

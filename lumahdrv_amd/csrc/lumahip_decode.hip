@@ -104,9 +104,9 @@ static bool planes_are_separate_buffers(const DstFrames &f)
 
 // The device red / blue tables of this call's preScaling (nullptr: not for this stream).  Built by one launch of k_build_rb the
 // first time a preScaling is seen (two tables of 2^(bitdepth + bitdepthC) floats: 8 MiB for the HDR10 recipe, ~20 us), kept per
-// context -- up to two preScalings; launches that read an older copy may still be queued anywhere, so making room waits for the
-// device first.  What a gather costs is the L1 hit rate of the lines a picture touches, not the size of the table: PQ-12 with
-// 12-bit colour (2 x 64 MiB) is read as profitably as the HDR10 recipe's 8 MiB; beyond RB_MAX_BYTES the tables are not built.
+// context -- up to two preScalings (lumahip_ctx::rb_tabs).  What a gather costs is the L1 hit rate of the lines a picture
+// touches, not the size of the table: PQ-12 with 12-bit colour (2 x 64 MiB) is read as profitably as the HDR10 recipe's 8 MiB;
+// beyond RB_MAX_BYTES the tables are not built.
 static constexpr size_t RB_MAX_BYTES = (size_t)256 << 20;
 
 int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab)
@@ -118,22 +118,13 @@ int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab)
     // clears `rb_unavailable` with the tables).
     if (c->rb_mode == 0 || c->rb_unavailable || !c->q.ytab || 2 * n * nc * sizeof(float) > RB_MAX_BYTES || !(sc == sc))
         return LUMAHIP_OK;
-    for (auto &t : c->rb_tabs)
-        if (memcmp(&t.sc, &sc, 4) == 0) {
-            t.last_use = ++c->rb_clock;
-            *tab = t.d;
-            return LUMAHIP_OK;
-        }
-    if (c->rb_tabs.size() >= 2) {
-        HIPCHK(c, hipDeviceSynchronize());
-        const size_t old = c->rb_tabs[0].last_use < c->rb_tabs[1].last_use ? 0 : 1;
-        (void)hipFree(c->rb_tabs[old].d);
-        c->rb_tabs.erase(c->rb_tabs.begin() + (long)old);
+    if (const DevTable<float> *t = c->rb_tabs.find(sc)) {
+        *tab = t->get();
+        return LUMAHIP_OK;
     }
-    lumahip_ctx::RbTab t;
-    t.sc = sc;
-    t.last_use = ++c->rb_clock;
-    if (c->test_fail_rb_alloc || hipMalloc(&t.d, 2 * n * nc * sizeof(float)) != hipSuccess) {
+    HIPCHK(c, c->rb_tabs.make_room());   // (up to 256 MiB each: the old copy goes before the new one is asked for)
+    DevTable<float> d;
+    if (c->test_fail_rb_alloc || d.alloc(2 * n * nc) != hipSuccess) {
         c->test_fail_rb_alloc = false;
         (void)hipGetLastError();
         c->rb_unavailable = true;
@@ -141,7 +132,7 @@ int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab)
     }
     RbArgs a{};
     a.ytab = c->q.ytab;
-    a.out = t.d;
+    a.out = d.get();
     a.n = (int)n;
     a.nc = (int)nc;
     a.maxC = c->q.maxC;
@@ -151,12 +142,12 @@ int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab)
     // done when this returns, whatever stream or lane the decode launch goes to
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(t.d);
         c->rb_unavailable = true;
         return LUMAHIP_OK;
     }
-    c->rb_tabs.push_back(t);
-    *tab = t.d;
+    const float *p = d.get();
+    HIPCHK(c, c->rb_tabs.insert(sc, std::move(d)));
+    *tab = p;
     return LUMAHIP_OK;
 }
 
@@ -235,7 +226,7 @@ int decode_impl(lumahip_ctx *c, const SrcPlanes &p, float sc, const DstFrames &f
         a.q.ytab = nullptr;
     size_t lds = lds_bytes(c, false, cs_eff);
     if (cs_eff == CS_YCBCR && c->q.ytab && !yt)
-        lds -= ((size_t)(c->q.lut_len + c->q.pad) * 4 + 15) & ~(size_t)15;   // (display variant: no y table)
+        lds -= lut_lds_bytes(c->q);   // (display variant: no y table)
     const int threads = block_threads_for(c, lds, false, cs_eff == CS_YCBCR);
     if (!make_geom(a.g, w, h, vw, threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");

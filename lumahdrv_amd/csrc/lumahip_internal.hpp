@@ -1,12 +1,15 @@
 // lumahip_internal.hpp -- what the translation units behind include/lumahip.h share: the context, error helpers,
 // launch-geometry rules and the device-side implementations the host entry points call.  Not installed, not part of the ABI.
 //
-//   lumahip_core.hip    context life cycle, quantizer upload, layout checks, memory helpers               (no kernels)
+//   lumahip_core.hip    context life cycle, the per-stream tables of a quantizer (which, when, how large), layout checks,
+//                       memory helpers                                                                    (no kernels)
+//   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which k_encode / k_decode instantiation a launch takes: pick_enc<IN16> / pick_dec<OUT16>, included by
 //                       the four kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
-//   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels
+//   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
+//                       tables next to the kernel that builds them
 //   lumahip_encode_f16.hip / lumahip_decode_f16.hip  pick_enc<true> / pick_dec<true> (the binary16-frame kernels, exported as
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
@@ -35,6 +38,7 @@
 #include "host_lut.hpp"
 #include "lut_index.hpp"
 #include "numa_host.hpp"
+#include "lumahip_tables.hpp"
 
 // Largest search table (encode: threshold records, decode: the luminance table) a workgroup stages in LDS; beyond it
 // the table is read from global memory (L2-resident).  gfx950 has 160 KiB of LDS per CU; tables beyond 53 KiB run as one
@@ -94,36 +98,28 @@ struct lumahip_ctx {
     int ptf = 0;
     unsigned bitdepth = 0, bitdepthC = 0;
     lh::QuantDev q{};
-    std::shared_ptr<const lh::ThreshIndex> tix;  // encode-side search index, built on first use (ensure_search_index)
-    std::shared_ptr<const lh::LinIndex> lix;     // value-keyed records, when the float-bit ones miss LDS and these fit (PTF_LINEAR)
-    bool use_lin_index = true;                   // lumahip_tune("lin_index", 0): never (A/B, tests)
+    // The device tables of the quantizer (lumahip_core.hip upload_table / ensure_search_index publish them in q and q_y): the
+    // luminance table and, YCbCr only, the per-stream y table of the decode kernels (host_lut.cpp); the encode-side search
+    // records (float-bit or value-keyed, built on first use) and, YCbCr only, those of the composite luma -> code function
+    lhost::DevTable<float> d_lut, d_ytab;
+    lhost::DevTable<uint32_t> d_rec, d_rec_y;
+    std::shared_ptr<const lh::ThreshIndex> tix;  // what d_rec was uploaded from, unless the records are value-keyed (lumahip_quantizer_info)
+    bool use_lin_index = true;                   // lumahip_tune("lin_index", 0): no value-keyed records (A/B, tests)
     bool index_ready = false;
-    // YCbCr only: records of the composite luma -> code function (encode), the per-stream y table (decode); host_lut.cpp
-    std::shared_ptr<const lh::ThreshIndex> tix_y;
-    uint32_t *d_rec_y = nullptr;
     lh::QuantDev q_y{};           // q with the composite records in place of the luminance records
-    float *d_ytab = nullptr;
     bool use_ycbcr_tables = true; // lumahip_tune("ycbcr_tables", 0): per-pixel PQ evaluation as in round 2 (A/B, tests)
     // YCbCr encode, binary16 inputs: device copies of the half-input table (luma_device.hpp half_lookup), one per (sc, Lmax) seen;
-    // d == nullptr records "not usable for this pair" (host_lut.cpp ycbcr_half_table_host).  lumahip_core.hip half_table_for
-    struct HalfTab {
-        float sc = 0.0f, Lmax = 0.0f;
-        float *d = nullptr;
-        unsigned long last_use = 0;
+    // an empty entry records "not usable for this pair" (host_lut.cpp ycbcr_half_table_host).  lumahip_core.hip half_table_for
+    struct ScLmax {
+        float sc, Lmax;
     };
-    std::vector<HalfTab> half_tabs;
-    unsigned long half_clock = 0;
+    lhost::DevTableLru<ScLmax, float, 4> half_tabs;
     int half_mode = 1;            // lumahip_tune("half_table"): 0 = never, 1 = while the stream looks like binary16 data (half_pol: LagPolicy), 2 = always
     LagPolicy half_pol{true, 1024};     // which kernel an eligible YCbCr encode launch takes (half_mode 1): a report = "these are not halves"
     unsigned long half_launches = 0;
     // YCbCr decode: device copies of the per-stream red / blue tables (lumahip_decode.hip rb_table_for), one per preScaling seen
-    struct RbTab {
-        float sc = 0.0f;
-        float *d = nullptr;
-        unsigned long last_use = 0;
-    };
-    std::vector<RbTab> rb_tabs;
-    unsigned long rb_clock = 0, rb_launches = 0;
+    lhost::DevTableLru<float, float, 2> rb_tabs;
+    unsigned long rb_launches = 0;
     bool test_fail_rb_alloc = false;
     bool rb_unavailable = false;  // allocating or building the tables failed for this stream: plain kernels, no retry per launch
     LagPolicy rb_pol{false, 64};      // which kernel an eligible YCbCr decode launch takes (rb_mode 1): NO report = "no wave found its codes local"
@@ -133,8 +129,6 @@ struct lumahip_ctx {
     int rb_near_y = 64, rb_near_c = 24;    // lumahip_tune("rb_near_y" / "rb_near_c"): the closeness bounds of mode 1 (luma_kernels.hpp rb_wave_local)
     bool force_literal = false;   // lumahip_tune("force_literal"): the reference's bisection instead of the records
     std::vector<float> h_lut;     // host copy of the table handed to lumahip_set_quantizer
-    float *d_lut = nullptr;
-    uint32_t *d_rec = nullptr;
     bool lut_in_lds = true;  // decode side: tables up to 12 bits are staged in LDS
     float minLum = 0.0f;
 
@@ -364,6 +358,7 @@ struct DecodeLaunch {
 };
 
 // ---- lumahip_launch.hip
+static inline size_t lut_lds_bytes(const QuantDev &q) { return ((size_t)(q.lut_len + q.pad) * 4 + 15) & ~(size_t)15; }   // the luminance table, or the y table, in LDS
 size_t lds_bytes(const lumahip_ctx *c, bool encode_side, int cs_eff, bool ycode = false, bool half = false);   // ycode: the composite-record encode kernels; half: + the half-input table
 int block_threads_for(const lumahip_ctx *c, size_t lds, bool few_waves = false, bool valu_bound = false);
 int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers = 0, int ycbcr = 0);   // few_writers: 0 no, 1 yes, 2 yes with the colour planes in separate buffers; ycbcr: 0 no, 1 yes, 2 the half-input encode kernels

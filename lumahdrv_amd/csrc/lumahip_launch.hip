@@ -12,7 +12,7 @@ size_t lds_bytes(const lumahip_ctx *c, bool encode_side, int cs_eff, bool ycode,
 {
     const QuantDev &q = c->q;
     size_t b = 0;
-    const size_t lut_b = ((size_t)(q.lut_len + q.pad) * 4 + 15) & ~(size_t)15;
+    const size_t lut_b = lut_lds_bytes(q);
     if (encode_side && ycode) {
         b += ((size_t)c->q_y.nbuckets * 4 + 15) & ~(size_t)15;
     } else if (encode_side) {
