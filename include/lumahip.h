@@ -39,7 +39,8 @@ extern "C" {
  * signature, so a program linked against version 2 runs against this library.
  *   5, later additions that change no existing symbol (detect them with dlsym): the binary16 frame calls
  *     lumahip_encode_frames_device_f16 / _planar_f16, lumahip_decode_frames_device_f16 / _planar_f16,
- *     lumahip_encode_frame_host_f16, lumahip_decode_frame_host_f16 and the probe lumahip_f16_narrow_probe_device.
+ *     lumahip_encode_frame_host_f16, lumahip_decode_frame_host_f16 and the probe lumahip_f16_narrow_probe_device; the transcode
+ *     calls lumahip_set_source_quantizer, lumahip_transcode_frames_device, lumahip_transcode_frame_host.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -117,6 +118,13 @@ int lumahip_tune(lumahip_ctx *ctx, const char *key, long value);
  * process-wide cache keyed by the table) by the first encode-side call, so a context that only decodes never builds it. */
 int lumahip_set_quantizer(lumahip_ctx *ctx, int ptf, unsigned bitdepth, int colorspace, unsigned bitdepthC,
                           float maxLum, float minLum, const float *lut_host, size_t lut_len);
+
+/* The SOURCE quantizer of the transcode calls (lumahip_transcode_frames_device below): the description of the stream whose code
+ * planes are read, with the arguments and argument checks of lumahip_set_quantizer.  It is held beside the context's quantizer
+ * and is independent of it: setting one never disturbs the other, and no other call reads it.  It owns decode-side tables only
+ * (the luminance table; for YCbCr the per-stream y table), built when it is set. */
+int lumahip_set_source_quantizer(lumahip_ctx *ctx, int ptf, unsigned bitdepth, int colorspace, unsigned bitdepthC,
+                                 float maxLum, float minLum, const float *lut_host, size_t lut_len);
 
 /* Host-only helper: builds the 2^bitdepth-entry table exactly as LumaQuantizer::setQuantizer does
  * (src/luma_quantizer.cpp:114-169,172-212) -- host libm powf / log10f for PQ / LOG, Lmax*i/maxVal for
@@ -329,6 +337,40 @@ int lumahip_decode_frame_host_f16(lumahip_ctx *ctx, const unsigned char *const p
 int lumahip_decode_frames_device_rotating(lumahip_ctx *ctx, const unsigned char *const planes_dev[3], const int stride[3],
                                           const size_t plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h, int profile,
                                           float preScaling, float *const bases_dev[3], size_t frame_stride);
+
+/* Transcode: the code planes of one stream into the code planes of another, in ONE launch and without a float frame between
+ * them.  It replaces the pair
+ *     LumaDecoder::getVpxChannels + transformColorSpace(frame, false, src_sc)   (src/luma_decoder.cpp:205-240, src/luma_quantizer.cpp:374-479)
+ *     transformColorSpace(frame, true, dst_sc) + LumaEncoder::setVpxChannel     (src/luma_quantizer.cpp:267-373, src/luma_encoder.cpp:260-317)
+ * i.e. `lumadec | lumaenc`, or lumahip_decode_frames_device followed by lumahip_encode_frames_device through a float buffer of
+ * 12 bytes per pixel -- and writes the planes that pair writes, bit for bit (the source's `/ src_sc` and the target's `* dst_sc`
+ * are both carried out).  The source planes are read under the SOURCE quantizer (lumahip_set_source_quantizer) in src_profile,
+ * the destination planes are written under the context's quantizer (lumahip_set_quantizer) in dst_profile; plane p of frame f at
+ * planes_dev[p] + f*plane_frame_stride[p] bytes on either side.  The two profiles are independent (4:4:4 -> 4:2:0 averages the
+ * per-pixel chroma as the encoder does; 8- and 16-bit samples on either side).  stats_dev (nullable) as in
+ * lumahip_encode_frames_device: {sum, min, max} of the target's transformed channel 0 per frame.  Asynchronous on the context's
+ * stream, never waits on the host; takes part in unordered sections like the four _device encode / decode calls; the launch
+ * shape honours lumahip_tune "grid_enc", "lane_grid_enc", "block" and "blocks_per_cu".
+ * Errors, all before anything is launched: LUMAHIP_ERR_STATE unless both quantizers are set; LUMAHIP_ERR_ARG for odd sizes, bad
+ * strides, or when a source plane's extent over the batch overlaps a destination plane's; LUMAHIP_ERR_UNSUPPORTED outside the
+ * supported set, which is:
+ *   - colour spaces LUMAHIP_CS_LUV and LUMAHIP_CS_YCBCR on either side (RGB and XYZ: not provided);
+ *   - source: luminance bit depth <= 12, colour bit depth <= 12 (its tables are staged in LDS); a YCbCr source needs its y table
+ *     (a table of finite non-negative values, lumahip_tune "ycbcr_tables" not 0 when it was set);
+ *   - target: Lu'v' with its search records in LDS (lumahip_quantizer_info search mode 3 or 7: e.g. PQ up to 13 bits, PTF_LINEAR
+ *     12), YCbCr with the composite luma -> code records in LDS (the HDR10 recipe has them; lumahip_tune "ycbcr_tables" not 0);
+ *     never after lumahip_tune "force_literal";
+ *   - the tables of both sides together within the 160 KiB of LDS a workgroup can have.
+ * The host form uploads the source planes, runs one launch and downloads the destination planes, synchronously; mean_lum
+ * (nullable) follows the rules of lumahip_encode_frame_host, the reference's sequential sum being taken over channel 0 of the
+ * decoded and transformed frame in exactly the cases where that call takes it. */
+int lumahip_transcode_frames_device(lumahip_ctx *ctx, const unsigned char *const src_planes_dev[3], const int src_stride[3],
+                                    const size_t src_plane_frame_stride[3], int src_profile, float src_sc, unsigned nframes,
+                                    unsigned w, unsigned h, unsigned char *const dst_planes_dev[3], const int dst_stride[3],
+                                    const size_t dst_plane_frame_stride[3], int dst_profile, float dst_sc, float *stats_dev);
+int lumahip_transcode_frame_host(lumahip_ctx *ctx, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile,
+                                 float src_sc, unsigned w, unsigned h, unsigned char *const dst_planes[3], const int dst_stride[3],
+                                 int dst_profile, float dst_sc, float *mean_lum);
 
 /* Unordered section.  Frames -- and therefore batches of frames -- are independent in this path (the quantizer is
  * read-only state, src/luma_quantizer.cpp:215-264,267-482 keep nothing between frames), so a caller with several batches to

@@ -37,6 +37,7 @@ SYMBOLS = [
     "lumahip_multi_encode_frames_device", "lumahip_multi_decode_frames_device", "lumahip_multi_sync",
     "lumahip_encode_frames_device_f16", "lumahip_encode_frames_device_planar_f16", "lumahip_decode_frames_device_f16",
     "lumahip_decode_frames_device_planar_f16", "lumahip_encode_frame_host_f16", "lumahip_decode_frame_host_f16", "lumahip_f16_narrow_probe_device",
+    "lumahip_set_source_quantizer", "lumahip_transcode_frames_device", "lumahip_transcode_frame_host",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -73,7 +74,7 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 # device code + launch geometry + compiler flags (NOT the host plumbing: lumahip_core / _host / _pool / _multi, lumahip_internal.hpp)
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
-                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp")
+                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip")
 
 
 def kernel_source_sha() -> str:
@@ -164,6 +165,9 @@ def lib():
     L.lumahip_decode_frames_device_planar_f16.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, pp3, sz]
     L.lumahip_encode_frame_host_f16.argtypes = [vp, vp, u, u, f, i, pp3, ip3, C.POINTER(f)]
     L.lumahip_decode_frame_host_f16.argtypes = [vp, pp3, ip3, u, u, i, f, vp]
+    L.lumahip_set_source_quantizer.argtypes = [vp, i, u, i, u, f, f, vp, sz]
+    L.lumahip_transcode_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, vp]
+    L.lumahip_transcode_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, C.POINTER(f)]
     L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_host_register.argtypes = [vp, vp, sz]
@@ -439,6 +443,12 @@ class Context:
         self._chk(self.L.lumahip_set_quantizer(self.h, ptf, bitdepth, cs, bitdepthC, max_lum, min_lum,
                                                lut.ctypes.data, lut.size))
 
+    def set_source_quantizer(self, ptf, bitdepth, cs, bitdepthC, max_lum, min_lum, lut: np.ndarray):
+        """the stream the transcode calls READ (held beside the quantizer of set_quantizer, independent of it)"""
+        lut = np.ascontiguousarray(lut, dtype=np.float32)
+        self._chk(self.L.lumahip_set_source_quantizer(self.h, ptf, bitdepth, cs, bitdepthC, max_lum, min_lum,
+                                                      lut.ctypes.data, lut.size))
+
     def quantizer_info(self):
         a = (C.c_int * 5)()
         self._chk(self.L.lumahip_quantizer_info(self.h, a))
@@ -489,6 +499,21 @@ class Context:
         self._chk(self.L.lumahip_decode_frame_host(self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]),
                                                    _arr3(C.c_int, strides), w, h, profile, sc, out.ctypes.data))
         return out
+
+    def transcode_frame(self, planes, strides, w, h, src_sc=1.0, src_profile=2, dst_sc=1.0, dst_profile=2, align=32, dst_strides=None,
+                        want_mean=True):
+        """code planes under the source quantizer -> (planes, strides, mean_lum) under the quantizer, one fused launch; equal to
+        decode_frame on a context with the source quantizer followed by encode_frame on this one"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        _, hs, st, _ = plane_geometry(w, h, dst_profile, align)
+        if dst_strides is not None:
+            st = tuple(dst_strides)
+        out = [np.zeros((hs[p], st[p]), dtype=np.uint8) for p in range(3)]
+        mean = C.c_float(0)
+        self._chk(self.L.lumahip_transcode_frame_host(self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
+                                                      src_profile, src_sc, w, h, _arr3(C.c_void_p, [p.ctypes.data for p in out]),
+                                                      _arr3(C.c_int, st), dst_profile, dst_sc, C.byref(mean) if want_mean else None))
+        return out, st, (float(mean.value) if want_mean else None)
 
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
@@ -582,6 +607,13 @@ class Context:
         self._chk(self.L.lumahip_encode_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
                                                       _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
                                                       _arr3(C.c_size_t, plane_frame_strides), stats_ptr))
+
+    def transcode_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
+                                dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr=None):
+        self._chk(self.L.lumahip_transcode_frames_device(self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides),
+                                                         _arr3(C.c_size_t, src_plane_frame_strides), src_profile, src_sc, nframes, w, h,
+                                                         _arr3(C.c_void_p, dst_plane_ptrs), _arr3(C.c_int, dst_strides),
+                                                         _arr3(C.c_size_t, dst_plane_frame_strides), dst_profile, dst_sc, stats_ptr))
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

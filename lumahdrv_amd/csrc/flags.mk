@@ -11,3 +11,6 @@ FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vect
 #   VALU-bound YCbCr kernels unchanged -- so it is the encode unit's only.  ("iterative-ilp" crashes this compiler on these units.)
 FLAGS_lumahip_encode := -mllvm -amdgpu-sched-strategy=max-ilp
 FLAGS_lumahip_encode_f16 := $(FLAGS_lumahip_encode)
+#   lumahip_transcode: the default strategy.  Its kernels are neither the HBM-bound encode kernels max-ilp helped nor measured
+#   either way yet: no A/B, no flag.
+FLAGS_lumahip_transcode :=

@@ -102,7 +102,8 @@ struct DecArgs {
 // [lut: lut_len+pad floats, rounded to 16 B | records: nbuckets u32, rounded to 16 B]
 // [YCbCr decode with per-stream tables: y table (as long as the lut), then the Cb and Cr chroma-term tables, maxC+1 floats each]
 // [u'v' table: maxC+1 floats (Lu'v' decode only), see luv_chroma_uv | half-input table (YCbCr encode, LM == 6)].
-// Which parts a kernel stages is a compile-time set (encode: records; decode: the table).
+// Which parts a kernel stages is a compile-time set (encode: records; decode: the table; transcode: both sides, the two-quantizer
+// stage_tables below).
 // STAGE_POWFN: the 768-byte powf tables instead of the wide ones (the half-input kernels: their LDS belongs to the half table).
 enum : int { STAGE_LUT = 1, STAGE_REC = 4, STAGE_POWF = 8, STAGE_UV = 16, STAGE_YT = 32, STAGE_POWFN = 64, STAGE_HALF = 128, STAGE_CT = 256 };
 
@@ -204,6 +205,27 @@ LH_DEV void stage_tables(unsigned char *smem, const QuantDev &q, const float *ha
             uv[i] = uv_table_entry(i, q.maxC);
     }
     __syncthreads();
+}
+
+// Two quantizers in one workgroup (k_transcode): ONE copy of the powf tables when either side asks for them (first, as above),
+// behind it the tables of `qa` (WHAT_A), then those of `qb` (WHAT_B) from the next 16-byte boundary on -- each side staged by
+// the function above at its own base, so the layout inside a side is the one its device functions know.
+// lds_quant_bytes: what a side occupies behind the powf tables
+template <int WHAT>
+LH_DEV int lds_quant_bytes(const QuantDev &q)
+{
+    static_assert(!(WHAT & STAGE_HALF), "the half-input table is not part of a two-quantizer layout");
+    const int col = (((int)q.maxC + 1) * 4 + 15) & ~15;
+    return ((WHAT & STAGE_LUT) ? lds_lut_bytes(q) : 0) + ((WHAT & STAGE_REC) ? lds_rec_bytes(q) : 0) + ((WHAT & STAGE_YT) ? lds_lut_bytes(q) : 0) +
+           ((WHAT & STAGE_CT) ? 2 * col : 0) + ((WHAT & STAGE_UV) ? col : 0);
+}
+template <int WHAT_A, int WHAT_B>
+LH_DEV void stage_tables(unsigned char *smem, const QuantDev &qa, const QuantDev &qb)
+{
+    static_assert(!((WHAT_A | WHAT_B) & (STAGE_POWFN | STAGE_HALF)), "the wide powf tables or none; no half-input table");
+    constexpr int POWF = (WHAT_A | WHAT_B) & STAGE_POWF;
+    stage_tables<(WHAT_A & ~STAGE_POWF) | POWF>(smem, qa);
+    stage_tables<WHAT_B & ~STAGE_POWF>(smem + lds_table_offset<POWF>() + lds_quant_bytes<WHAT_A>(qa), qb);
 }
 
 // ---- sample stores / loads ------------------------------------------------------------------------
@@ -466,7 +488,8 @@ LH_DEV void stats_flush(EncStats &st, float *stats, int tx)
 // colour transform of one unit (row-major pixel order inside the unit: j = r*VW + i)
 // HALF (YCbCr, LM == 6): the pixels go through the half-input table at `s_half` (LDS), which has `* sc` folded in
 // Returns (HALF only) whether this thread's unit fell back to the general functions.
-template <int CS, int VW, bool YCODE = false, bool HALF = false, typename K>
+// STATS = false: the caller accumulates the statistics itself (k_transcode with the composite records, whose channel 0 is not the luminance)
+template <int CS, int VW, bool YCODE = false, bool HALF = false, bool STATS = true, typename K>
 LH_DEV bool enc_transform(EncUnit<VW> &u, const EncArgs &a, const K &k, float (&c0)[2 * VW],
                           float (&c1)[2 * VW], float (&c2)[2 * VW], EncStats &st, const float *s_half = nullptr)
 {
@@ -502,7 +525,7 @@ LH_DEV bool enc_transform(EncUnit<VW> &u, const EncArgs &a, const K &k, float (&
                 xform_fwd<CS>(u.in[0][r][i], u.in[1][r][i], u.in[2][r][i], k, c0[r * VW + i], c1[r * VW + i], c2[r * VW + i]);
     }
 
-    if (a.stats) {
+    if (STATS && a.stats) {
 #pragma unroll
         for (int j = 0; j < 2 * VW; j++) {
             st.sum += c0[j];
@@ -955,9 +978,12 @@ struct DecNoHook {
     __device__ __forceinline__ void operator()() const {}
 };
 // OUT16: the frames are binary16 (a.dst[c] points at halves; offsets and strides count elements either way)
-template <int CS, bool SUB, int VW, bool DISP, bool UVTAB, bool YT = false, bool SCFAST = false, bool RB = false, bool OUT16 = false,
+// VALUES: nothing is stored; the unit's floats -- after `/ sc`: what the reference stores in its LumaFrame -- go to vals[c][r][i],
+// colour channel c of pixel i in row r (dec_values below, for k_transcode)
+template <int CS, bool SUB, int VW, bool DISP, bool UVTAB, bool YT = false, bool SCFAST = false, bool RB = false, bool OUT16 = false, bool VALUES = false,
           typename LutPtr, typename K, typename Hook = DecNoHook>
-LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k, LutPtr lut, const float *s_uv, Hook before_stores = Hook())
+LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k, LutPtr lut, const float *s_uv, Hook before_stores = Hook(),
+                        float (*vals)[2][VW] = nullptr)
 {
     bool gathered = false;
     static_assert(!RB || (YT && CS == CS_YCBCR), "the red / blue tables belong to the YCbCr kernels with the y table");
@@ -1091,6 +1117,17 @@ LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k,
                     out[c][r][i] = div_ieee(out[c][r][i], k.sc);
     }
 
+    if constexpr (VALUES) {
+        static_assert(!DISP && !OUT16, "values only: no stores of any kind");
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+#pragma unroll
+            for (int r = 0; r < 2; r++)
+#pragma unroll
+                for (int i = 0; i < VW; i++)
+                    vals[c][r][i] = out[c][r][i];
+        return gathered;
+    }
     before_stores();
     if constexpr (OUT16) {
         // (packed and planar frames only: the host never sets rot_on for these kernels, lumahip_decode_frames_device_f16)
@@ -1163,6 +1200,13 @@ LH_DEV bool dec_process(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k,
         }
     }
     return gathered;
+}
+
+// the arithmetic of dec_process alone: out = the unit's floats, in the layout of EncUnit::in
+template <int CS, bool SUB, int VW, bool UVTAB, bool YT = false, bool SCFAST = false, typename LutPtr, typename K>
+LH_DEV void dec_values(const DecUnit<SUB, VW> &u, const DecArgs &a, const K &k, LutPtr lut, const float *s_uv, float (&out)[3][2][VW])
+{
+    dec_process<CS, SUB, VW, false, UVTAB, YT, SCFAST, false, false, true>(u, a, k, lut, s_uv, DecNoHook(), out);
 }
 
 // DISP: additionally (or only) emit the RGBA8 display image -- a separate instantiation so that the plain
@@ -1282,6 +1326,136 @@ __global__ __launch_bounds__(1024) void k_decode(const DecArgs a)
             if (threadIdx.x == 0 && s_gathered[0])
                 __hip_atomic_store(a.rb_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
+    }
+}
+
+// ---- TRANSCODE --------------------------------------------------------------------------------------
+// Code planes of one stream -> code planes of another, DEC then ENC of the head of this file without the float frame between
+// them: per unit, dec_load and dec_values under the source quantizer (`/ sc` of the source included), the floats handed to
+// enc_transform in registers (`* sc` of the target included: the division and the multiplication both stay, the planes are the
+// two-call result bit for bit), enc_emit under the target quantizer.  6 B per pixel instead of 30 (profile 2 -> profile 2).
+// CSD / SUBD: the source's colour space and subsampling, CSE / SUBE: the target's -- independent; 4:4:4 -> 4:2:0 averages the
+// per-pixel chroma as enc_emit does, 4:2:0 -> 4:4:4 stores the replicated sample's code four times.
+// LM: the target's search mode: 3 or 7 (Lu'v': the luminance records in LDS), 5 (YCbCr: the composite records in LDS).
+// Source side: the luminance table in LDS, plus the u'v' table (Lu'v') or the y table and the two chroma-term tables (YCbCr);
+// red and blue are always computed (no per-stream red / blue tables, no feedback word: the launch is a function of the
+// arguments alone).  LDS: [powf tables, once, when either side is YCbCr][source tables][target records] (stage_tables<A, B>).
+// The loop is k_encode's: the next unit's sample loads are issued after the current unit's stores.
+struct TransArgs {
+    DecArgs d;   // q, src, stride, src_frame_stride, sc, bps, aligned of the source planes; g (the same geometry as e.g)
+    EncArgs e;   // q (the composite records for LM == 5), dst, stride, dst_frame_stride, sc, bps, aligned, stats of the target planes
+};
+
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__(1024) void k_transcode(const TransArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(CSD == CS_LUV || CSD == CS_YCBCR, "source colour spaces: Lu'v' and YCbCr");
+    static_assert((CSE == CS_LUV && (LM == 3 || LM == 7)) || (CSE == CS_YCBCR && LM == 5), "target: Lu'v' with records in LDS, YCbCr with the composite records");
+    constexpr bool YD = CSD == CS_YCBCR, YE = CSE == CS_YCBCR;
+    constexpr int WHAT_D = STAGE_LUT | (YD ? STAGE_POWF | STAGE_YT | STAGE_CT : STAGE_UV);
+    constexpr int WHAT_E = STAGE_REC | (YE ? STAGE_POWF : 0);
+    stage_tables<WHAT_D, WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<WHAT_D | WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    EncStats st;
+    st.frame = -1;
+    st.sum = 0.0f;
+    st.mn = __builtin_inff();
+    st.mx = -__builtin_inff();
+
+    DecUnit<SUBD, VW> cur, nxt;
+    dec_load<SUBD, VW>(cur, a.d, blockIdx.x, tx, ty, NW);
+    for (int t = blockIdx.x; t < a.d.g.totalTiles; t += G) {
+        if (a.e.stats) {
+            const int f = t / a.d.g.tilesPerFrame;  // wave-uniform
+            if (f != st.frame) {
+                stats_flush(st, a.e.stats, tx);
+                st.frame = f;
+            }
+        }
+        if (cur.valid) {
+            EncUnit<VW> u;
+            if constexpr (YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    dec_values<CSD, SUBD, VW, false, true, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+                else
+                    dec_values<CSD, SUBD, VW, false, true, false>(cur, a.d, kd, s_lut, s_uv, u.in);
+            } else {
+                dec_values<CSD, SUBD, VW, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, YE, false, !YE>(u, a.e, ke, c0, c1, c2, st);
+            if constexpr (YE) {
+                // channel 0 is t = 219 y + 16 (ycbcr_fwd<., YCODE>); the statistics are about the luminance PQdec(t / 255), which
+                // only a launch that asks for them evaluates -- with the complete functions, whose bits the encode kernels' are
+                if (a.e.stats) {
+#pragma unroll
+                    for (int j = 0; j < 2 * VW; j++) {
+                        const float lum = pq_decode(div_ieee(c0[j], 255.0f), ke);
+                        st.sum += lum;
+                        st.mn = fminf(st.mn, lum);
+                        st.mx = fmaxf(st.mx, lum);
+                    }
+                }
+            }
+            // (the tile, and with it the frame, is wave-uniform: saying so keeps the planes' frame offsets scalar)
+            enc_emit<CSE, SUBE, VW, LM>(__builtin_amdgcn_readfirstlane(cur.f), cur.ux, cur.uy, c0, c1, c2, a.e, static_cast<const float *>(nullptr), s_rec);   // (record searches: no table pointer)
+        }
+        dec_load<SUBD, VW>(nxt, a.d, t + G, tx, ty, NW);
+        cur = nxt;
+    }
+    if (a.e.stats)
+        stats_flush(st, a.e.stats, tx);
+}
+
+// The decoded-and-transformed channel 0 of one frame, pixel by pixel with the complete functions (the array the reference's
+// sequential mean sums, k_seq_sum): only for the host call's rare exact mean (lumahip_transcode_frame_host).
+struct TransChan0Args {
+    QuantDev qd;
+    const unsigned char *src[3];
+    int stride[3];
+    int bps, sub, w, h;
+    float sc_src, sc_dst, Lmax_dst;
+    float *out;
+};
+
+template <int CSD, int CSE>
+__global__ __launch_bounds__(256) void k_transcode_channel0(const TransChan0Args a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[(CSD == CS_YCBCR || CSE == CS_YCBCR) ? sizeof(PowfTablesWide) : 16];
+    PowfTablesWide &s_pw = *reinterpret_cast<PowfTablesWide *>(s_raw);
+    if constexpr (CSD == CS_YCBCR || CSE == CS_YCBCR) {
+        stage_powf_tables(&s_pw);
+        __syncthreads();
+    }
+    const XformConst kd = make_xform_const<CSD>(a.sc_src, a.qd.Lmax, &s_pw), ke = make_xform_const<CSE>(a.sc_dst, a.Lmax_dst, &s_pw);
+    const size_t n = (size_t)a.w * a.h;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int y = (int)(i / a.w), x = (int)(i - (size_t)y * a.w);
+        const int yc = a.sub ? y / 2 : y, xc = a.sub ? x / 2 : x;
+        int s0[1], s1[1], s2[1];
+        load_samples<1>(a.src[0] + (size_t)y * a.stride[0] + (size_t)x * a.bps, s0, a.bps, 0);
+        load_samples<1>(a.src[1] + (size_t)yc * a.stride[1] + (size_t)xc * a.bps, s1, a.bps, 0);
+        load_samples<1>(a.src[2] + (size_t)yc * a.stride[2] + (size_t)xc * a.bps, s2, a.bps, 0);
+        float r, g, b, c0, c1, c2;
+        xform_inv<CSD>(dequantize_lut(s0[0], a.qd.lut, a.qd.maxVal), dequantize_color(s1[0], a.qd.maxC), dequantize_color(s2[0], a.qd.maxC), kd, r, g, b);
+        r = div_ieee(r, a.sc_src);
+        g = div_ieee(g, a.sc_src);
+        b = div_ieee(b, a.sc_src);
+        xform_fwd<CSE>(r * a.sc_dst, g * a.sc_dst, b * a.sc_dst, ke, c0, c1, c2);
+        a.out[i] = c0;
     }
 }
 

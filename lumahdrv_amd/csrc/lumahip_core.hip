@@ -385,50 +385,68 @@ hipError_t upload_records(DevTable<uint32_t> &d, const std::vector<uint32_t> &re
 size_t powf_lds_bytes(const QuantDev &q) { return q.cs == CS_YCBCR ? sizeof(PowfTablesWide) : 0; }
 }  // namespace
 
-// device copy of the table + the decode-side decisions: everything a decoder needs.  Nothing of the context changes before
-// both uploads have succeeded; then the tables derived from the old table go with it.
-static int upload_table(lumahip_ctx *c)
-{
-    const size_t n = c->h_lut.size();
-    const size_t powf_b = powf_lds_bytes(c->q);
-    // decode side: luminance table (+ Lu'v' chroma table, + the powf tables for YCbCr) staged in LDS
-    const bool lut_in_lds = c->bitdepthC <= 12 && (n + 4) * sizeof(float) <= std::max<size_t>(c->lds_table_max, 16 * 1024 + 16) &&
-                            (n + 4) * sizeof(float) + ((size_t)4 << c->bitdepthC) + 64 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP;
-    const size_t lut_floats = (n + 1 + 3) & ~(size_t)3;  // NaN padding up to a multiple of 16 bytes
+// The decode-side tables of a quantizer -- the luminance table and, YCbCr only, the per-stream y table -- and whether a decode-side
+// kernel stages them in LDS: what lumahip_set_quantizer and lumahip_set_source_quantizer both upload.  Built beside the context.
+struct DecodeTables {
     DevTable<float> lut, ytab;
-    HIPCHK(c, lut.upload(c->h_lut.data(), n, lut_floats, __builtin_nanf("")));
-    if (c->q.cs == CS_YCBCR && c->use_ycbcr_tables && lut_in_lds) {
+    bool lut_in_lds = false;
+    size_t lut_floats = 0;
+};
+static int upload_decode_tables(lumahip_ctx *c, const Lut &h_lut, const QuantDev &q, unsigned bitdepthC, DecodeTables &t)
+{
+    const size_t n = h_lut.size();
+    const size_t powf_b = powf_lds_bytes(q);
+    // decode side: luminance table (+ Lu'v' chroma table, + the powf tables for YCbCr) staged in LDS
+    t.lut_in_lds = bitdepthC <= 12 && (n + 4) * sizeof(float) <= std::max<size_t>(c->lds_table_max, 16 * 1024 + 16) &&
+                   (n + 4) * sizeof(float) + ((size_t)4 << bitdepthC) + 64 + powf_b <= LUMAHIP_LDS_PER_WORKGROUP;
+    t.lut_floats = (n + 1 + 3) & ~(size_t)3;  // NaN padding up to a multiple of 16 bytes
+    HIPCHK(c, t.lut.upload(h_lut.data(), n, t.lut_floats, __builtin_nanf("")));
+    if (q.cs == CS_YCBCR && c->use_ycbcr_tables && t.lut_in_lds) {
         // YCbCr decode: the first PQ evaluation of a pixel depends on its luminance code only -- one table per stream, built
         // with the host libm (the function the reference calls).  Only for tables of finite non-negative values: the
         // kernels' range analysis of what follows (luma_device.hpp ycbcr_inv) assumes them.
         bool ok = true;
         for (size_t i = 0; i < n && ok; i++)
-            ok = c->h_lut[i] >= 0.0f && c->h_lut[i] <= 3.0e38f;
-        const size_t both = 2 * (((n + 4) * sizeof(float) + 15) & ~(size_t)15) + ((size_t)8 << c->bitdepthC) + 64 + powf_b;   // + the two chroma-term tables
+            ok = h_lut[i] >= 0.0f && h_lut[i] <= 3.0e38f;
+        const size_t both = 2 * (((n + 4) * sizeof(float) + 15) & ~(size_t)15) + ((size_t)8 << bitdepthC) + 64 + powf_b;   // + the two chroma-term tables
         if (ok && both <= LUMAHIP_LDS_PER_WORKGROUP) {
             Lut yt(n);
-            ycbcr_ytab_host(c->h_lut.data(), n, c->q.Lmax, yt.data());
-            HIPCHK(c, ytab.upload(yt.data(), n, lut_floats, 0.0f));
+            ycbcr_ytab_host(h_lut.data(), n, q.Lmax, yt.data());
+            HIPCHK(c, t.ytab.upload(yt.data(), n, t.lut_floats, 0.0f));
         }
     }
-    c->lut_in_lds = lut_in_lds;
-    c->d_lut = std::move(lut);
-    c->d_ytab = std::move(ytab);
+    return LUMAHIP_OK;
+}
+// ... published in the quantizer description the kernels take (literal search until an encode-side launch builds the records)
+static void publish_decode_tables(QuantDev &q, const DevTable<float> &lut, const DevTable<float> &ytab, size_t n, size_t lut_floats)
+{
+    q.lut = lut.get();
+    q.rec = nullptr;
+    q.ytab = ytab.get();
+    q.lut_len = (int)n;
+    q.pad = (int)(lut_floats - n);
+    q.maxVal = (int)n - 1;                                   // (int)pow(2,bitdepth)-1, src/luma_quantizer.cpp:180
+    q.mode = n <= 4096 ? LUT_LITERAL_LDS : LUT_LITERAL_GLOBAL;
+    q.shift = q.kmin = q.nbuckets = 0;
+}
+
+// device copy of the table + the decode-side decisions: everything a decoder needs.  Nothing of the context changes before
+// both uploads have succeeded; then the tables derived from the old table go with it.
+static int upload_table(lumahip_ctx *c)
+{
+    DecodeTables t;
+    if (int rc = upload_decode_tables(c, c->h_lut, c->q, c->bitdepthC, t))
+        return rc;
+    c->lut_in_lds = t.lut_in_lds;
+    c->d_lut = std::move(t.lut);
+    c->d_ytab = std::move(t.ytab);
     c->d_rec.reset();
     c->d_rec_y.reset();
     c->rb_tabs.clear();     // (the red / blue tables of the YCbCr decode kernels were built from the old y table)
     c->rb_unavailable = false;
     c->tix.reset();
     c->index_ready = false;
-    QuantDev &q = c->q;
-    q.lut = c->d_lut.get();
-    q.rec = nullptr;
-    q.ytab = c->d_ytab.get();
-    q.lut_len = (int)n;
-    q.pad = (int)(lut_floats - n);
-    q.maxVal = (int)n - 1;                                   // (int)pow(2,bitdepth)-1, src/luma_quantizer.cpp:180
-    q.mode = n <= 4096 ? LUT_LITERAL_LDS : LUT_LITERAL_GLOBAL;
-    q.shift = q.kmin = q.nbuckets = 0;
+    publish_decode_tables(c->q, c->d_lut, c->d_ytab, c->h_lut.size(), t.lut_floats);
     return LUMAHIP_OK;
 }
 
@@ -504,17 +522,25 @@ static int requantize(lumahip_ctx *c)
     return upload_table(c);
 }
 
-extern "C" int lumahip_set_quantizer(lumahip_ctx *c, int ptf, unsigned bitdepth, int cs, unsigned bitdepthC,
-                                     float maxLum, float minLum, const float *lut, size_t n)
+// what lumahip_set_quantizer and lumahip_set_source_quantizer ask of their arguments
+static int check_quantizer_args(lumahip_ctx *c, int ptf, unsigned bitdepth, unsigned bitdepthC, const float *lut, size_t n)
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
     if (bitdepth < 1 || bitdepth > 16 || bitdepthC < 1 || bitdepthC > 16)
         return fail(c, LUMAHIP_ERR_ARG, "bit depths must be 1..16 (got %u / %u)", bitdepth, bitdepthC);
     if (!lut || n != ((size_t)1 << bitdepth))
         return fail(c, LUMAHIP_ERR_ARG, "LUT must hold 2^bitdepth = %zu floats (got %zu)", (size_t)1 << bitdepth, n);
     if (ptf < 0 || ptf > 4)
         return fail(c, LUMAHIP_ERR_ARG, "unknown transfer function %d", ptf);
+    return LUMAHIP_OK;
+}
+
+extern "C" int lumahip_set_quantizer(lumahip_ctx *c, int ptf, unsigned bitdepth, int cs, unsigned bitdepthC,
+                                     float maxLum, float minLum, const float *lut, size_t n)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (int rc = check_quantizer_args(c, ptf, bitdepth, bitdepthC, lut, n))
+        return rc;
     if (c->es_head != c->es_tail)
         return fail(c, LUMAHIP_ERR_STATE, "frames pushed with lumahip_encode_stream_push are still in flight: pop them before changing the quantizer");
     // an unknown colour space is accepted here, as in the reference (setQuantizer stores it blindly,
@@ -536,6 +562,37 @@ extern "C" int lumahip_set_quantizer(lumahip_ctx *c, int ptf, unsigned bitdepth,
     if (rc)
         return rc;
     c->have_quant = true;
+    return LUMAHIP_OK;
+}
+
+// The source quantizer of the transcode calls (lumahip_ctx::SourceQuant): a second set of decode-side tables beside the
+// quantizer's, owned the same way (DevTable).  Nothing of the quantizer above is read or written here, and nothing here by
+// lumahip_set_quantizer.  The old tables go when the new ones are up: hipFree waits for whatever launch still reads them.
+extern "C" int lumahip_set_source_quantizer(lumahip_ctx *c, int ptf, unsigned bitdepth, int cs, unsigned bitdepthC,
+                                            float maxLum, float minLum, const float *lut, size_t n)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (int rc = check_quantizer_args(c, ptf, bitdepth, bitdepthC, lut, n))
+        return rc;
+    (void)minLum;   // (part of the stream's description, as in lumahip_set_quantizer; no decode-side table depends on it)
+    HIPCHK(c, hipSetDevice(c->device));
+    QuantDev q{};
+    q.maxC = (float)(((unsigned)1 << bitdepthC) - 1);     // src/luma_quantizer.cpp:183
+    q.cs = cs;
+    q.Lmax = maxLum;
+    DecodeTables t;
+    if (int rc = upload_decode_tables(c, Lut(lut, lut + n), q, bitdepthC, t))
+        return rc;
+    lumahip_ctx::SourceQuant &sq = c->src;
+    sq.d_lut = std::move(t.lut);
+    sq.d_ytab = std::move(t.ytab);
+    publish_decode_tables(q, sq.d_lut, sq.d_ytab, n, t.lut_floats);
+    sq.q = q;
+    sq.bitdepth = bitdepth;
+    sq.bitdepthC = bitdepthC;
+    sq.lut_in_lds = t.lut_in_lds;
+    sq.have = true;
     return LUMAHIP_OK;
 }
 

@@ -72,6 +72,34 @@ __global__ void k_fold_stats(const float *part, float *out, int nframes)
 
 namespace lhost {
 
+// Per-frame statistics of a launch (EncArgs::stats): stats_begin before it -- *part = the partial triples, initialised on *s --
+// and stats_fold behind it, on the same stream.
+// The partial triples live in a context-owned scratch buffer; launches with statistics of one context share it, which is
+// safe on one stream (in order) and is why an unordered section with statistics keeps to its first lane (*s is set to it)
+int stats_begin(lumahip_ctx *c, unsigned nframes, bool lanes, hipStream_t *s, float **part)
+{
+    const size_t need = (size_t)nframes * STATS_SLOTS * 3 * sizeof(float);
+    if (c->d_stats_part_cap < need) {
+        HIPCHK(c, hipDeviceSynchronize());
+        (void)hipFree(c->d_stats_part);
+        c->d_stats_part = nullptr;
+        c->d_stats_part_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_stats_part, need));
+        c->d_stats_part_cap = need;
+    }
+    if (lanes && c->lanes_active)
+        *s = c->lane_stream[0];
+    *part = c->d_stats_part;
+    const int np = (int)nframes * STATS_SLOTS;
+    hipLaunchKernelGGL(k_init_stats, dim3((np + 255) / 256), dim3(256), 0, *s, c->d_stats_part, np);
+    return LUMAHIP_OK;
+}
+
+void stats_fold(lumahip_ctx *c, unsigned nframes, float *stats, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_fold_stats, dim3((nframes + 63) / 64), dim3(64), 0, s, c->d_stats_part, stats, (int)nframes);
+}
+
 int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const DstPlanes &p, float *stats, const EncodeLaunch &o)
 {
     const bool in16 = f.elem == Elem::F16;
@@ -166,30 +194,14 @@ int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, cons
         HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int grid = grid_for(c, threads, a.g.totalTiles, 0, 0, half ? 2 : cs_eff == CS_YCBCR ? 1 : 0);
     hipStream_t s = launch_stream(c, o.stream, o.lanes);
-    if (stats) {
-        // partial triples live in a context-owned scratch buffer; launches with statistics of one context share it, which is
-        // safe on one stream (in order) and is why an unordered section with statistics keeps to its first lane
-        const size_t need = (size_t)nframes * STATS_SLOTS * 3 * sizeof(float);
-        if (c->d_stats_part_cap < need) {
-            HIPCHK(c, hipDeviceSynchronize());
-            (void)hipFree(c->d_stats_part);
-            c->d_stats_part = nullptr;
-            c->d_stats_part_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_stats_part, need));
-            c->d_stats_part_cap = need;
-        }
-        if (o.lanes && c->lanes_active)
-            s = c->lane_stream[0];
-        a.stats = c->d_stats_part;
-        const int np = (int)nframes * STATS_SLOTS;
-        hipLaunchKernelGGL(k_init_stats, dim3((np + 255) / 256), dim3(256), 0, s, c->d_stats_part, np);
-    }
+    if (stats && (rc = stats_begin(c, nframes, o.lanes, &s, &a.stats)))
+        return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
     half_guard.launched = true;
     if (half_flag && (rc = lag_policy_launched(c, c->half_pol, s)))
         return rc;
     if (stats)
-        hipLaunchKernelGGL(k_fold_stats, dim3((nframes + 63) / 64), dim3(64), 0, s, c->d_stats_part, stats, (int)nframes);
+        stats_fold(c, nframes, stats, s);
     HIPCHK(c, hipGetLastError());
     return LUMAHIP_OK;
 }

@@ -996,6 +996,68 @@ extern "C" int lumahip_decode_frame_host(lumahip_ctx *c, const unsigned char *co
     return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, Elem::F32, c->q.cs);
 }
 
+// Source planes up, one transcode launch, destination planes down, synchronously on the context's stream; the context's plane
+// staging holds both sets.  mean_lum as lumahip_encode_frame_host: the launch's statistic, replaced by the reference's
+// sequential sum -- over channel 0 of the decoded and transformed frame, which only then is written, into the staging frame --
+// in the cases where that call takes the exact sum too (mean_needs_reference_sum).
+extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile,
+                                            float src_sc, unsigned w, unsigned h, unsigned char *const dst_planes[3], const int dst_stride[3],
+                                            int dst_profile, float dst_sc, float *mean_lum)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!src_planes || !src_stride || !dst_planes || !dst_stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    int rc = check_geom(c, w, h, dst_profile, c->q.cs);
+    if (rc)
+        return rc;
+    if (src_profile < 0 || src_profile > 3)
+        return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src_profile);
+    if (!c->src.have)
+        return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    PlaneLayout Ls, Ld;
+    plane_layout(Ls, w, h, src_profile, src_stride);
+    plane_layout(Ld, w, h, dst_profile, dst_stride);
+    int p = bad_plane(Ls, src_planes, src_stride);
+    if (p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "source plane %d: null or stride %d < row bytes %d", p, src_stride[p], Ls.row_bytes[p]);
+    if ((p = bad_plane(Ld, dst_planes, dst_stride)) >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "destination plane %d: null or stride %d < row bytes %d", p, dst_stride[p], Ld.row_bytes[p]);
+    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, Ls.total + Ld.total)))
+        return rc;
+    if (!c->d_stats)
+        HIPCHK(c, hipMalloc(&c->d_stats, 3 * sizeof(float)));
+    unsigned char *sp[3], *dp[3];
+    device_planes(sp, c->d_planes, Ls, src_stride);
+    device_planes(dp, c->d_planes + Ls.total, Ld, dst_stride);
+    for (int k = 0; k < 3; k++)
+        if ((rc = plane_h2d(c, sp, src_planes, src_stride, Ls, k, 0, h, c->stream)))
+            return rc;
+    if ((rc = transcode_impl(c, {sp, src_stride, NO_PFS, src_profile}, src_sc, 1, w, h, {dp, dst_stride, NO_PFS, dst_profile}, dst_sc,
+                             mean_lum ? c->d_stats : nullptr, {c->stream, false})))
+        return rc;
+    if ((rc = planes_d2h(c, dst_planes, dp, dst_stride, Ld, 0, h, c->stream, false)))
+        return rc;
+    if (!mean_lum) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return LUMAHIP_OK;
+    }
+    float st[3];
+    if ((rc = read_small(c, st, c->d_stats, 3, c->stream)))  // synchronises the stream
+        return rc;
+    *mean_lum = st[0] / (float)((int)w * (int)h);
+    if (mean_needs_reference_sum(*mean_lum, st[1], w, h)) {
+        if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, (size_t)w * h * sizeof(float))))
+            return rc;
+        if ((rc = transcode_channel0(c, {sp, src_stride, NO_PFS, src_profile}, src_sc, w, h, dst_sc, c->d_frame, c->stream)))
+            return rc;
+        return seq_mean(c, c->d_frame, w, h, mean_lum);
+    }
+    return LUMAHIP_OK;
+}
+
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the
 // caller's halves go up as they are (no round-trip test, unlike the half upload above) and the decoded halves come down as the
 // kernel wrote them.

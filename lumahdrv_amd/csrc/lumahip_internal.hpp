@@ -5,14 +5,15 @@
 //                       memory helpers                                                                    (no kernels)
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
-//   lumahip_pick.hpp    which k_encode / k_decode instantiation a launch takes: pick_enc<IN16> / pick_dec<OUT16>, included by
-//                       the four kernel units below and by nothing else
+//   lumahip_pick.hpp    which k_encode / k_decode / k_transcode instantiation a launch takes: pick_enc<IN16> / pick_dec<OUT16> /
+//                       pick_trans<VW>, included by the five kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
 //                       tables next to the kernel that builds them
 //   lumahip_encode_f16.hip / lumahip_decode_f16.hip  pick_enc<true> / pick_dec<true> (the binary16-frame kernels, exported as
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
+//   lumahip_transcode.hip  pick_trans (every k_transcode), the transcode dispatch and its two entry points
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -131,6 +132,18 @@ struct lumahip_ctx {
     std::vector<float> h_lut;     // host copy of the table handed to lumahip_set_quantizer
     bool lut_in_lds = true;  // decode side: tables up to 12 bits are staged in LDS
     float minLum = 0.0f;
+
+    // The SOURCE quantizer of the transcode calls (lumahip_set_source_quantizer, lumahip_transcode.hip): held beside the quantizer
+    // above and independent of it -- setting one never disturbs the other.  Decode-side tables only: the luminance table, the
+    // YCbCr y table; the u'v' / chroma-term tables are computed by the kernel as it stages.  No search records, no red / blue
+    // tables, no LagPolicy: a transcode launch is chosen from its arguments alone.
+    struct SourceQuant {
+        bool have = false;
+        unsigned bitdepth = 0, bitdepthC = 0;
+        lh::QuantDev q{};
+        lhost::DevTable<float> d_lut, d_ytab;
+        bool lut_in_lds = false;
+    } src;
 
     // staging for the _host entry points
     float *d_frame = nullptr;
@@ -361,7 +374,7 @@ struct DecodeLaunch {
 static inline size_t lut_lds_bytes(const QuantDev &q) { return ((size_t)(q.lut_len + q.pad) * 4 + 15) & ~(size_t)15; }   // the luminance table, or the y table, in LDS
 size_t lds_bytes(const lumahip_ctx *c, bool encode_side, int cs_eff, bool ycode = false, bool half = false);   // ycode: the composite-record encode kernels; half: + the half-input table
 int block_threads_for(const lumahip_ctx *c, size_t lds, bool few_waves = false, bool valu_bound = false);
-int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers = 0, int ycbcr = 0);   // few_writers: 0 no, 1 yes, 2 yes with the colour planes in separate buffers; ycbcr: 0 no, 1 yes, 2 the half-input encode kernels
+int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers = 0, int ycbcr = 0, bool transcode = false);   // few_writers: 0 no, 1 yes, 2 yes with the colour planes in separate buffers; ycbcr: 0 no, 1 yes, 2 the half-input encode kernels; transcode: the k_transcode family (dir 0)
 // ---- lumahip_core.hip
 int ensure_search_index(lumahip_ctx *c, hipStream_t s);   // every encode-side launch calls this first (lazy build / process-wide cache); s: the stream that launch goes to
 bool ycbcr_composite_ready(const lumahip_ctx *c);   // encode: the composite luma -> code records exist and fit LDS
@@ -400,6 +413,8 @@ int check_layout(lumahip_ctx *c, const SrcFrames &f, bool overlap_test, const in
 // ---- lumahip_encode.hip / lumahip_decode.hip
 int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const DstPlanes &p, float *stats, const EncodeLaunch &o);
 bool encode_supports_in16(lumahip_ctx *c, unsigned w);
+int stats_begin(lumahip_ctx *c, unsigned nframes, bool lanes, hipStream_t *s, float **part);   // the statistics scratch of a launch (lumahip_encode.hip)
+void stats_fold(lumahip_ctx *c, unsigned nframes, float *stats, hipStream_t s);
 int decode_impl(lumahip_ctx *c, const SrcPlanes &p, float sc, const DstFrames &f, const DecodeLaunch &o);
 int rb_table_for(lumahip_ctx *c, float sc, hipStream_t s, const float **tab);   // built on s the first time a preScaling is seen
 int array_launch(lumahip_ctx *c, const float *d_in, float *d_out, size_t n, unsigned ch, bool quant);
@@ -409,6 +424,18 @@ typedef void (*enc_kernel_t)(const lh::EncArgs);
 typedef void (*dec_kernel_t)(const lh::DecArgs);
 enc_kernel_t pick_enc_f16(int cs, bool sub, int vw, int mode);
 dec_kernel_t pick_dec_f16(int cs, bool sub, int vw, bool gl, bool yt, bool rb);
+
+// ---- lumahip_transcode.hip
+struct TranscodeLaunch {
+    hipStream_t stream;
+    bool lanes = false;   // as EncodeLaunch::lanes
+};
+// source planes under the context's source quantizer and src_sc -> destination planes under its quantizer and dst_sc
+int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
+                   float *stats, const TranscodeLaunch &o);
+typedef void (*trans_kernel_t)(const lh::TransArgs);
+// the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
+int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

@@ -67,10 +67,15 @@ int block_threads_for(const lumahip_ctx *c, size_t lds, bool few_waves, bool val
 // {1, 2, 4, 8, 20, 50 frames} x {Lu'v', YCbCr} x {encode, decode} with every setting interleaved in one process
 // (tools/bench/launch_rules_sweep.py, profiles/r03_launch_rules.txt: before / after tables).  lumahip_tune "grid_enc" / "grid_dec"
 // (absolute) and "blocks_per_cu" (per CU, both directions) are measurement overrides.
-int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers, int ycbcr)
+int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers, int ycbcr, bool transcode)
 {
     int per_cu = c->blocks_per_cu > 0 ? c->blocks_per_cu : 2048 / threads;
     const bool rule = c->blocks_per_cu == 0;
+    // The transcode kernels (k_transcode; dir 0, ycbcr: either side is YCbCr) are a family of their own with 6 B per pixel of
+    // traffic and both directions' arithmetic.  Their rule STARTS FROM the encode kernels' below (3 workgroups of 256 threads per
+    // CU for the Lu'v' pairs, 12 / 18 of 512 for the YCbCr ones) and has NOT been chosen by a same-box A/B yet: `transcode` marks
+    // the launches such a measurement would move.
+    (void)transcode;
     // The 4:2:0 16-bit decode kernels write 12 of their 15 bytes per pixel, and fewer concurrent writers suit the memory
     // system better than the default 8 workgroups of 256 threads per CU: 5 per CU on long launches (20 x 4K: 455 us against
     // 483; 8K x4 and longer likewise), 6 per CU on medium ones (1080p x8 ... x50, 4K x2 ... x8, 8K x1 ... x2: 2-5 % faster

@@ -1,8 +1,8 @@
-// lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / lh::k_decode, luma_kernels.hpp) a launch takes.
+// lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / lh::k_decode / lh::k_transcode, luma_kernels.hpp) a launch takes.
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
-// export them as pick_enc_f16 / pick_dec_f16.  Included by those four units only.
+// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_trans<4> / pick_trans<2>.  Included by those five units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -91,6 +91,33 @@ static dec_kernel_t pick_dec(int cs, bool sub, int vw, bool gl, bool disp, bool 
         if constexpr (!OUT16)
             return sub ? pick_dec_cs<OUT16, CS_PACK, true>(vw, gl, disp, yt, rb) : pick_dec_cs<OUT16, CS_PACK, false>(vw, gl, disp, yt, rb);
         break;
+    }
+    return nullptr;
+}
+
+// The transcode kernels (lh::k_transcode): source colour space / subsampling, target colour space / subsampling, the target's
+// search mode -- Lu'v': LUT_THRESH_LDS or LUT_LINKEY_LDS, YCbCr: 5 = the composite records.  nullptr: outside the supported set.
+// VW a template parameter so that, like the pickers above, only the unit that names it (lumahip_transcode.hip) compiles the kernels
+template <int VW, int CSD, bool SUBD>
+static trans_kernel_t pick_trans_src(int cse, bool sube, int mode)
+{
+    using namespace lh;
+    if (cse == CS_LUV && mode == LUT_THRESH_LDS)
+        return sube ? k_transcode<CSD, SUBD, CS_LUV, true, VW, 3> : k_transcode<CSD, SUBD, CS_LUV, false, VW, 3>;
+    if (cse == CS_LUV && mode == LUT_LINKEY_LDS)
+        return sube ? k_transcode<CSD, SUBD, CS_LUV, true, VW, 7> : k_transcode<CSD, SUBD, CS_LUV, false, VW, 7>;
+    if (cse == CS_YCBCR && mode == 5)
+        return sube ? k_transcode<CSD, SUBD, CS_YCBCR, true, VW, 5> : k_transcode<CSD, SUBD, CS_YCBCR, false, VW, 5>;
+    return nullptr;
+}
+
+template <int VW>
+static trans_kernel_t pick_trans(int csd, bool subd, int cse, bool sube, int mode)
+{
+    using namespace lh;
+    switch (csd) {
+    case CS_LUV: return subd ? pick_trans_src<VW, CS_LUV, true>(cse, sube, mode) : pick_trans_src<VW, CS_LUV, false>(cse, sube, mode);
+    case CS_YCBCR: return subd ? pick_trans_src<VW, CS_YCBCR, true>(cse, sube, mode) : pick_trans_src<VW, CS_YCBCR, false>(cse, sube, mode);
     }
     return nullptr;
 }
