@@ -40,7 +40,8 @@ extern "C" {
  *   5, later additions that change no existing symbol (detect them with dlsym): the binary16 frame calls
  *     lumahip_encode_frames_device_f16 / _planar_f16, lumahip_decode_frames_device_f16 / _planar_f16,
  *     lumahip_encode_frame_host_f16, lumahip_decode_frame_host_f16 and the probe lumahip_f16_narrow_probe_device; the transcode
- *     calls lumahip_set_source_quantizer, lumahip_transcode_frames_device, lumahip_transcode_frame_host.
+ *     calls lumahip_set_source_quantizer, lumahip_transcode_frames_device, lumahip_transcode_frame_host; the distortion calls
+ *     lumahip_distortion_frames_device / _planar / _f16 / _planar_f16 and lumahip_distortion_frame_host.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -371,6 +372,48 @@ int lumahip_transcode_frames_device(lumahip_ctx *ctx, const unsigned char *const
 int lumahip_transcode_frame_host(lumahip_ctx *ctx, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile,
                                  float src_sc, unsigned w, unsigned h, unsigned char *const dst_planes[3], const int dst_stride[3],
                                  int dst_profile, float dst_sc, float *mean_lum);
+
+/* Distortion: how far GIVEN code planes -- what came back from the VP9 decoder -- are from the planes the source frames went in
+ * as, measured in the stream's own code domain and in the launch that would have encoded them; no scratch planes, no second
+ * pass.  For every sample position of every plane, e is the unsigned sample lumahip_encode_frames_device would store there for
+ * that frame, sc and profile under the context's quantizer (exactly as stored at the profile's sample width: 8-bit profiles keep
+ * the stored byte), and g the unsigned sample present in the given plane, read as the decoder reads it (one byte, or two bytes
+ * little-endian; not clamped to the table size).  Per frame f and plane p the call delivers four uint64_t at
+ * out_dev[(f*3 + p)*4 + 0..3]:
+ *     sse = sum (e-g)^2,   sad = sum |e-g|,   max_abs = max |e-g|,   n_differ = #{e != g}
+ * over the plane's samples only (w x h for plane 0 and 4:4:4 chroma, (w/2) x (h/2) for 4:2:0 chroma; row padding and the gaps
+ * between frames are never read).  out_dev is zero-initialised by the call.  All arithmetic is integer: the words are the same
+ * from run to run whatever the launch shape.  sse is the numerator of a PU-PSNR-style measure: 10 log10(peak^2 n / sse) with
+ * peak the largest code of the plane.
+ * The arguments are those of the matching encode call, except that the planes are read only and out_dev (required, 8-byte
+ * aligned, 12 * nframes words, sharing no byte with the frames or the given planes) takes the place of stats_dev.  The _f16
+ * forms follow the binary16 encode calls above (alignment rules, exact widening).  Asynchronous on the context's stream, never
+ * waits on the host; takes part in unordered sections like the encode calls; the launch shape honours lumahip_tune "grid_enc",
+ * "lane_grid_enc", "block" and "blocks_per_cu".  The kernel is chosen from the arguments alone: YCbCr float frames take the
+ * per-pixel kernel with the composite records; YCbCr binary16 frames the half-input table whenever
+ * lumahip_ycbcr_half_table_host accepts (sc, maxLum) and lumahip_tune("half_table") is not 0, without a feedback word; the
+ * results are the same either way.  All four colour spaces, all four profiles.
+ * Errors, all before anything is launched (out_dev is then untouched): LUMAHIP_ERR_STATE without a quantizer; LUMAHIP_ERR_ARG
+ * for odd sizes, bad strides, a null or misaligned out_dev or one that overlaps an input; LUMAHIP_ERR_UNSUPPORTED unless the
+ * search records are in LDS (lumahip_quantizer_info search mode 3 or 7; never after lumahip_tune "force_literal").
+ * The host form takes one float frame (LumaFrame layout) and the given planes in host memory, uploads them, runs one launch,
+ * downloads the 12 words into `out` and returns synchronously. */
+int lumahip_distortion_frames_device(lumahip_ctx *ctx, const float *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                     unsigned h, float sc, int profile, const unsigned char *const planes_dev[3], const int stride[3],
+                                     const size_t plane_frame_stride[3], uint64_t *out_dev);
+int lumahip_distortion_frames_device_planar(lumahip_ctx *ctx, const float *const rgb_planes_dev[3], size_t frame_stride,
+                                            unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                            const unsigned char *const planes_dev[3], const int stride[3],
+                                            const size_t plane_frame_stride[3], uint64_t *out_dev);
+int lumahip_distortion_frames_device_f16(lumahip_ctx *ctx, const uint16_t *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                         unsigned h, float sc, int profile, const unsigned char *const planes_dev[3],
+                                         const int stride[3], const size_t plane_frame_stride[3], uint64_t *out_dev);
+int lumahip_distortion_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t *const rgb_planes_dev[3], size_t frame_stride,
+                                                unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                                const unsigned char *const planes_dev[3], const int stride[3],
+                                                const size_t plane_frame_stride[3], uint64_t *out_dev);
+int lumahip_distortion_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                  const unsigned char *const planes[3], const int stride[3], uint64_t out[12]);
 
 /* Unordered section.  Frames -- and therefore batches of frames -- are independent in this path (the quantizer is
  * read-only state, src/luma_quantizer.cpp:215-264,267-482 keep nothing between frames), so a caller with several batches to

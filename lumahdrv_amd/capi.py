@@ -38,6 +38,8 @@ SYMBOLS = [
     "lumahip_encode_frames_device_f16", "lumahip_encode_frames_device_planar_f16", "lumahip_decode_frames_device_f16",
     "lumahip_decode_frames_device_planar_f16", "lumahip_encode_frame_host_f16", "lumahip_decode_frame_host_f16", "lumahip_f16_narrow_probe_device",
     "lumahip_set_source_quantizer", "lumahip_transcode_frames_device", "lumahip_transcode_frame_host",
+    "lumahip_distortion_frames_device", "lumahip_distortion_frames_device_planar", "lumahip_distortion_frames_device_f16",
+    "lumahip_distortion_frames_device_planar_f16", "lumahip_distortion_frame_host",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -74,7 +76,7 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 # device code + launch geometry + compiler flags (NOT the host plumbing: lumahip_core / _host / _pool / _multi, lumahip_internal.hpp)
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
-                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip")
+                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip")
 
 
 def kernel_source_sha() -> str:
@@ -168,6 +170,11 @@ def lib():
     L.lumahip_set_source_quantizer.argtypes = [vp, i, u, i, u, f, f, vp, sz]
     L.lumahip_transcode_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, vp]
     L.lumahip_transcode_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, C.POINTER(f)]
+    L.lumahip_distortion_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
+    L.lumahip_distortion_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
+    L.lumahip_distortion_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
+    L.lumahip_distortion_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
+    L.lumahip_distortion_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, vp]
     L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_host_register.argtypes = [vp, vp, sz]
@@ -392,6 +399,16 @@ def thresh_lookup(ix, v: np.ndarray) -> np.ndarray:
     return ((ix["rec"][k] + low) >> np.uint32(ix["shift"])).astype(np.int64)
 
 
+def code_psnr(sse, nsamples, peak) -> float:
+    """PSNR in the code domain from a sum of squared code differences (Context.distortion_*): 10 log10(peak^2 * nsamples / sse),
+    `peak` the largest code of the plane (2**bitdepth - 1); infinity for identical planes"""
+    if nsamples <= 0 or peak <= 0:
+        raise ValueError("code_psnr needs nsamples > 0 and peak > 0")
+    if int(sse) == 0:
+        return float("inf")
+    return 10.0 * float(np.log10(float(peak) * float(peak) * float(nsamples) / float(sse)))
+
+
 def _arr3(ctype, vals):
     return (ctype * 3)(*vals)
 
@@ -515,6 +532,18 @@ class Context:
                                                       _arr3(C.c_int, st), dst_profile, dst_sc, C.byref(mean) if want_mean else None))
         return out, st, (float(mean.value) if want_mean else None)
 
+    def distortion_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2) -> np.ndarray:
+        """rgb: (3,h,w) float32; planes: the given code planes as three (rows, stride) uint8 arrays.  Returns a (3, 4) uint64 array:
+        per plane {sse, sad, max_abs, n_differ} of the planes encode_frame would write against the given ones"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        _, h, w = rgb.shape
+        planes = [np.ascontiguousarray(p) for p in planes]
+        out = np.zeros((3, 4), dtype=np.uint64)
+        self._chk(self.L.lumahip_distortion_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
+                                                       _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
+                                                       out.ctypes.data))
+        return out
+
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
         mean_lum), equal to encode_frame of the same frame widened to float32."""
@@ -614,6 +643,33 @@ class Context:
                                                          _arr3(C.c_size_t, src_plane_frame_strides), src_profile, src_sc, nframes, w, h,
                                                          _arr3(C.c_void_p, dst_plane_ptrs), _arr3(C.c_int, dst_strides),
                                                          _arr3(C.c_size_t, dst_plane_frame_strides), dst_profile, dst_sc, stats_ptr))
+
+    # distortion of given planes against the frames' own encode: out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ}
+    # as uint64 (zeroed by the call); the arguments are those of the matching encode call
+    def distortion_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides,
+                                 out_ptr):
+        self._chk(self.L.lumahip_distortion_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                          _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                          _arr3(C.c_size_t, plane_frame_strides), out_ptr))
+
+    def distortion_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                        plane_frame_strides, out_ptr):
+        self._chk(self.L.lumahip_distortion_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
+                                                                 sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                                 _arr3(C.c_size_t, plane_frame_strides), out_ptr))
+
+    def distortion_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                     plane_frame_strides, out_ptr):
+        self._chk(self.L.lumahip_distortion_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                              _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                              _arr3(C.c_size_t, plane_frame_strides), out_ptr))
+
+    def distortion_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                            plane_frame_strides, out_ptr):
+        self._chk(self.L.lumahip_distortion_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
+                                                                     w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
+                                                                     _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
+                                                                     out_ptr))
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

@@ -536,28 +536,26 @@ LH_DEV bool enc_transform(EncUnit<VW> &u, const EncArgs &a, const K &k, float (&
     return general;
 }
 
-// quantize + subsample + pack + store one transformed unit
-template <int CS, bool SUB, int VW, int LM, typename LutPtr, typename IdxPtr>
-LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const float (&c1)[2 * VW],
-                     const float (&c2)[2 * VW], const EncArgs &a, LutPtr lut, IdxPtr idx)
+// The codes of one transformed unit: quantize + subsample, stated once for every kernel that needs them.  Each row of codes is
+// handed to `out` the moment it exists -- out.template row<N>(pl, r, codes): the N codes of plane pl that sit in row r of the
+// unit (r = 0 for 4:2:0 chroma, whose unit is one row of VW / 2 samples) -- so a consumer that stores (EncStoreUnit, below) keeps
+// plane 0 one row (VW searches in flight) at a time: that keeps the live register set small enough for 6 waves per SIMD.
+template <int CS, bool SUB, int VW, int LM, typename LutPtr, typename IdxPtr, typename Out>
+LH_DEV void enc_codes(const float (&c0)[2 * VW], const float (&c1)[2 * VW], const float (&c2)[2 * VW], const QuantDev &q, LutPtr lut, IdxPtr idx,
+                      Out &out)
 {
     constexpr bool LUT_ALL = (CS == CS_RGB || CS == CS_XYZ);  // planes 1,2 also go through the LUT
-    const float maxC = a.q.maxC;
-    // plane 0, one row (VW searches in flight) at a time: keeps the live register set small enough for
-    // 6 waves per SIMD
-    {
-        unsigned char *d = a.dst[0] + (size_t)f * a.dst_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] +
-                           (size_t)ux * VW * a.bps;
+    const float maxC = q.maxC;
+    // plane 0
 #pragma unroll
-        for (int r = 0; r < 2; r++) {
-            float v[VW];
-            int row[VW];
+    for (int r = 0; r < 2; r++) {
+        float v[VW];
+        int row[VW];
 #pragma unroll
-            for (int i = 0; i < VW; i++)
-                v[i] = c0[r * VW + i];
-            quantize_lut<LM, VW, CS == CS_LUV>(v, row, lut, idx, a.q);  // Lu'v': Y is >= 1e-4 or NaN
-            store_samples<VW>(d + (size_t)r * a.stride[0], row, a.bps, a.aligned);
-        }
+        for (int i = 0; i < VW; i++)
+            v[i] = c0[r * VW + i];
+        quantize_lut<LM, VW, CS == CS_LUV>(v, row, lut, idx, q);  // Lu'v': Y is >= 1e-4 or NaN
+        out.template row<VW>(0, r, row);
     }
 
     // planes 1, 2
@@ -578,8 +576,8 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
                 a1[qd] *= 0.25f;
                 a2[qd] *= 0.25f;
             }
-            quantize_lut<LM, NQ>(a1, k1, lut, idx, a.q);
-            quantize_lut<LM, NQ>(a2, k2, lut, idx, a.q);
+            quantize_lut<LM, NQ>(a1, k1, lut, idx, q);
+            quantize_lut<LM, NQ>(a2, k2, lut, idx, q);
         } else {
             const float qc = 0.25f * maxC;
 #pragma unroll
@@ -589,15 +587,13 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
                 k2[qd] = quantize_color_sum4<CS == CS_LUV>(a2[qd], maxC, qc);
             }
         }
-        store_samples<NQ>(a.dst[1] + (size_t)f * a.dst_frame_stride[1] + (size_t)uy * a.stride[1] +
-                              (size_t)ux * NQ * a.bps, k1, a.bps, a.aligned);
-        store_samples<NQ>(a.dst[2] + (size_t)f * a.dst_frame_stride[2] + (size_t)uy * a.stride[2] +
-                              (size_t)ux * NQ * a.bps, k2, a.bps, a.aligned);
+        out.template row<NQ>(1, 0, k1);
+        out.template row<NQ>(2, 0, k2);
     } else {
         int k1[2 * VW], k2[2 * VW];
         if constexpr (LUT_ALL) {
-            quantize_lut<LM, 2 * VW>(c1, k1, lut, idx, a.q);
-            quantize_lut<LM, 2 * VW>(c2, k2, lut, idx, a.q);
+            quantize_lut<LM, 2 * VW>(c1, k1, lut, idx, q);
+            quantize_lut<LM, 2 * VW>(c2, k2, lut, idx, q);
         } else {
 #pragma unroll
             for (int j = 0; j < 2 * VW; j++) {
@@ -607,18 +603,39 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
         }
 #pragma unroll
         for (int pl = 1; pl < 3; pl++) {
-            unsigned char *d = a.dst[pl] + (size_t)f * a.dst_frame_stride[pl] + (size_t)(2 * uy) * a.stride[pl] +
-                               (size_t)ux * VW * a.bps;
             int row[VW];
 #pragma unroll
             for (int r = 0; r < 2; r++) {
 #pragma unroll
                 for (int i = 0; i < VW; i++)
                     row[i] = (pl == 1) ? k1[r * VW + i] : k2[r * VW + i];
-                store_samples<VW>(d + (size_t)r * a.stride[pl], row, a.bps, a.aligned);
+                out.template row<VW>(pl, r, row);
             }
         }
     }
+}
+
+// "store a unit": pack the rows enc_codes hands over into unit (ux, uy) of frame f of the planes of `a`
+template <bool SUB>
+struct EncStoreUnit {
+    const EncArgs &a;
+    int f, ux, uy;
+    template <int N>
+    LH_DEVS void row(int pl, int r, const int (&codes)[N]) const
+    {
+        const int y0 = (SUB && pl) ? uy : 2 * uy;   // first plane row of the unit
+        unsigned char *d = a.dst[pl] + (size_t)f * a.dst_frame_stride[pl] + (size_t)y0 * a.stride[pl] + (size_t)ux * N * a.bps;
+        store_samples<N>(d + (size_t)r * a.stride[pl], codes, a.bps, a.aligned);
+    }
+};
+
+// quantize + subsample + pack + store one transformed unit
+template <int CS, bool SUB, int VW, int LM, typename LutPtr, typename IdxPtr>
+LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const float (&c1)[2 * VW],
+                     const float (&c2)[2 * VW], const EncArgs &a, LutPtr lut, IdxPtr idx)
+{
+    const EncStoreUnit<SUB> out{a, f, ux, uy};
+    enc_codes<CS, SUB, VW, LM>(c0, c1, c2, a.q, lut, idx, out);
 }
 
 template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
@@ -1456,6 +1473,160 @@ __global__ __launch_bounds__(256) void k_transcode_channel0(const TransChan0Args
         b = div_ieee(b, a.sc_src);
         xform_fwd<CSE>(r * a.sc_dst, g * a.sc_dst, b * a.sc_dst, ke, c0, c1, c2);
         a.out[i] = c0;
+    }
+}
+
+// ---- DISTORTION -------------------------------------------------------------------------------------
+// How far GIVEN code planes are from the planes k_encode would write for the same frames: per frame and plane the integer sums
+// {sum (e-g)^2, sum |e-g|, max |e-g|, #(e != g)} over the plane's samples, e = the sample k_encode stores (masked to the profile's
+// sample width exactly as store_samples packs it), g = the sample that is there, as the decoder reads it.  k_encode up to the
+// codes (enc_load, enc_transform, enc_codes: same decomposition, persistent loop and pipeline); instead of "pack and store" the
+// consumer below takes the difference.  Reads 12 + 3 B per pixel (6 + 3 from binary16 frames), writes 12 words per frame.
+// The given samples are the decode kernels' own prefetch (dec_issue: load_samples' vector loads without the unpack; rows they
+// cannot take go through load_samples itself, later): issued right behind the next unit's pixel loads, one iteration ahead, and
+// unpacked row by row where the codes are compared -- the wait for the pixels (loads complete in order) leaves them in flight.
+// Accumulation: 64 bits per lane for the two sums (one squared difference of 16-bit samples fills 32); a workgroup's frame index
+// is uniform, so when it changes (and once at the end) its lanes meet in 12 words of LDS and ONE thread per word adds (max:
+// maxes) it into out[frame * 12 + .] -- one 64-bit integer atomic per workgroup, frame and word (thousands of waves on one
+// address is what profiles/r03_hostfed_trace.txt records).  Integers throughout: the result does not depend on the
+// launch shape or on the order of arrival.
+struct DistArgs {
+    EncArgs e;       // q (the composite records for LM 5 / 6), g, src, frame_stride, sc, half of the frames; dst / stride / bps unused
+    DecArgs d;       // the given planes: src, stride, src_frame_stride, bps, aligned; g (the same geometry as e.g)
+    uint64_t *out;   // [nframes][3 planes][sse, sad, max_abs, n_differ], zeroed before the launch
+};
+
+struct DistAcc {
+    uint64_t sse[3], sad[3];
+    uint32_t mx[3], nd[3];   // (a lane's share of one frame is far below 2^32 samples)
+    int frame;
+    LH_DEVS void reset()
+    {
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            sse[p] = sad[p] = 0;
+            mx[p] = nd[p] = 0;
+        }
+    }
+};
+
+// the consumer of enc_codes that measures: each row handed over against the same row of the given unit, unpacked from the
+// prefetched words `g` only now (rows the vector loads could not take are loaded here, byte by byte, as dec_finish does)
+template <bool SUB, int VW>
+struct DistMeasureUnit {
+    const DecRaw<SUB, VW> &g;
+    const DecArgs &d;
+    DistAcc &acc;
+    int mask;   // 0xffff / 0xff: what store_samples keeps of a code
+    template <int N>
+    LH_DEVS void row(int pl, int r, const int (&codes)[N]) const
+    {
+        int given[N];
+        if (d.aligned) {
+            unpack_raw<N>(pl == 0 ? g.y[r] : pl == 1 ? g.c1[r] : g.c2[r], given, d.bps);
+        } else {
+            const int y0 = (SUB && pl) ? g.uy : 2 * g.uy;   // first plane row of the unit
+            load_samples<N>(d.src[pl] + (size_t)g.f * d.src_frame_stride[pl] + (size_t)(y0 + r) * d.stride[pl] + (size_t)g.ux * N * d.bps, given,
+                            d.bps, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            const int df = (codes[i] & mask) - given[i];
+            const uint32_t ad = (uint32_t)(df < 0 ? -df : df);   // <= 65535: ad * ad fits 32 bits
+            acc.sse[pl] += (uint64_t)(ad * ad);
+            acc.sad[pl] += ad;
+            acc.mx[pl] = ad > acc.mx[pl] ? ad : acc.mx[pl];
+            acc.nd[pl] += ad != 0;
+        }
+    }
+};
+
+// Every thread of the workgroup calls this at the same point (the frame index is workgroup-uniform).  s_acc: 12 zeroed words of
+// LDS in which the lanes that saw a difference meet (LDS atomics; a flush happens once per workgroup and frame, not per unit),
+// then one thread per word hands it to out[frame * 12 + .] and clears it
+LH_DEV void dist_flush(DistAcc &acc, unsigned long long *s_acc, uint64_t *out)
+{
+    if (acc.frame >= 0) {
+#pragma unroll
+        for (int p = 0; p < 3; p++)
+            if (acc.nd[p] != 0) {
+                atomicAdd(&s_acc[4 * p + 0], (unsigned long long)acc.sse[p]);
+                atomicAdd(&s_acc[4 * p + 1], (unsigned long long)acc.sad[p]);
+                atomicMax(&s_acc[4 * p + 2], (unsigned long long)acc.mx[p]);
+                atomicAdd(&s_acc[4 * p + 3], (unsigned long long)acc.nd[p]);
+            }
+        __syncthreads();
+        if (threadIdx.x < 12) {
+            const unsigned long long v = s_acc[threadIdx.x];
+            s_acc[threadIdx.x] = 0;
+            unsigned long long *dst = reinterpret_cast<unsigned long long *>(out) + (size_t)acc.frame * 12 + threadIdx.x;
+            if (v != 0) {
+                if ((threadIdx.x & 3) == 2)
+                    atomicMax(dst, v);
+                else
+                    atomicAdd(dst, v);
+            }
+        }
+        __syncthreads();
+    }
+    acc.reset();
+}
+
+// LM: 3 / 7 (the luminance records in LDS), 5 (YCbCr: the composite records), 6 (5 + the half-input table; binary16 frames).
+// Register budget: four waves per SIMD for every variant -- the accumulators (18 registers) and the given words in flight (up to
+// 8) do not fit the 80 registers of the light k_encode variants, and the launch rules run three 256-thread workgroups per CU anyway.
+template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void k_distortion(const DistArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(LM == 3 || LM == 7 || ((LM == 5 || LM == 6) && CS == CS_YCBCR), "search records in LDS; the composite records belong to YCbCr");
+    constexpr bool HALF = (LM == 6);
+    __shared__ unsigned long long s_acc[12];
+    if (threadIdx.x < 12)
+        s_acc[threadIdx.x] = 0;   // (stage_tables synchronises)
+    constexpr int WHAT = STAGE_REC | (CS == CS_YCBCR ? (HALF ? STAGE_POWFN | STAGE_HALF : STAGE_POWF) : 0);
+    stage_tables<WHAT>(smem, a.e.q, a.e.half);
+
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + lds_table_offset<WHAT>());
+    const float *s_half = reinterpret_cast<const float *>(smem + lds_table_offset<WHAT>() + lds_rec_bytes(a.e.q));  // LM == 6
+    using PowTab = typename std::conditional<HALF, PowfTables, PowfTablesWide>::type;
+    const XformConstT<PowTab> k = make_xform_const<CS, PowTab>(a.e.sc, a.e.q.Lmax, reinterpret_cast<const PowTab *>(smem));
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+    const int mask = a.d.bps == 2 ? 0xffff : 0xff;
+
+    DistAcc acc;
+    acc.frame = -1;
+    acc.reset();
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    st.frame = -1;
+    st.sum = st.mn = st.mx = 0.0f;
+
+    // k_encode's loop; the given words of a unit travel with its pixels.  One flush site: the iteration past the last tile sees
+    // "frame" -2, flushes and leaves.
+    EncUnit<VW> u;
+    DecRaw<SUB, VW> given;
+    enc_load<VW, IN16>(u, a.e, blockIdx.x, tx, ty, NW);
+    dec_issue<SUB, VW>(given, a.d, blockIdx.x, tx, ty, NW);
+    for (int t = blockIdx.x;; t += G) {
+        const bool done = t >= a.e.g.totalTiles;        // workgroup-uniform, as the frame index is
+        const int f = done ? -2 : t / a.e.g.tilesPerFrame;
+        if (f != acc.frame) {
+            dist_flush(acc, s_acc, a.out);
+            acc.frame = f;
+        }
+        if (done)
+            break;
+        if (u.valid) {
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CS, VW, LM == 5 || LM == 6, HALF, false>(u, a.e, k, c0, c1, c2, st, s_half);
+            const DistMeasureUnit<SUB, VW> out{given, a.d, acc, mask};
+            enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+        }
+        enc_load<VW, IN16>(u, a.e, t + G, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.d, t + G, tx, ty, NW);
     }
 }
 

@@ -1058,6 +1058,44 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
     return LUMAHIP_OK;
 }
 
+// One float frame and given planes in host memory -> the 12 distortion words (lumahip_distortion.hip), synchronously
+extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                             const unsigned char *const planes[3], const int stride[3], uint64_t out[12])
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!rgb || !planes || !stride || !out)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    int rc = check_geom(c, w, h, profile, c->q.cs);
+    if (rc)
+        return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    PlaneLayout L;
+    plane_layout(L, w, h, profile, stride);
+    const int p = bad_plane(L, planes, stride);
+    if (p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
+    const size_t nfl = (size_t)3 * w * h;
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
+        (rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)) ||
+        (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, 12 * sizeof(uint64_t))))
+        return rc;
+    unsigned char *dp[3];
+    device_planes(dp, c->d_planes, L, stride);
+    if ((rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))
+        return rc;
+    for (int k = 0; k < 3; k++)
+        if ((rc = plane_h2d(c, dp, planes, stride, L, k, 0, h, c->stream)))
+            return rc;
+    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->d_arr);
+    const unsigned char *cdp[3] = {dp[0], dp[1], dp[2]};
+    if ((rc = distortion_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, {cdp, stride, NO_PFS, profile}, d_out,
+                              {c->stream, false})))
+        return rc;
+    return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(d_out), 24, c->stream);   // (12 words; synchronises the stream)
+}
+
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the
 // caller's halves go up as they are (no round-trip test, unlike the half upload above) and the decoded halves come down as the
 // kernel wrote them.

@@ -6,7 +6,7 @@
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which k_encode / k_decode / k_transcode instantiation a launch takes: pick_enc<IN16> / pick_dec<OUT16> /
-//                       pick_trans<VW>, included by the five kernel units below and by nothing else
+//                       pick_trans<VW> / pick_dist<IN16>, included by the seven kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
 //                       tables next to the kernel that builds them
@@ -14,6 +14,8 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_transcode.hip  pick_trans (every k_transcode), the transcode dispatch and its two entry points
+//   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<false> / pick_dist<true> (every k_distortion), the distortion
+//                       dispatch and the _device entry points
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -409,6 +411,26 @@ hipStream_t launch_stream(lumahip_ctx *c, hipStream_t s, bool lanes);   // s, or
 void plane_dims(unsigned w, unsigned h, int profile, int p, int &rows, int &row_bytes);
 // the code planes' strides against f's geometry and, with `overlap_test`, that no two colour planes of f overlap
 int check_layout(lumahip_ctx *c, const SrcFrames &f, bool overlap_test, const int stride[3], const size_t pfs[3], int profile);
+// bytes plane p covers over the batch: up to the end of its last row in the last frame
+static inline size_t plane_extent(unsigned w, unsigned h, int profile, int p, int stride, size_t pfs, unsigned nframes)
+{
+    int rows, row_bytes;
+    plane_dims(w, h, profile, p, rows, row_bytes);
+    return (size_t)(nframes - 1) * pfs + (size_t)(rows - 1) * (size_t)stride + (size_t)row_bytes;
+}
+// every base, stride and frame stride of these planes takes the vector accesses of VW pixels per thread and row
+template <typename B>
+static inline bool planes_aligned(const CodePlanesT<B> &p, int vw)
+{
+    const bool sub = (p.profile == 0 || p.profile == 2);
+    const int bps = p.profile > 1 ? 2 : 1;
+    for (int k = 0; k < 3; k++) {
+        const size_t ub = (size_t)((k && sub) ? vw / 2 : vw) * bps;
+        if (!is_aligned(p.planes[k], ub) || (p.stride[k] % (int)ub) != 0 || (p.pfs[k] % ub) != 0)
+            return false;
+    }
+    return true;
+}
 
 // ---- lumahip_encode.hip / lumahip_decode.hip
 int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const DstPlanes &p, float *stats, const EncodeLaunch &o);
@@ -436,6 +458,17 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
 typedef void (*trans_kernel_t)(const lh::TransArgs);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
+
+// ---- lumahip_distortion.hip / lumahip_distortion_f16.hip: pick_dist<false> / pick_dist<true> of lumahip_pick.hpp (every
+// k_distortion; the binary16-frame ones compile side by side with the float ones and are exported as pick_dist_f16)
+struct DistortionLaunch {
+    hipStream_t stream;
+    bool lanes = false;   // as EncodeLaunch::lanes
+};
+// the frames of f under the context's quantizer and sc against the given planes: 12 words per frame at out_dev
+int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out_dev, const DistortionLaunch &o);
+typedef void (*dist_kernel_t)(const lh::DistArgs);
+dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

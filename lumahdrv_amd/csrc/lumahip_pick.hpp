@@ -2,7 +2,8 @@
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
-// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_trans<4> / pick_trans<2>.  Included by those five units only.
+// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_trans<4> / pick_trans<2>; lumahip_distortion.hip /
+// lumahip_distortion_f16.hip take pick_dist<false> / pick_dist<true>.  Included by those seven units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -118,6 +119,41 @@ static trans_kernel_t pick_trans(int csd, bool subd, int cse, bool sube, int mod
     switch (csd) {
     case CS_LUV: return subd ? pick_trans_src<VW, CS_LUV, true>(cse, sube, mode) : pick_trans_src<VW, CS_LUV, false>(cse, sube, mode);
     case CS_YCBCR: return subd ? pick_trans_src<VW, CS_YCBCR, true>(cse, sube, mode) : pick_trans_src<VW, CS_YCBCR, false>(cse, sube, mode);
+    }
+    return nullptr;
+}
+
+// The distortion kernels (lh::k_distortion): search records in LDS only.  mode: LUT_THRESH_LDS or LUT_LINKEY_LDS, or for YCbCr
+// 5 = the composite records (float frames), 6 = the same + the half-input table (binary16 frames).  nullptr: outside that set.
+template <bool IN16, int CS, bool SUB>
+static dist_kernel_t pick_dist_cs(int vw, int mode)
+{
+    using namespace lh;
+    if constexpr (CS == CS_YCBCR) {
+        if constexpr (!IN16) {
+            if (mode == 5)
+                return vw == 4 ? k_distortion<CS, SUB, 4, 5> : k_distortion<CS, SUB, 2, 5>;
+        } else {
+            if (mode == 6)
+                return vw == 4 ? k_distortion<CS, SUB, 4, 6, true> : k_distortion<CS, SUB, 2, 6, true>;
+        }
+    }
+    if (mode == LUT_THRESH_LDS)
+        return vw == 4 ? k_distortion<CS, SUB, 4, 3, IN16> : k_distortion<CS, SUB, 2, 3, IN16>;
+    if (mode == LUT_LINKEY_LDS)
+        return vw == 4 ? k_distortion<CS, SUB, 4, 7, IN16> : k_distortion<CS, SUB, 2, 7, IN16>;
+    return nullptr;
+}
+
+template <bool IN16>
+static dist_kernel_t pick_dist(int cs, bool sub, int vw, int mode)
+{
+    using namespace lh;
+    switch (cs) {
+    case CS_LUV: return sub ? pick_dist_cs<IN16, CS_LUV, true>(vw, mode) : pick_dist_cs<IN16, CS_LUV, false>(vw, mode);
+    case CS_RGB: return sub ? pick_dist_cs<IN16, CS_RGB, true>(vw, mode) : pick_dist_cs<IN16, CS_RGB, false>(vw, mode);
+    case CS_YCBCR: return sub ? pick_dist_cs<IN16, CS_YCBCR, true>(vw, mode) : pick_dist_cs<IN16, CS_YCBCR, false>(vw, mode);
+    case CS_XYZ: return sub ? pick_dist_cs<IN16, CS_XYZ, true>(vw, mode) : pick_dist_cs<IN16, CS_XYZ, false>(vw, mode);
     }
     return nullptr;
 }

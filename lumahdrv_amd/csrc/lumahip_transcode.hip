@@ -11,28 +11,6 @@ namespace lhost {
 
 static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-// bytes plane p covers over the batch: up to the end of its last row in the last frame
-static size_t plane_extent(unsigned w, unsigned h, int profile, int p, int stride, size_t pfs, unsigned nframes)
-{
-    int rows, row_bytes;
-    plane_dims(w, h, profile, p, rows, row_bytes);
-    return (size_t)(nframes - 1) * pfs + (size_t)(rows - 1) * (size_t)stride + (size_t)row_bytes;
-}
-
-// every base, stride and frame stride of these planes takes the vector accesses of VW pixels per thread and row
-template <typename B>
-static bool planes_aligned(const CodePlanesT<B> &p, int vw)
-{
-    const bool sub = (p.profile == 0 || p.profile == 2);
-    const int bps = p.profile > 1 ? 2 : 1;
-    for (int k = 0; k < 3; k++) {
-        const size_t ub = (size_t)((k && sub) ? vw / 2 : vw) * bps;
-        if (!is_aligned(p.planes[k], ub) || (p.stride[k] % (int)ub) != 0 || (p.pfs[k] % ub) != 0)
-            return false;
-    }
-    return true;
-}
-
 int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
                    float *stats, const TranscodeLaunch &o)
 {
