@@ -41,7 +41,8 @@ extern "C" {
  *     lumahip_encode_frames_device_f16 / _planar_f16, lumahip_decode_frames_device_f16 / _planar_f16,
  *     lumahip_encode_frame_host_f16, lumahip_decode_frame_host_f16 and the probe lumahip_f16_narrow_probe_device; the transcode
  *     calls lumahip_set_source_quantizer, lumahip_transcode_frames_device, lumahip_transcode_frame_host; the distortion calls
- *     lumahip_distortion_frames_device / _planar / _f16 / _planar_f16 and lumahip_distortion_frame_host.
+ *     lumahip_distortion_frames_device / _planar / _f16 / _planar_f16 and lumahip_distortion_frame_host; the transcode
+ *     distortion calls lumahip_transcode_distortion_frames_device and lumahip_transcode_distortion_frame_host.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -414,6 +415,37 @@ int lumahip_distortion_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t
                                                 const size_t plane_frame_stride[3], uint64_t *out_dev);
 int lumahip_distortion_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                   const unsigned char *const planes[3], const int stride[3], uint64_t out[12]);
+
+/* Transcode distortion: how far GIVEN code planes in the target's format -- what came back from the VP9 decoder on the delivery
+ * side -- are from the planes the SOURCE stream's planes transcode to, in the launch that would have transcoded them; no float
+ * frames (a transcoding pipeline never has them), no scratch planes, no second pass.  For every sample position of every plane, e
+ * is the unsigned sample lumahip_transcode_frames_device would store there for the same source planes, source quantizer, context
+ * quantizer, profiles and preScalings, masked to dst_profile's sample width (8-bit profiles keep the stored byte), and g the
+ * unsigned sample present in the given plane, read as the decoder reads it (one byte, or two bytes little-endian; not clamped).
+ * Per frame f and plane p the call delivers four uint64_t at out_dev[(f*3 + p)*4 + 0..3]:
+ *     sse = sum (e-g)^2,   sad = sum |e-g|,   max_abs = max |e-g|,   n_differ = #{e != g}
+ * over the plane's samples only (row padding and the gaps between frames are never read).  out_dev (required, 8-byte aligned,
+ * 12 * nframes words) is zero-initialised by the call.  All arithmetic is integer: the words are bit-reproducible whatever the
+ * launch shape.  Both plane sets are read only, so -- unlike the transcode call's -- the source and the given planes may overlap
+ * each other; out_dev may share no byte with either.  Asynchronous on the context's stream, never waits on the host; takes part
+ * in unordered sections like the transcode call; the launch shape honours lumahip_tune "grid_enc", "lane_grid_enc", "block" and
+ * "blocks_per_cu" (a "block" beyond the 512 threads the kernels with YCbCr on either side are compiled for is clamped to 512).
+ * The supported set is exactly lumahip_transcode_frames_device's (Lu'v' and YCbCr on either side, all 16 profile pairs, source
+ * tables of at most 12 bits in LDS, target search mode 3 or 7 or the composite records, never after lumahip_tune
+ * "force_literal"), with the 12 accumulator words counted into the LDS of a workgroup beside both sides' tables.
+ * Errors, all before anything is launched (out_dev is then untouched): LUMAHIP_ERR_STATE unless both quantizers are set;
+ * LUMAHIP_ERR_UNSUPPORTED outside the supported set; LUMAHIP_ERR_ARG for odd sizes, bad strides, a null or misaligned out_dev
+ * or one that shares a byte with either plane set.
+ * The host form uploads both plane sets, runs one launch, downloads the 12 words into `out` and returns synchronously. */
+int lumahip_transcode_distortion_frames_device(lumahip_ctx *ctx, const unsigned char *const src_planes_dev[3], const int src_stride[3],
+                                               const size_t src_plane_frame_stride[3], int src_profile, float src_sc, unsigned nframes,
+                                               unsigned w, unsigned h, const unsigned char *const given_planes_dev[3],
+                                               const int given_stride[3], const size_t given_plane_frame_stride[3], int dst_profile,
+                                               float dst_sc, uint64_t *out_dev);
+int lumahip_transcode_distortion_frame_host(lumahip_ctx *ctx, const unsigned char *const src_planes[3], const int src_stride[3],
+                                            int src_profile, float src_sc, unsigned w, unsigned h,
+                                            const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
+                                            float dst_sc, uint64_t out[12]);
 
 /* Unordered section.  Frames -- and therefore batches of frames -- are independent in this path (the quantizer is
  * read-only state, src/luma_quantizer.cpp:215-264,267-482 keep nothing between frames), so a caller with several batches to

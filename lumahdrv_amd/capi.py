@@ -40,6 +40,7 @@ SYMBOLS = [
     "lumahip_set_source_quantizer", "lumahip_transcode_frames_device", "lumahip_transcode_frame_host",
     "lumahip_distortion_frames_device", "lumahip_distortion_frames_device_planar", "lumahip_distortion_frames_device_f16",
     "lumahip_distortion_frames_device_planar_f16", "lumahip_distortion_frame_host",
+    "lumahip_transcode_distortion_frames_device", "lumahip_transcode_distortion_frame_host",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -76,7 +77,8 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 # device code + launch geometry + compiler flags (NOT the host plumbing: lumahip_core / _host / _pool / _multi, lumahip_internal.hpp)
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
-                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip")
+                  "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
+                  "lumahip_transcode_distortion.hip")
 
 
 def kernel_source_sha() -> str:
@@ -175,6 +177,8 @@ def lib():
     L.lumahip_distortion_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
     L.lumahip_distortion_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
     L.lumahip_distortion_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, vp]
+    L.lumahip_transcode_distortion_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, vp]
+    L.lumahip_transcode_distortion_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, vp]
     L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_host_register.argtypes = [vp, vp, sz]
@@ -544,6 +548,19 @@ class Context:
                                                        out.ctypes.data))
         return out
 
+    def transcode_distortion_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
+                                   dst_profile=2) -> np.ndarray:
+        """planes: code planes under the source quantizer; given_planes: code planes in the target's format, three (rows, stride)
+        uint8 arrays each.  Returns a (3, 4) uint64 array: per plane {sse, sad, max_abs, n_differ} of the planes transcode_frame
+        would write against the given ones, in one fused launch"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        given_planes = [np.ascontiguousarray(p) for p in given_planes]
+        out = np.zeros((3, 4), dtype=np.uint64)
+        self._chk(self.L.lumahip_transcode_distortion_frame_host(
+            self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
+            _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc, out.ctypes.data))
+        return out
+
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
         mean_lum), equal to encode_frame of the same frame widened to float32."""
@@ -670,6 +687,15 @@ class Context:
                                                                      w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
                                                                      _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
                                                                      out_ptr))
+
+    # distortion of given planes against the source planes' own transcode: the arguments are transcode_frames_device's, the
+    # target-side planes are read, out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ} as uint64 (zeroed by the call)
+    def transcode_distortion_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
+                                           given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, out_ptr):
+        self._chk(self.L.lumahip_transcode_distortion_frames_device(
+            self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides), _arr3(C.c_size_t, src_plane_frame_strides), src_profile,
+            src_sc, nframes, w, h, _arr3(C.c_void_p, given_plane_ptrs), _arr3(C.c_int, given_strides),
+            _arr3(C.c_size_t, given_plane_frame_strides), dst_profile, dst_sc, out_ptr))
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

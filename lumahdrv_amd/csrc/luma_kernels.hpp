@@ -1630,6 +1630,100 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
     }
 }
 
+// ---- TRANSCODE DISTORTION ---------------------------------------------------------------------------
+// How far GIVEN code planes are from the planes k_transcode would write for the same source planes: the fourth combination of the
+// parts above -- k_transcode's front end (dec_load, dec_values, enc_transform under the two quantizers, stage_tables<WHAT_D, WHAT_E>,
+// without statistics) with k_distortion's consumer (enc_codes into DistMeasureUnit, dist_flush at the one flush site).  Reads 3 + 3 B
+// per pixel (profile 2 on both sides), writes 12 words per frame; no scratch planes, no float frame.
+// The given samples travel as k_distortion's do (DecRaw through dec_issue, under the TARGET's subsampling and sample size): their
+// loads are issued right behind the next unit's source loads, one iteration ahead and never behind the search, and are unpacked
+// row by row where the codes are compared.
+struct TransDistArgs {
+    DecArgs d;       // the source planes, as TransArgs::d
+    EncArgs e;       // the target quantizer: q (the composite records for LM == 5), g, sc; nothing is stored
+    DecArgs g;       // the given planes: src, stride, src_frame_stride, bps, aligned; g (the same geometry as d.g)
+    uint64_t *out;   // [nframes][3 planes][sse, sad, max_abs, n_differ], zeroed before the launch
+};
+
+// Threads per workgroup the variants are register-allocated for: the pairs with YCbCr on either side already sit at 111 - 128
+// registers in k_transcode and the measuring consumer adds the accumulators (18) and the given words (up to 8), which does not fit
+// the 64 registers of a 1024-thread workgroup without scratch -- they are bounded at 512 threads (128 registers), which is what the
+// launch rules give them anyway (block_threads_for, valu_bound), and the dispatcher clamps forced or table-driven larger
+// workgroups to it.  The Lu'v' -> Lu'v' pairs keep 1024: their tables alone decide the workgroup size.
+template <int CSD, int CSE>
+struct TransDistBound {
+    static constexpr int value = (CSD == CS_YCBCR || CSE == CS_YCBCR) ? 512 : 1024;
+};
+
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode_distortion(const TransDistArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(CSD == CS_LUV || CSD == CS_YCBCR, "source colour spaces: Lu'v' and YCbCr");
+    static_assert((CSE == CS_LUV && (LM == 3 || LM == 7)) || (CSE == CS_YCBCR && LM == 5), "target: Lu'v' with records in LDS, YCbCr with the composite records");
+    constexpr bool YD = CSD == CS_YCBCR, YE = CSE == CS_YCBCR;
+    __shared__ unsigned long long s_acc[12];
+    if (threadIdx.x < 12)
+        s_acc[threadIdx.x] = 0;   // (stage_tables synchronises)
+    constexpr int WHAT_D = STAGE_LUT | (YD ? STAGE_POWF | STAGE_YT | STAGE_CT : STAGE_UV);
+    constexpr int WHAT_E = STAGE_REC | (YE ? STAGE_POWF : 0);
+    stage_tables<WHAT_D, WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<WHAT_D | WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+
+    DistAcc acc;
+    acc.frame = -1;
+    acc.reset();
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    st.frame = -1;
+    st.sum = st.mn = st.mx = 0.0f;
+
+    // k_transcode's loop with k_distortion's flush site: the iteration past the last tile sees "frame" -2, flushes and leaves
+    DecUnit<SUBD, VW> cur, nxt;
+    DecRaw<SUBE, VW> given;
+    dec_load<SUBD, VW>(cur, a.d, blockIdx.x, tx, ty, NW);
+    dec_issue<SUBE, VW>(given, a.g, blockIdx.x, tx, ty, NW);
+    for (int t = blockIdx.x;; t += G) {
+        const bool done = t >= a.d.g.totalTiles;        // workgroup-uniform, as the frame index is
+        const int f = done ? -2 : t / a.d.g.tilesPerFrame;
+        if (f != acc.frame) {
+            dist_flush(acc, s_acc, a.out);
+            acc.frame = f;
+        }
+        if (done)
+            break;
+        if (cur.valid) {
+            EncUnit<VW> u;
+            if constexpr (YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    dec_values<CSD, SUBD, VW, false, true, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+                else
+                    dec_values<CSD, SUBD, VW, false, true, false>(cur, a.d, kd, s_lut, s_uv, u.in);
+            } else {
+                dec_values<CSD, SUBD, VW, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, YE, false, false>(u, a.e, ke, c0, c1, c2, st);
+            const DistMeasureUnit<SUBE, VW> out{given, a.g, acc, mask};
+            enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+        }
+        dec_load<SUBD, VW>(nxt, a.d, t + G, tx, ty, NW);
+        dec_issue<SUBE, VW>(given, a.g, t + G, tx, ty, NW);
+        cur = nxt;
+    }
+}
+
 // ---- stand-alone colour transform (LumaQuantizer::transformColorSpace as public API) ---------------
 struct XfArgs {
     float *buf;

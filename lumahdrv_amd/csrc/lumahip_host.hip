@@ -1096,6 +1096,52 @@ extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, u
     return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(d_out), 24, c->stream);   // (12 words; synchronises the stream)
 }
 
+// Source planes and given planes in host memory -> the 12 words of the transcode distortion (lumahip_transcode_distortion.hip),
+// synchronously; the context's plane staging holds both sets
+extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                       int src_profile, float src_sc, unsigned w, unsigned h,
+                                                       const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
+                                                       float dst_sc, uint64_t out[12])
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!src_planes || !src_stride || !given_planes || !given_stride || !out)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    int rc = check_geom(c, w, h, dst_profile, c->q.cs);
+    if (rc)
+        return rc;
+    if (src_profile < 0 || src_profile > 3)
+        return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src_profile);
+    if (!c->src.have)
+        return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    PlaneLayout Ls, Lg;
+    plane_layout(Ls, w, h, src_profile, src_stride);
+    plane_layout(Lg, w, h, dst_profile, given_stride);
+    int p = bad_plane(Ls, src_planes, src_stride);
+    if (p >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "source plane %d: null or stride %d < row bytes %d", p, src_stride[p], Ls.row_bytes[p]);
+    if ((p = bad_plane(Lg, given_planes, given_stride)) >= 0)
+        return fail(c, LUMAHIP_ERR_ARG, "given plane %d: null or stride %d < row bytes %d", p, given_stride[p], Lg.row_bytes[p]);
+    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, Ls.total + Lg.total)) ||
+        (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, 12 * sizeof(uint64_t))))
+        return rc;
+    unsigned char *sp[3], *gp[3];
+    device_planes(sp, c->d_planes, Ls, src_stride);
+    device_planes(gp, c->d_planes + Ls.total, Lg, given_stride);
+    for (int k = 0; k < 3; k++)
+        if ((rc = plane_h2d(c, sp, src_planes, src_stride, Ls, k, 0, h, c->stream)) ||
+            (rc = plane_h2d(c, gp, given_planes, given_stride, Lg, k, 0, h, c->stream)))
+            return rc;
+    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->d_arr);
+    const unsigned char *csp[3] = {sp[0], sp[1], sp[2]}, *cgp[3] = {gp[0], gp[1], gp[2]};
+    if ((rc = transcode_distortion_impl(c, {csp, src_stride, NO_PFS, src_profile}, src_sc, 1, w, h, {cgp, given_stride, NO_PFS, dst_profile}, dst_sc,
+                                        d_out, {c->stream, false})))
+        return rc;
+    return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(d_out), 24, c->stream);   // (12 words; synchronises the stream)
+}
+
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the
 // caller's halves go up as they are (no round-trip test, unlike the half upload above) and the decoded halves come down as the
 // kernel wrote them.

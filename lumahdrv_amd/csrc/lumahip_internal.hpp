@@ -14,6 +14,7 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_transcode.hip  pick_trans (every k_transcode), the transcode dispatch and its two entry points
+//   lumahip_transcode_distortion.hip  pick_transdist (every k_transcode_distortion), its dispatch and device entry point
 //   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<false> / pick_dist<true> (every k_distortion), the distortion
 //                       dispatch and the _device entry points
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
@@ -456,6 +457,22 @@ struct TranscodeLaunch {
 int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
                    float *stats, const TranscodeLaunch &o);
 typedef void (*trans_kernel_t)(const lh::TransArgs);
+// What transcode_plan decides for a launch over (source planes, target-side planes): the kernel's key (colour spaces,
+// subsamplings, vector width, the target's search mode as pick_trans takes it), the launch shape and the kernel arguments of both
+// sides except the target-side plane pointers, which the two callers fill in (written: EncArgs::dst; read: a DecArgs of their own)
+struct TranscodePlan {
+    int csd, cse, kmode, vw, threads, grid;
+    bool subd, sube, any_y;
+    size_t lds;      // dynamic LDS of the launch (the measuring kernels' 12 words are static and counted in the budget)
+    lh::DecArgs d;   // q, g, src, stride, src_frame_stride, sc, bps, aligned of the source planes
+    lh::EncArgs e;   // q (the composite records for kmode 5), g, sc, bps, aligned of the target side
+};
+// measure = false: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one), out is ignored;
+// measure = true: tgt are the given planes of lumahip_transcode_distortion_frames_device (read only: any overlap with the source
+// is fine), out its 12 * nframes words (non-null, 8-byte aligned, sharing no byte with either plane set), the workgroup is
+// clamped to the measuring kernels' launch bound.  Every error is raised here, before anything of the launch is queued.
+int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
+                   bool measure, const uint64_t *out, hipStream_t stream, TranscodePlan &p);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 
@@ -469,6 +486,12 @@ struct DistortionLaunch {
 int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out_dev, const DistortionLaunch &o);
 typedef void (*dist_kernel_t)(const lh::DistArgs);
 dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode);
+
+// ---- lumahip_transcode_distortion.hip: pick_transdist of lumahip_pick.hpp (every k_transcode_distortion)
+// the source planes' transcode (transcode_impl's planes, never written) against the given planes: 12 words per frame at out_dev
+int transcode_distortion_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
+                              float dst_sc, uint64_t *out_dev, const TranscodeLaunch &o);
+typedef void (*transdist_kernel_t)(const lh::TransDistArgs);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

@@ -2,8 +2,9 @@
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
-// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_trans<4> / pick_trans<2>; lumahip_distortion.hip /
-// lumahip_distortion_f16.hip take pick_dist<false> / pick_dist<true>.  Included by those seven units only.
+// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_trans<4> / pick_trans<2>;
+// lumahip_transcode_distortion.hip takes pick_transdist<4> / pick_transdist<2>; lumahip_distortion.hip /
+// lumahip_distortion_f16.hip take pick_dist<false> / pick_dist<true>.  Included by those eight units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -123,7 +124,37 @@ static trans_kernel_t pick_trans(int csd, bool subd, int cse, bool sube, int mod
     return nullptr;
 }
 
-// The distortion kernels (lh::k_distortion): search records in LDS only.  mode: LUT_THRESH_LDS or LUT_LINKEY_LDS, or for YCbCr
+// The transcode distortion kernels (lh::k_transcode_distortion): pick_trans's keys, kernel for kernel; named by
+// lumahip_transcode_distortion.hip only.  *bound: the threads per workgroup the kernel is compiled for (lh::TransDistBound)
+template <int VW, int CSD, bool SUBD>
+static transdist_kernel_t pick_transdist_src(int cse, bool sube, int mode, int *bound)
+{
+    using namespace lh;
+    if (cse == CS_LUV && (mode == LUT_THRESH_LDS || mode == LUT_LINKEY_LDS)) {
+        *bound = TransDistBound<CSD, CS_LUV>::value;
+        if (mode == LUT_THRESH_LDS)
+            return sube ? k_transcode_distortion<CSD, SUBD, CS_LUV, true, VW, 3> : k_transcode_distortion<CSD, SUBD, CS_LUV, false, VW, 3>;
+        return sube ? k_transcode_distortion<CSD, SUBD, CS_LUV, true, VW, 7> : k_transcode_distortion<CSD, SUBD, CS_LUV, false, VW, 7>;
+    }
+    if (cse == CS_YCBCR && mode == 5) {
+        *bound = TransDistBound<CSD, CS_YCBCR>::value;
+        return sube ? k_transcode_distortion<CSD, SUBD, CS_YCBCR, true, VW, 5> : k_transcode_distortion<CSD, SUBD, CS_YCBCR, false, VW, 5>;
+    }
+    return nullptr;
+}
+
+template <int VW>
+static transdist_kernel_t pick_transdist(int csd, bool subd, int cse, bool sube, int mode, int *bound)
+{
+    using namespace lh;
+    switch (csd) {
+    case CS_LUV: return subd ? pick_transdist_src<VW, CS_LUV, true>(cse, sube, mode, bound) : pick_transdist_src<VW, CS_LUV, false>(cse, sube, mode, bound);
+    case CS_YCBCR: return subd ? pick_transdist_src<VW, CS_YCBCR, true>(cse, sube, mode, bound) : pick_transdist_src<VW, CS_YCBCR, false>(cse, sube, mode, bound);
+    }
+    return nullptr;
+}
+
+// The distortion kernels (lh::k_distortion): search records in LDS only. mode: LUT_THRESH_LDS or LUT_LINKEY_LDS, or for YCbCr
 // 5 = the composite records (float frames), 6 = the same + the half-input table (binary16 frames).  nullptr: outside that set.
 template <bool IN16, int CS, bool SUB>
 static dist_kernel_t pick_dist_cs(int vw, int mode)

@@ -11,16 +11,22 @@ namespace lhost {
 
 static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
-int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
-                   float *stats, const TranscodeLaunch &o)
+static bool ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
+
+// The one place that decides what a launch over (source planes, target-side planes) may be and how it runs: argument checks, the
+// supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (tgt = the planes it
+// writes; out = nullptr) and for the transcode distortion (measure: tgt = the given planes it reads, out = its words).
+int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
+                   bool measure, const uint64_t *out, hipStream_t stream, TranscodePlan &p)
 {
-    if (!src.planes || !src.stride || !src.pfs || !dst.planes || !dst.stride || !dst.pfs || nframes == 0)
+    const char *const what = measure ? "transcode distortion" : "transcode";
+    if (!src.planes || !src.stride || !src.pfs || !tgt.planes || !tgt.stride || !tgt.pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    for (int p = 0; p < 3; p++)
-        if (!src.planes[p] || !dst.planes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "null plane %d", p);
+    for (int k = 0; k < 3; k++)
+        if (!src.planes[k] || !tgt.planes[k])
+            return fail(c, LUMAHIP_ERR_ARG, "null plane %d", k);
     const int cse = c->q.cs;
-    int rc = check_geom(c, w, h, dst.profile, cse);
+    int rc = check_geom(c, w, h, tgt.profile, cse);
     if (rc)
         return rc;
     if (src.profile < 0 || src.profile > 3)
@@ -30,30 +36,40 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
         return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
     const int csd = sq.q.cs;
     const SrcFrames geom{{nullptr, nullptr, nullptr}, Elem::F32, 0, nframes, w, h};   // (the code planes' checks read the geometry only)
-    if ((rc = check_layout(c, geom, false, src.stride, src.pfs, src.profile)) || (rc = check_layout(c, geom, false, dst.stride, dst.pfs, dst.profile)))
+    if ((rc = check_layout(c, geom, false, src.stride, src.pfs, src.profile)) || (rc = check_layout(c, geom, false, tgt.stride, tgt.pfs, tgt.profile)))
         return rc;
-    // no source plane may share a byte with a destination plane over the batch (the extent test of the rotating decode's buffers)
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-            const uintptr_t bi = (uintptr_t)src.planes[i], bj = (uintptr_t)dst.planes[j];
-            const size_t ei = plane_extent(w, h, src.profile, i, src.stride[i], src.pfs[i], nframes);
-            const size_t ej = plane_extent(w, h, dst.profile, j, dst.stride[j], dst.pfs[j], nframes);
-            if (bi < bj + ej && bj < bi + ei)
-                return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
+    if (!measure) {
+        // no source plane may share a byte with a destination plane over the batch (the extent test of the rotating decode's buffers)
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                if (ranges_overlap((uintptr_t)src.planes[i], plane_extent(w, h, src.profile, i, src.stride[i], src.pfs[i], nframes),
+                                   (uintptr_t)tgt.planes[j], plane_extent(w, h, tgt.profile, j, tgt.stride[j], tgt.pfs[j], nframes)))
+                    return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
+    } else {
+        // both plane sets are read only and may overlap each other; out_dev may not share a byte with anything the launch reads
+        if (!out || !is_aligned(out, 8))
+            return fail(c, LUMAHIP_ERR_ARG, "out_dev must be non-null and 8-byte aligned");
+        const size_t out_bytes = (size_t)nframes * 12 * sizeof(uint64_t);
+        for (int k = 0; k < 3; k++) {
+            if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)src.planes[k], plane_extent(w, h, src.profile, k, src.stride[k], src.pfs[k], nframes)))
+                return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps source plane %d", k);
+            if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)tgt.planes[k], plane_extent(w, h, tgt.profile, k, tgt.stride[k], tgt.pfs[k], nframes)))
+                return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps given plane %d", k);
         }
+    }
     // ---- the supported set; everything else is refused here, before anything is launched
     if ((csd != CS_LUV && csd != CS_YCBCR) || (cse != CS_LUV && cse != CS_YCBCR))
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "transcode: colour spaces Lu'v' and YCbCr only (source %d, target %d)", csd, cse);
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: colour spaces Lu'v' and YCbCr only (source %d, target %d)", what, csd, cse);
     if (sq.bitdepth > 12 || !sq.lut_in_lds)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "transcode: the source's luminance table must be staged in LDS (bit depth <= 12, got %u)", sq.bitdepth);
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the source's luminance table must be staged in LDS (bit depth <= 12, got %u)", what, sq.bitdepth);
     if (csd == CS_YCBCR && !sq.q.ytab)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "transcode: no y table for this YCbCr source (table values, LDS size or lumahip_tune \"ycbcr_tables\")");
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: no y table for this YCbCr source (table values, LDS size or lumahip_tune \"ycbcr_tables\")", what);
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_search_index(c, o.stream)))
+    if ((rc = ensure_search_index(c, stream)))
         return rc;
     const bool ycode = cse == CS_YCBCR;
     if (ycode ? !ycbcr_composite_ready(c) : (c->q.mode != LUT_THRESH_LDS && c->q.mode != LUT_LINKEY_LDS))
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "transcode: the target needs %s in LDS (search mode %d)",
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the target needs %s in LDS (search mode %d)", what,
                     ycode ? "the composite luma -> code records" : "its luminance records", c->q.mode);
     const QuantDev &qe = ycode ? c->q_y : c->q;
     const bool any_y = csd == CS_YCBCR || cse == CS_YCBCR;
@@ -61,45 +77,74 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     // [powf tables once][source: luminance table + u'v' table | + y table + two chroma-term tables][target: records]  (k_transcode)
     const size_t lds = (any_y ? sizeof(PowfTablesWide) : 0) + lut_lds_bytes(sq.q) + (csd == CS_YCBCR ? lut_lds_bytes(sq.q) + 2 * col : col) +
                        round16((size_t)qe.nbuckets * (qe.mode == LUT_LINKEY_LDS ? 8 : 4));
-    if (lds > LUMAHIP_LDS_PER_WORKGROUP)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "transcode: the tables of both sides take %zu bytes of LDS, a workgroup has %zu", lds, LUMAHIP_LDS_PER_WORKGROUP);
+    const size_t acc_lds = measure ? 128 : 0;   // the 12 words the waves of a measuring workgroup meet in
+    if (lds + acc_lds > LUMAHIP_LDS_PER_WORKGROUP)
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the tables of both sides take %zu bytes of LDS, a workgroup has %zu", what, lds + acc_lds,
+                    LUMAHIP_LDS_PER_WORKGROUP);
 
-    const bool subd = (src.profile == 0 || src.profile == 2), sube = (dst.profile == 0 || dst.profile == 2);
+    p.csd = csd;
+    p.cse = cse;
+    p.subd = (src.profile == 0 || src.profile == 2);
+    p.sube = (tgt.profile == 0 || tgt.profile == 2);
+    p.any_y = any_y;
+    p.kmode = ycode ? 5 : qe.mode;
+    p.lds = lds;
     // four pixels per thread and row when every base and stride of both sides allows the vector accesses, else two
-    const int vw = ((w % 4) == 0 && planes_aligned(src, 4) && planes_aligned(dst, 4)) ? 4 : 2;
+    p.vw = ((w % 4) == 0 && planes_aligned(src, 4) && planes_aligned(tgt, 4)) ? 4 : 2;
     const bool long_launch = (unsigned long long)w * h * nframes >= 60000000ull;   // as the encode dispatch
-    const int threads = block_threads_for(c, lds, long_launch && !any_y, any_y);
-    TransArgs a{};
-    if (!make_geom(a.d.g, w, h, vw, threads / 64, nframes))
+    p.threads = block_threads_for(c, lds, long_launch && !any_y, any_y);
+    // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
+    // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
+    const int bound = !measure ? 1024 : any_y ? TransDistBound<CS_YCBCR, CS_YCBCR>::value : TransDistBound<CS_LUV, CS_LUV>::value;
+    if (p.threads > bound)
+        p.threads = bound;
+    p.d = DecArgs{};
+    if (!make_geom(p.d.g, w, h, p.vw, p.threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
-    a.e.g = a.d.g;
-    a.d.q = sq.q;
-    a.e.q = qe;
-    a.e.q.cs = cse;
-    a.d.sc = src_sc;
-    a.e.sc = dst_sc;
-    a.d.bps = src.profile > 1 ? 2 : 1;
-    a.e.bps = dst.profile > 1 ? 2 : 1;
-    a.d.aligned = planes_aligned(src, vw) ? 1 : 0;
-    a.e.aligned = planes_aligned(dst, vw) ? 1 : 0;
-    for (int p = 0; p < 3; p++) {
-        a.d.src[p] = src.planes[p];
-        a.d.stride[p] = src.stride[p];
-        a.d.src_frame_stride[p] = src.pfs[p];
-        a.e.dst[p] = dst.planes[p];
-        a.e.stride[p] = dst.stride[p];
-        a.e.dst_frame_stride[p] = dst.pfs[p];
+    p.d.q = sq.q;
+    p.d.sc = src_sc;
+    p.d.bps = src.profile > 1 ? 2 : 1;
+    p.d.aligned = planes_aligned(src, p.vw) ? 1 : 0;
+    for (int k = 0; k < 3; k++) {
+        p.d.src[k] = src.planes[k];
+        p.d.stride[k] = src.stride[k];
+        p.d.src_frame_stride[k] = src.pfs[k];
     }
-    const trans_kernel_t kern = vw == 4 ? pick_trans<4>(csd, subd, cse, sube, ycode ? 5 : qe.mode) : pick_trans<2>(csd, subd, cse, sube, ycode ? 5 : qe.mode);
+    p.e = EncArgs{};
+    p.e.g = p.d.g;
+    p.e.q = qe;
+    p.e.q.cs = cse;
+    p.e.sc = dst_sc;
+    p.e.bps = tgt.profile > 1 ? 2 : 1;
+    p.e.aligned = planes_aligned(tgt, p.vw) ? 1 : 0;
+    p.grid = grid_for(c, p.threads, p.d.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
+    return LUMAHIP_OK;
+}
+
+int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
+                   float *stats, const TranscodeLaunch &o)
+{
+    TranscodePlan p;
+    int rc = transcode_plan(c, src, src_sc, nframes, w, h, {dst.planes, dst.stride, dst.pfs, dst.profile}, dst_sc, false, nullptr, o.stream, p);
+    if (rc)
+        return rc;
+    TransArgs a{};
+    a.d = p.d;
+    a.e = p.e;
+    for (int k = 0; k < 3; k++) {
+        a.e.dst[k] = dst.planes[k];
+        a.e.stride[k] = dst.stride[k];
+        a.e.dst_frame_stride[k] = dst.pfs[k];
+    }
+    const trans_kernel_t kern = p.vw == 4 ? pick_trans<4>(p.csd, p.subd, p.cse, p.sube, p.kmode) : pick_trans<2>(p.csd, p.subd, p.cse, p.sube, p.kmode);
     if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode kernel for colour spaces %d -> %d", csd, cse);
-    if (lds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int grid = grid_for(c, threads, a.d.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode kernel for colour spaces %d -> %d", p.csd, p.cse);
+    if (p.lds > 64 * 1024)
+        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     hipStream_t s = launch_stream(c, o.stream, o.lanes);
     if (stats && (rc = stats_begin(c, nframes, o.lanes, &s, &a.e.stats)))
         return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds, s, a);
     if (stats)
         stats_fold(c, nframes, stats, s);
     HIPCHK(c, hipGetLastError());
