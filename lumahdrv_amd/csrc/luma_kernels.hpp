@@ -437,9 +437,9 @@ LH_DEV void enc_load(EncUnit<VW> &u, const EncArgs &a, int t, int tx, int ty, in
     }
 }
 
-struct EncStats {
-    float sum, mn, mx;
-    int frame;
+struct EncStats {   // "no frame yet, nothing seen": what stats_flush leaves behind, too
+    float sum = 0.0f, mn = __builtin_inff(), mx = -__builtin_inff();
+    int frame = -1;
 };
 
 // Per-frame statistics: every wave adds its partial {sum, min, max} with three atomics.  Thousands of waves on ONE triple
@@ -638,34 +638,62 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
     enc_codes<CS, SUB, VW, LM>(c0, c1, c2, a.q, lut, idx, out);
 }
 
+// ---- THE KERNELS THAT END IN enc_codes ----------------------------------------------------------------
+// Two front ends produce a transformed unit (c0, c1, c2), two consumers take the codes enc_codes makes of it:
+//                                                        store (EncStoreUnit)   measure (DistMeasureUnit, dist_flush)
+//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion
+//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion
+//                   enc_transform
+// A kernel is its front end, its consumer and the persistent loop that orders their loads against each other; the loops differ on
+// purpose (stores before the next loads / the given words travelling along, one flush site) and stay written out.  Also written
+// out: the stage_tables calls and, in the plane-fed kernels, the LDS pointers, kd / ke and the per-unit dec_values / enc_transform
+// block -- behind a constructor or a helper they compile to other register allocations.
+
+// The tables of the frame front end for colour space CS and search mode LM (stage_tables' WHAT)
+template <int CS, int LM>
+constexpr int frame_front_what()
+{
+    return (LM == 0 ? STAGE_LUT : 0) | ((LM == 3 || LM == 5 || LM == 6 || LM == 7) ? STAGE_REC : 0) |
+           (CS == CS_YCBCR ? (LM == 6 ? STAGE_POWFN | STAGE_HALF : STAGE_POWF) : 0);
+}
+
+// Frames in: where stage_tables<WHAT>(smem, a.q, a.half) has put the tables of (CS, LM), and the constants enc_transform takes.
+// LM == 6 (HALF): the 768-byte powf tables, the LDS belongs to the half-input table at s_half
+template <int CS, int LM>
+struct FrameFront {
+    static_assert((LM != 5 && LM != 6) || CS == CS_YCBCR, "the composite records belong to the YCbCr kernels");
+    static constexpr bool HALF = (LM == 6);
+    static constexpr int WHAT = frame_front_what<CS, LM>();
+    using PowTab = typename std::conditional<HALF, PowfTables, PowfTablesWide>::type;
+    const float *s_lut;      // LM == 0
+    const uint32_t *s_rec;   // LM == 3, 5, 6, 7
+    const float *s_half;     // LM == 6
+    XformConstT<PowTab> k;
+    LH_DEVS FrameFront(unsigned char *smem, const EncArgs &a)
+        : s_lut(reinterpret_cast<const float *>(smem + lds_table_offset<WHAT>())),
+          s_rec(reinterpret_cast<const uint32_t *>(smem + lds_table_offset<WHAT>())),
+          s_half(reinterpret_cast<const float *>(smem + lds_table_offset<WHAT>() + lds_rec_bytes(a.q))),
+          k(make_xform_const<CS, PowTab>(a.sc, a.q.Lmax, reinterpret_cast<const PowTab *>(smem))) {}
+};
+
+// k_encode: every search mode (LM 0, 2, 4 too: the table or the records in global memory) and, with the half-input table, the
+// workgroup's vote on whether the frames hold binary16 values
 template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(EncWaves<CS, SUB, VW>::value))) void k_encode(const EncArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    static_assert((LM != 5 && LM != 6) || CS == CS_YCBCR, "the composite records belong to the YCbCr kernels");
     constexpr bool HALF = (LM == 6);
     __shared__ int s_votes[HALF ? 2 : 1];   // HALF: waves of this workgroup that had units / that left the table in every one
     if (HALF && threadIdx.x == 0)
         s_votes[0] = s_votes[HALF ? 1 : 0] = 0;   // (stage_tables synchronises)
-    constexpr int WHAT = (LM == 0 ? STAGE_LUT : 0) | ((LM == 3 || LM == 5 || LM == 6 || LM == 7) ? STAGE_REC : 0) |
-                         (CS == CS_YCBCR ? (HALF ? STAGE_POWFN | STAGE_HALF : STAGE_POWF) : 0);
-    stage_tables<WHAT>(smem, a.q, a.half);
-
-    const float *s_lut = reinterpret_cast<const float *>(smem + lds_table_offset<WHAT>());        // LM == 0
-    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + lds_table_offset<WHAT>());  // LM == 3, 5, 6
-    const float *s_half = reinterpret_cast<const float *>(smem + lds_table_offset<WHAT>() + lds_rec_bytes(a.q));  // LM == 6
-    using PowTab = typename std::conditional<HALF, PowfTables, PowfTablesWide>::type;
-    const XformConstT<PowTab> k = make_xform_const<CS, PowTab>(a.sc, a.q.Lmax, reinterpret_cast<const PowTab *>(smem));
+    stage_tables<FrameFront<CS, LM>::WHAT>(smem, a.q, a.half);
+    const FrameFront<CS, LM> fr(smem, a);
 
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int NW = blockDim.x >> 6;
     const int G = gridDim.x;
 
     EncStats st;
-    st.frame = -1;
-    st.sum = 0.0f;
-    st.mn = __builtin_inff();
-    st.mx = -__builtin_inff();
 
     // Per unit: transform, search / pack / store, THEN issue the next unit's loads (the current inputs are dead by then,
     // so both units share one set of registers); the other waves of the SIMD cover the load latency.  Issuing the loads
@@ -687,7 +715,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(EncWaves<C
         float c0[2 * VW], c1[2 * VW], c2[2 * VW];
         bool general = false;
         if (valid)
-            general = enc_transform<CS, VW, LM == 5 || LM == 6, HALF>(u, a, k, c0, c1, c2, st, s_half);
+            general = enc_transform<CS, VW, LM == 5 || LM == 6, HALF>(u, a, fr.k, c0, c1, c2, st, fr.s_half);
         if constexpr (HALF) {
             // a tile that overhangs the frame may leave this wave without a single pixel: such a unit is no evidence either way
             n_units += __builtin_amdgcn_ballot_w64(valid) != 0;
@@ -695,15 +723,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(EncWaves<C
         }
         if (valid) {
             if constexpr (LM == 6)
-                enc_emit<CS, SUB, VW, 5>(f, ux, uy, c0, c1, c2, a, s_lut, s_rec);
+                enc_emit<CS, SUB, VW, 5>(f, ux, uy, c0, c1, c2, a, fr.s_lut, fr.s_rec);
             else if constexpr (LM == 3 || LM == 5 || LM == 7)
-                enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, s_lut, s_rec);
+                enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, fr.s_lut, fr.s_rec);
             else if constexpr (LM == 4)
                 enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, a.q.lut, a.q.rec);
             else if constexpr (LM == 0)
-                enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, s_lut, s_rec);
+                enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, fr.s_lut, fr.s_rec);
             else
-                enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, a.q.lut, s_rec);
+                enc_emit<CS, SUB, VW, LM>(f, ux, uy, c0, c1, c2, a, a.q.lut, fr.s_rec);
         }
         enc_load<VW, IN16>(u, a, t + G, tx, ty, NW);
     }
@@ -1350,33 +1378,40 @@ __global__ __launch_bounds__(1024) void k_decode(const DecArgs a)
 // Code planes of one stream -> code planes of another, DEC then ENC of the head of this file without the float frame between
 // them: per unit, dec_load and dec_values under the source quantizer (`/ sc` of the source included), the floats handed to
 // enc_transform in registers (`* sc` of the target included: the division and the multiplication both stay, the planes are the
-// two-call result bit for bit), enc_emit under the target quantizer.  6 B per pixel instead of 30 (profile 2 -> profile 2).
+// two-call result bit for bit), enc_codes under the target quantizer.  6 B per pixel instead of 30 (profile 2 -> profile 2).
 // CSD / SUBD: the source's colour space and subsampling, CSE / SUBE: the target's -- independent; 4:4:4 -> 4:2:0 averages the
-// per-pixel chroma as enc_emit does, 4:2:0 -> 4:4:4 stores the replicated sample's code four times.
+// per-pixel chroma as enc_codes does, 4:2:0 -> 4:4:4 stores the replicated sample's code four times.
 // LM: the target's search mode: 3 or 7 (Lu'v': the luminance records in LDS), 5 (YCbCr: the composite records in LDS).
 // Source side: the luminance table in LDS, plus the u'v' table (Lu'v') or the y table and the two chroma-term tables (YCbCr);
 // red and blue are always computed (no per-stream red / blue tables, no feedback word: the launch is a function of the
 // arguments alone).  LDS: [powf tables, once, when either side is YCbCr][source tables][target records] (stage_tables<A, B>).
-// The loop is k_encode's: the next unit's sample loads are issued after the current unit's stores.
 struct TransArgs {
     DecArgs d;   // q, src, stride, src_frame_stride, sc, bps, aligned of the source planes; g (the same geometry as e.g)
     EncArgs e;   // q (the composite records for LM == 5), dst, stride, dst_frame_stride, sc, bps, aligned, stats of the target planes
 };
 
+// Code planes in: the supported pairs and what stage_tables<WHAT_D, WHAT_E> stages for the source's and the target's quantizer
+template <int CSD, int CSE, int LM>
+struct PlaneFront {
+    static_assert(CSD == CS_LUV || CSD == CS_YCBCR, "source colour spaces: Lu'v' and YCbCr");
+    static_assert((CSE == CS_LUV && (LM == 3 || LM == 7)) || (CSE == CS_YCBCR && LM == 5), "target: Lu'v' with records in LDS, YCbCr with the composite records");
+    static constexpr bool YD = CSD == CS_YCBCR, YE = CSE == CS_YCBCR;
+    static constexpr int WHAT_D = STAGE_LUT | (YD ? STAGE_POWF | STAGE_YT | STAGE_CT : STAGE_UV);
+    static constexpr int WHAT_E = STAGE_REC | (YE ? STAGE_POWF : 0);
+};
+
+// k_transcode: the statistics of the target planes (a.e.stats), and k_encode's loop -- the next unit's sample loads are issued
+// after the current unit's stores
 template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
 __global__ __launch_bounds__(1024) void k_transcode(const TransArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    static_assert(CSD == CS_LUV || CSD == CS_YCBCR, "source colour spaces: Lu'v' and YCbCr");
-    static_assert((CSE == CS_LUV && (LM == 3 || LM == 7)) || (CSE == CS_YCBCR && LM == 5), "target: Lu'v' with records in LDS, YCbCr with the composite records");
-    constexpr bool YD = CSD == CS_YCBCR, YE = CSE == CS_YCBCR;
-    constexpr int WHAT_D = STAGE_LUT | (YD ? STAGE_POWF | STAGE_YT | STAGE_CT : STAGE_UV);
-    constexpr int WHAT_E = STAGE_REC | (YE ? STAGE_POWF : 0);
-    stage_tables<WHAT_D, WHAT_E>(smem, a.d.q, a.e.q);
-    constexpr int off = lds_table_offset<WHAT_D | WHAT_E>();
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
     const float *s_lut = reinterpret_cast<const float *>(smem + off);
     const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
-    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<WHAT_D>(a.d.q));
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
     const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
     const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
     const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
@@ -1386,10 +1421,6 @@ __global__ __launch_bounds__(1024) void k_transcode(const TransArgs a)
     const int G = gridDim.x;
 
     EncStats st;
-    st.frame = -1;
-    st.sum = 0.0f;
-    st.mn = __builtin_inff();
-    st.mx = -__builtin_inff();
 
     DecUnit<SUBD, VW> cur, nxt;
     dec_load<SUBD, VW>(cur, a.d, blockIdx.x, tx, ty, NW);
@@ -1403,7 +1434,7 @@ __global__ __launch_bounds__(1024) void k_transcode(const TransArgs a)
         }
         if (cur.valid) {
             EncUnit<VW> u;
-            if constexpr (YD) {
+            if constexpr (Front::YD) {
                 // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
                 if (kd.sc_mode == 1)
                     dec_values<CSD, SUBD, VW, false, true, true>(cur, a.d, kd, s_lut, s_uv, u.in);
@@ -1413,8 +1444,8 @@ __global__ __launch_bounds__(1024) void k_transcode(const TransArgs a)
                 dec_values<CSD, SUBD, VW, true>(cur, a.d, kd, s_lut, s_uv, u.in);
             }
             float c0[2 * VW], c1[2 * VW], c2[2 * VW];
-            enc_transform<CSE, VW, YE, false, !YE>(u, a.e, ke, c0, c1, c2, st);
-            if constexpr (YE) {
+            enc_transform<CSE, VW, Front::YE, false, !Front::YE>(u, a.e, ke, c0, c1, c2, st);
+            if constexpr (Front::YE) {
                 // channel 0 is t = 219 y + 16 (ycbcr_fwd<., YCODE>); the statistics are about the luminance PQdec(t / 255), which
                 // only a launch that asks for them evaluates -- with the complete functions, whose bits the encode kernels' are
                 if (a.e.stats) {
@@ -1479,27 +1510,25 @@ __global__ __launch_bounds__(256) void k_transcode_channel0(const TransChan0Args
 // ---- DISTORTION -------------------------------------------------------------------------------------
 // How far GIVEN code planes are from the planes k_encode would write for the same frames: per frame and plane the integer sums
 // {sum (e-g)^2, sum |e-g|, max |e-g|, #(e != g)} over the plane's samples, e = the sample k_encode stores (masked to the profile's
-// sample width exactly as store_samples packs it), g = the sample that is there, as the decoder reads it.  k_encode up to the
-// codes (enc_load, enc_transform, enc_codes: same decomposition, persistent loop and pipeline); instead of "pack and store" the
-// consumer below takes the difference.  Reads 12 + 3 B per pixel (6 + 3 from binary16 frames), writes 12 words per frame.
+// sample width exactly as store_samples packs it), g = the sample that is there, as the decoder reads it.  Reads 12 + 3 B per pixel
+// (6 + 3 from binary16 frames), writes 12 words per frame.
 // The given samples are the decode kernels' own prefetch (dec_issue: load_samples' vector loads without the unpack; rows they
 // cannot take go through load_samples itself, later): issued right behind the next unit's pixel loads, one iteration ahead, and
 // unpacked row by row where the codes are compared -- the wait for the pixels (loads complete in order) leaves them in flight.
-// Accumulation: 64 bits per lane for the two sums (one squared difference of 16-bit samples fills 32); a workgroup's frame index
-// is uniform, so when it changes (and once at the end) its lanes meet in 12 words of LDS and ONE thread per word adds (max:
-// maxes) it into out[frame * 12 + .] -- one 64-bit integer atomic per workgroup, frame and word (thousands of waves on one
-// address is what profiles/r03_hostfed_trace.txt records).  Integers throughout: the result does not depend on the
-// launch shape or on the order of arrival.
+// Accumulation: 64 bits per lane for the two sums (one squared difference of 16-bit samples fills 32); one 64-bit integer atomic
+// per workgroup, frame and word reaches out[] (thousands of waves on one address is what profiles/r03_hostfed_trace.txt records).
+// Integers throughout: the result does not depend on the launch shape or on the order of arrival.
 struct DistArgs {
     EncArgs e;       // q (the composite records for LM 5 / 6), g, src, frame_stride, sc, half of the frames; dst / stride / bps unused
-    DecArgs d;       // the given planes: src, stride, src_frame_stride, bps, aligned; g (the same geometry as e.g)
+    DecArgs g;       // the given planes: src, stride, src_frame_stride, bps, aligned; g (the same geometry as e.g)
     uint64_t *out;   // [nframes][3 planes][sse, sad, max_abs, n_differ], zeroed before the launch
 };
 
 struct DistAcc {
     uint64_t sse[3], sad[3];
     uint32_t mx[3], nd[3];   // (a lane's share of one frame is far below 2^32 samples)
-    int frame;
+    int frame = -1;          // no frame yet
+    LH_DEVS DistAcc() { reset(); }
     LH_DEVS void reset()
     {
 #pragma unroll
@@ -1541,103 +1570,95 @@ struct DistMeasureUnit {
     }
 };
 
-// Every thread of the workgroup calls this at the same point (the frame index is workgroup-uniform).  s_acc: 12 zeroed words of
-// LDS in which the lanes that saw a difference meet (LDS atomics; a flush happens once per workgroup and frame, not per unit),
-// then one thread per word hands it to out[frame * 12 + .] and clears it
-LH_DEV void dist_flush(DistAcc &acc, unsigned long long *s_acc, uint64_t *out)
+// The 12 words of LDS in which the lanes of a measuring workgroup that saw a difference meet (LDS atomics), zeroed: called before
+// the front end's stage_tables, which synchronises.  Must stay LH_DEV: force-inlined, the array is the calling kernel's
+LH_DEV unsigned long long *dist_words()
 {
-    if (acc.frame >= 0) {
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-            if (acc.nd[p] != 0) {
-                atomicAdd(&s_acc[4 * p + 0], (unsigned long long)acc.sse[p]);
-                atomicAdd(&s_acc[4 * p + 1], (unsigned long long)acc.sad[p]);
-                atomicMax(&s_acc[4 * p + 2], (unsigned long long)acc.mx[p]);
-                atomicAdd(&s_acc[4 * p + 3], (unsigned long long)acc.nd[p]);
-            }
-        __syncthreads();
-        if (threadIdx.x < 12) {
-            const unsigned long long v = s_acc[threadIdx.x];
-            s_acc[threadIdx.x] = 0;
-            unsigned long long *dst = reinterpret_cast<unsigned long long *>(out) + (size_t)acc.frame * 12 + threadIdx.x;
-            if (v != 0) {
-                if ((threadIdx.x & 3) == 2)
-                    atomicMax(dst, v);
-                else
-                    atomicAdd(dst, v);
-            }
-        }
-        __syncthreads();
-    }
-    acc.reset();
+    __shared__ unsigned long long s_acc[12];
+    if (threadIdx.x < 12)
+        s_acc[threadIdx.x] = 0;
+    return s_acc;
 }
 
-// LM: 3 / 7 (the luminance records in LDS), 5 (YCbCr: the composite records), 6 (5 + the half-input table; binary16 frames).
+// The one flush site, at the top of every iteration of a measuring loop: f = the frame of the iteration's tile, or -2 past the last
+// tile (the loop then leaves).  Every thread of the workgroup calls it at the same point (the frame index is workgroup-uniform).
+// When the frame changes the lanes meet in s_acc, then one thread per word hands it to out[frame * 12 + .] and clears it -- a flush
+// happens once per workgroup and frame, not per unit
+LH_DEV void dist_flush(DistAcc &acc, unsigned long long *s_acc, int f, uint64_t *out)
+{
+    if (f != acc.frame) {
+        if (acc.frame >= 0) {
+#pragma unroll
+            for (int p = 0; p < 3; p++)
+                if (acc.nd[p] != 0) {
+                    atomicAdd(&s_acc[4 * p + 0], (unsigned long long)acc.sse[p]);
+                    atomicAdd(&s_acc[4 * p + 1], (unsigned long long)acc.sad[p]);
+                    atomicMax(&s_acc[4 * p + 2], (unsigned long long)acc.mx[p]);
+                    atomicAdd(&s_acc[4 * p + 3], (unsigned long long)acc.nd[p]);
+                }
+            __syncthreads();
+            if (threadIdx.x < 12) {
+                const unsigned long long v = s_acc[threadIdx.x];
+                s_acc[threadIdx.x] = 0;
+                unsigned long long *dst = reinterpret_cast<unsigned long long *>(out) + (size_t)acc.frame * 12 + threadIdx.x;
+                if (v != 0) {
+                    if ((threadIdx.x & 3) == 2)
+                        atomicMax(dst, v);
+                    else
+                        atomicAdd(dst, v);
+                }
+            }
+            __syncthreads();
+        }
+        acc.reset();
+        acc.frame = f;
+    }
+}
+
+// k_distortion: LM 3 / 7 (the luminance records in LDS), 5 (YCbCr: the composite records), 6 (5 + the half-input table; binary16
+// frames).  k_encode's loop; the given words of a unit travel with its pixels.
 // Register budget: four waves per SIMD for every variant -- the accumulators (18 registers) and the given words in flight (up to
 // 8) do not fit the 80 registers of the light k_encode variants, and the launch rules run three 256-thread workgroups per CU anyway.
 template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void k_distortion(const DistArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    static_assert(LM == 3 || LM == 7 || ((LM == 5 || LM == 6) && CS == CS_YCBCR), "search records in LDS; the composite records belong to YCbCr");
-    constexpr bool HALF = (LM == 6);
-    __shared__ unsigned long long s_acc[12];
-    if (threadIdx.x < 12)
-        s_acc[threadIdx.x] = 0;   // (stage_tables synchronises)
-    constexpr int WHAT = STAGE_REC | (CS == CS_YCBCR ? (HALF ? STAGE_POWFN | STAGE_HALF : STAGE_POWF) : 0);
-    stage_tables<WHAT>(smem, a.e.q, a.e.half);
-
-    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + lds_table_offset<WHAT>());
-    const float *s_half = reinterpret_cast<const float *>(smem + lds_table_offset<WHAT>() + lds_rec_bytes(a.e.q));  // LM == 6
-    using PowTab = typename std::conditional<HALF, PowfTables, PowfTablesWide>::type;
-    const XformConstT<PowTab> k = make_xform_const<CS, PowTab>(a.e.sc, a.e.q.Lmax, reinterpret_cast<const PowTab *>(smem));
+    static_assert(LM == 3 || LM == 7 || LM == 5 || LM == 6, "search records in LDS");
+    unsigned long long *const s_acc = dist_words();
+    stage_tables<FrameFront<CS, LM>::WHAT>(smem, a.e.q, a.e.half);
+    const FrameFront<CS, LM> fr(smem, a.e);
 
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int NW = blockDim.x >> 6;
     const int G = gridDim.x;
-    const int mask = a.d.bps == 2 ? 0xffff : 0xff;
 
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
     DistAcc acc;
-    acc.frame = -1;
-    acc.reset();
     EncStats st;   // (enc_transform's parameter; unused with STATS = false)
-    st.frame = -1;
-    st.sum = st.mn = st.mx = 0.0f;
-
-    // k_encode's loop; the given words of a unit travel with its pixels.  One flush site: the iteration past the last tile sees
-    // "frame" -2, flushes and leaves.
     EncUnit<VW> u;
     DecRaw<SUB, VW> given;
     enc_load<VW, IN16>(u, a.e, blockIdx.x, tx, ty, NW);
-    dec_issue<SUB, VW>(given, a.d, blockIdx.x, tx, ty, NW);
+    dec_issue<SUB, VW>(given, a.g, blockIdx.x, tx, ty, NW);
     for (int t = blockIdx.x;; t += G) {
         const bool done = t >= a.e.g.totalTiles;        // workgroup-uniform, as the frame index is
-        const int f = done ? -2 : t / a.e.g.tilesPerFrame;
-        if (f != acc.frame) {
-            dist_flush(acc, s_acc, a.out);
-            acc.frame = f;
-        }
+        dist_flush(acc, s_acc, done ? -2 : t / a.e.g.tilesPerFrame, a.out);
         if (done)
             break;
         if (u.valid) {
             float c0[2 * VW], c1[2 * VW], c2[2 * VW];
-            enc_transform<CS, VW, LM == 5 || LM == 6, HALF, false>(u, a.e, k, c0, c1, c2, st, s_half);
-            const DistMeasureUnit<SUB, VW> out{given, a.d, acc, mask};
-            enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+            enc_transform<CS, VW, LM == 5 || LM == 6, LM == 6, false>(u, a.e, fr.k, c0, c1, c2, st, fr.s_half);
+            const DistMeasureUnit<SUB, VW> out{given, a.g, acc, mask};
+            enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), fr.s_rec, out);   // (record searches: no table pointer)
         }
         enc_load<VW, IN16>(u, a.e, t + G, tx, ty, NW);
-        dec_issue<SUB, VW>(given, a.d, t + G, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t + G, tx, ty, NW);
     }
 }
 
 // ---- TRANSCODE DISTORTION ---------------------------------------------------------------------------
-// How far GIVEN code planes are from the planes k_transcode would write for the same source planes: the fourth combination of the
-// parts above -- k_transcode's front end (dec_load, dec_values, enc_transform under the two quantizers, stage_tables<WHAT_D, WHAT_E>,
-// without statistics) with k_distortion's consumer (enc_codes into DistMeasureUnit, dist_flush at the one flush site).  Reads 3 + 3 B
-// per pixel (profile 2 on both sides), writes 12 words per frame; no scratch planes, no float frame.
-// The given samples travel as k_distortion's do (DecRaw through dec_issue, under the TARGET's subsampling and sample size): their
-// loads are issued right behind the next unit's source loads, one iteration ahead and never behind the search, and are unpacked
-// row by row where the codes are compared.
+// How far GIVEN code planes are from the planes k_transcode would write for the same source planes.  Reads 3 + 3 B per pixel
+// (profile 2 on both sides), writes 12 words per frame; no scratch planes, no float frame.  The given samples travel as
+// k_distortion's do, under the TARGET's subsampling and sample size, their loads right behind the next unit's source loads.
 struct TransDistArgs {
     DecArgs d;       // the source planes, as TransArgs::d
     EncArgs e;       // the target quantizer: q (the composite records for LM == 5), g, sc; nothing is stored
@@ -1655,23 +1676,18 @@ struct TransDistBound {
     static constexpr int value = (CSD == CS_YCBCR || CSE == CS_YCBCR) ? 512 : 1024;
 };
 
+// k_transcode's loop with the given words travelling beside the source codes
 template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
 __global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode_distortion(const TransDistArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    static_assert(CSD == CS_LUV || CSD == CS_YCBCR, "source colour spaces: Lu'v' and YCbCr");
-    static_assert((CSE == CS_LUV && (LM == 3 || LM == 7)) || (CSE == CS_YCBCR && LM == 5), "target: Lu'v' with records in LDS, YCbCr with the composite records");
-    constexpr bool YD = CSD == CS_YCBCR, YE = CSE == CS_YCBCR;
-    __shared__ unsigned long long s_acc[12];
-    if (threadIdx.x < 12)
-        s_acc[threadIdx.x] = 0;   // (stage_tables synchronises)
-    constexpr int WHAT_D = STAGE_LUT | (YD ? STAGE_POWF | STAGE_YT | STAGE_CT : STAGE_UV);
-    constexpr int WHAT_E = STAGE_REC | (YE ? STAGE_POWF : 0);
-    stage_tables<WHAT_D, WHAT_E>(smem, a.d.q, a.e.q);
-    constexpr int off = lds_table_offset<WHAT_D | WHAT_E>();
+    unsigned long long *const s_acc = dist_words();
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
     const float *s_lut = reinterpret_cast<const float *>(smem + off);
     const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
-    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<WHAT_D>(a.d.q));
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
     const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
     const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
     const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
@@ -1679,32 +1695,22 @@ __global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int NW = blockDim.x >> 6;
     const int G = gridDim.x;
+
     const int mask = a.g.bps == 2 ? 0xffff : 0xff;
-
     DistAcc acc;
-    acc.frame = -1;
-    acc.reset();
     EncStats st;   // (enc_transform's parameter; unused with STATS = false)
-    st.frame = -1;
-    st.sum = st.mn = st.mx = 0.0f;
-
-    // k_transcode's loop with k_distortion's flush site: the iteration past the last tile sees "frame" -2, flushes and leaves
     DecUnit<SUBD, VW> cur, nxt;
     DecRaw<SUBE, VW> given;
     dec_load<SUBD, VW>(cur, a.d, blockIdx.x, tx, ty, NW);
     dec_issue<SUBE, VW>(given, a.g, blockIdx.x, tx, ty, NW);
     for (int t = blockIdx.x;; t += G) {
-        const bool done = t >= a.d.g.totalTiles;        // workgroup-uniform, as the frame index is
-        const int f = done ? -2 : t / a.d.g.tilesPerFrame;
-        if (f != acc.frame) {
-            dist_flush(acc, s_acc, a.out);
-            acc.frame = f;
-        }
+        const bool done = t >= a.d.g.totalTiles;
+        dist_flush(acc, s_acc, done ? -2 : t / a.d.g.tilesPerFrame, a.out);
         if (done)
             break;
         if (cur.valid) {
             EncUnit<VW> u;
-            if constexpr (YD) {
+            if constexpr (Front::YD) {
                 // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
                 if (kd.sc_mode == 1)
                     dec_values<CSD, SUBD, VW, false, true, true>(cur, a.d, kd, s_lut, s_uv, u.in);
@@ -1714,7 +1720,7 @@ __global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode
                 dec_values<CSD, SUBD, VW, true>(cur, a.d, kd, s_lut, s_uv, u.in);
             }
             float c0[2 * VW], c1[2 * VW], c2[2 * VW];
-            enc_transform<CSE, VW, YE, false, false>(u, a.e, ke, c0, c1, c2, st);
+            enc_transform<CSE, VW, Front::YE, false, false>(u, a.e, ke, c0, c1, c2, st);
             const DistMeasureUnit<SUBE, VW> out{given, a.g, acc, mask};
             enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
         }

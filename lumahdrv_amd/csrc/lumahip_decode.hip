@@ -283,8 +283,6 @@ int decode_impl(lumahip_ctx *c, const SrcPlanes &p, float sc, const DstFrames &f
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no decode kernel for colour space %d%s", cs_eff, out16 ? " with binary16 frames" : "");
     LagLaunchGuard rb_guard{c->rb_pol, rb_flag};   // (a return before the launch takes the word back: the policy must not wait for it)
-    if (lds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // few_writers: the 4:2:0 16-bit kernels of the HBM-bound colour spaces (12 of 15 bytes per pixel are writes); 2 when the three
     // colour planes of the batch are separate buffers (no plane starts inside another plane's extent over the batch) -- the layout
     // a caller uses to spread the three write streams over the HBM region groups (lumahip_decode_frames_device_planar)
@@ -293,7 +291,8 @@ int decode_impl(lumahip_ctx *c, const SrcPlanes &p, float sc, const DstFrames &f
         few_writers = 2;
     const int grid = grid_for(c, threads, a.g.totalTiles, 1, few_writers, cs_eff == CS_YCBCR);
     hipStream_t s = launch_stream(c, o.stream, o.lanes);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
+    if ((rc = launch_fused(c, kern, grid, threads, lds, s, a)))
+        return rc;
     rb_guard.launched = true;
     if (rb_flag && (rc = lag_policy_launched(c, c->rb_pol, s)))
         return rc;

@@ -10,8 +10,6 @@ using namespace lhost;
 
 namespace lhost {
 
-static bool ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
-
 int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out, const DistortionLaunch &o)
 {
     const bool in16 = f.elem == Elem::F16;
@@ -28,19 +26,18 @@ int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
         return rc;
     if ((rc = check_layout(c, f, true, given.stride, given.pfs, profile)))
         return rc;
-    if (!out || !is_aligned(out, 8))
-        return fail(c, LUMAHIP_ERR_ARG, "out_dev must be non-null and 8-byte aligned");
+    if ((rc = check_out_words(c, out)))
+        return rc;
     const size_t esz = elem_size(f.elem);
-    if (!is_aligned(f.plane[0], 2 * esz) || !is_aligned(f.plane[1], 2 * esz) || !is_aligned(f.plane[2], 2 * esz) || (f.frame_stride % 2) != 0)
-        return fail(c, LUMAHIP_ERR_ARG, "colour planes must be %d-byte aligned and the frame stride even", (int)(2 * esz));
+    bool al4;
+    if ((rc = check_frame_alignment(c, f, esz, &al4)))
+        return rc;
     // out_dev may not share a byte with anything the launch reads
-    const size_t out_bytes = (size_t)nframes * 12 * sizeof(uint64_t);
     const size_t frame_span = ((size_t)(nframes - 1) * f.frame_stride + (size_t)w * h) * esz;
     for (int p = 0; p < 3; p++) {
-        if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)f.plane[p], frame_span))
+        if (ranges_overlap((uintptr_t)out, out_words_bytes(nframes), (uintptr_t)f.plane[p], frame_span))
             return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps colour plane %d of the frames", p);
-        if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)given.planes[p],
-                           plane_extent(w, h, profile, p, given.stride[p], given.pfs[p], nframes)))
+        if (out_overlaps_plane(out, given, p, w, h, nframes))
             return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps given plane %d", p);
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -66,14 +63,13 @@ int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     const bool sub = (profile == 0 || profile == 2);
     // four pixels per thread and row where the frames allow the 16 / 8-byte loads (the given planes fall back to byte loads by
     // themselves: DecArgs::aligned), else two
-    const bool al4 = is_aligned(f.plane[0], 4 * esz) && is_aligned(f.plane[1], 4 * esz) && is_aligned(f.plane[2], 4 * esz);
-    const int vw = ((w % 4) == 0 && al4 && (f.frame_stride % 4) == 0) ? 4 : 2;
+    const int vw = al4 ? 4 : 2;
     const bool long_launch = (unsigned long long)w * h * nframes >= 60000000ull;   // as the encode dispatch
     const int threads = block_threads_for(c, lds, long_launch && cs != CS_YCBCR, cs == CS_YCBCR && !half);
     DistArgs a{};
     if (!make_geom(a.e.g, w, h, vw, threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
-    a.d.g = a.e.g;
+    a.g.g = a.e.g;
     a.e.q = ycode ? c->q_y : c->q;
     a.e.q.cs = cs;
     a.e.half = half;
@@ -81,26 +77,15 @@ int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
         a.e.src[k] = static_cast<const float *>(f.plane[k]);   // (the IN16 kernels read the same pointers as halves: encode_frames_device_impl)
     a.e.frame_stride = f.frame_stride;
     a.e.sc = sc;
-    a.e.bps = a.d.bps = profile > 1 ? 2 : 1;
-    a.d.aligned = planes_aligned(given, vw) ? 1 : 0;
-    for (int p = 0; p < 3; p++) {
-        a.d.src[p] = given.planes[p];
-        a.d.stride[p] = given.stride[p];
-        a.d.src_frame_stride[p] = given.pfs[p];
-    }
+    read_planes(a.g, given, vw);
+    a.e.bps = a.g.bps;
     a.out = out;
     const int kmode = half ? 6 : ycode ? 5 : mode;
     const dist_kernel_t kern = in16 ? pick_dist_f16(cs, sub, vw, kmode) : pick_dist<false>(cs, sub, vw, kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no distortion kernel for colour space %d%s", cs, in16 ? " with binary16 frames" : "");
-    if (lds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int grid = grid_for(c, threads, a.e.g.totalTiles, 0, 0, half ? 2 : cs == CS_YCBCR ? 1 : 0);
-    hipStream_t s = launch_stream(c, o.stream, o.lanes);
-    HIPCHK(c, hipMemsetAsync(out, 0, out_bytes, s));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
-    HIPCHK(c, hipGetLastError());
-    return LUMAHIP_OK;
+    return launch_measuring(c, kern, grid, threads, lds, launch_stream(c, o.stream, o.lanes), a, nframes);
 }
 
 }  // namespace lhost

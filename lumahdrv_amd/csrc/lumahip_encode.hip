@@ -128,11 +128,10 @@ int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, cons
     const bool fast_search = (mode == LUT_THRESH_LDS || mode == LUT_THRESH_GLOBAL || mode == LUT_LINKEY_LDS);
     // the loads of VW pixels need VW-element alignment: VW = 4 where possible, VW = 2 always (float frames 16 / 8 bytes, binary16
     // frames by type 8 / 4 bytes; uploaded halves are held to the float rule: they lie at the float frame's element offsets)
-    const size_t esz = typed16 ? 2 : 4;
-    const bool al4 = is_aligned(rgb[0], 4 * esz) && is_aligned(rgb[1], 4 * esz) && is_aligned(rgb[2], 4 * esz);
-    int vw = (fast_search && (w % 4) == 0 && al4 && (frame_stride % 4) == 0) ? 4 : 2;
-    if (!is_aligned(rgb[0], 2 * esz) || !is_aligned(rgb[1], 2 * esz) || !is_aligned(rgb[2], 2 * esz) || (frame_stride % 2) != 0)
-        return fail(c, LUMAHIP_ERR_ARG, "colour planes must be %d-byte aligned and the frame stride even", (int)(2 * esz));
+    bool al4;
+    if ((rc = check_frame_alignment(c, f, typed16 ? 2 : 4, &al4)))
+        return rc;
+    int vw = (fast_search && al4) ? 4 : 2;
     if (upload16) {   // halves: 8-byte loads of four pixels
         if (mode != LUT_THRESH_LDS || (w % 4) != 0 || (frame_stride % 4) != 0)
             return fail(c, LUMAHIP_ERR_UNSUPPORTED, "binary16 frames need the luminance records in LDS and rows of a multiple of 4 pixels");
@@ -190,13 +189,10 @@ int encode_frames_device_impl(lumahip_ctx *c, const SrcFrames &f, float sc, cons
     enc_kernel_t kern = in16 ? pick_enc_f16(cs_eff, sub, vw, kmode) : pick_enc<false>(cs_eff, sub, vw, kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no encode kernel for colour space %d%s", cs_eff, in16 ? " with binary16 frames" : "");
-    if (lds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int grid = grid_for(c, threads, a.g.totalTiles, 0, 0, half ? 2 : cs_eff == CS_YCBCR ? 1 : 0);
     hipStream_t s = launch_stream(c, o.stream, o.lanes);
-    if (stats && (rc = stats_begin(c, nframes, o.lanes, &s, &a.stats)))
+    if ((stats && (rc = stats_begin(c, nframes, o.lanes, &s, &a.stats))) || (rc = launch_fused(c, kern, grid, threads, lds, s, a)))
         return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
     half_guard.launched = true;
     if (half_flag && (rc = lag_policy_launched(c, c->half_pol, s)))
         return rc;

@@ -996,6 +996,73 @@ extern "C" int lumahip_decode_frame_host(lumahip_ctx *c, const unsigned char *co
     return decode_frame_host_impl(c, planes, stride, w, h, profile, sc, rgb_out, Elem::F32, c->q.cs);
 }
 
+// ---- the calls that stage code planes as INPUT: transcode, distortion, transcode distortion ---------------------------------
+// One set of the caller's code planes and where it sits in the context's plane staging
+struct StagedPlanes {
+    const char *name;   // in error messages: "source ", "destination ", "given " or ""
+    const unsigned char *const *planes;
+    const int *stride;
+    int profile;
+    PlaneLayout L;
+    unsigned char *dp[3];          // the device planes ...
+    const unsigned char *cdp[3];   // ... and as a launch reads them
+    SrcPlanes dev() const { return {cdp, stride, NO_PFS, profile}; }
+};
+
+// What those calls open with, after their null checks: the geometry against the target-side set `tgt`, the source set's profile and
+// quantizer (src = nullptr: frames in, one set), both layouts, d_planes large enough for [src][tgt] and -- words -- d_arr for the 12
+// words of a measuring call
+static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes &tgt, bool words)
+{
+    int rc = check_geom(c, w, h, tgt.profile, c->q.cs);
+    if (rc)
+        return rc;
+    if (src && (src->profile < 0 || src->profile > 3))
+        return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src->profile);
+    if (src && !c->src.have)
+        return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    StagedPlanes *const sets[2] = {src, &tgt};
+    size_t total = 0;
+    for (StagedPlanes *s : sets) {
+        if (!s)
+            continue;
+        plane_layout(s->L, w, h, s->profile, s->stride);
+        const int p = bad_plane(s->L, s->planes, s->stride);
+        if (p >= 0)
+            return fail(c, LUMAHIP_ERR_ARG, "%splane %d: null or stride %d < row bytes %d", s->name, p, s->stride[p], s->L.row_bytes[p]);
+        total += s->L.total;
+    }
+    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, total)) ||
+        (words && (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, 12 * sizeof(uint64_t)))))
+        return rc;
+    size_t off = 0;
+    for (StagedPlanes *s : sets) {
+        if (!s)
+            continue;
+        device_planes(s->dp, c->d_planes + off, s->L, s->stride);
+        for (int k = 0; k < 3; k++)
+            s->cdp[k] = s->dp[k];
+        off += s->L.total;
+    }
+    return LUMAHIP_OK;
+}
+
+static int planes_up(lumahip_ctx *c, const StagedPlanes &s, unsigned h)
+{
+    for (int k = 0; k < 3; k++)
+        if (int rc = plane_h2d(c, s.dp, s.planes, s.stride, s.L, k, 0, h, c->stream))
+            return rc;
+    return LUMAHIP_OK;
+}
+
+// what the measuring calls close with: the 12 words down (synchronises the stream)
+static int words_down(lumahip_ctx *c, uint64_t out[12])
+{
+    return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(c->d_arr), 24, c->stream);
+}
+
 // Source planes up, one transcode launch, destination planes down, synchronously on the context's stream; the context's plane
 // staging holds both sets.  mean_lum as lumahip_encode_frame_host: the launch's statistic, replaced by the reference's
 // sequential sum -- over channel 0 of the decoded and transformed frame, which only then is written, into the staging frame --
@@ -1008,37 +1075,16 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
         return LUMAHIP_ERR_ARG;
     if (!src_planes || !src_stride || !dst_planes || !dst_stride)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, dst_profile, c->q.cs);
+    StagedPlanes src{"source ", src_planes, src_stride, src_profile}, dst{"destination ", dst_planes, dst_stride, dst_profile};
+    int rc = planes_staging(c, w, h, &src, dst, false);
     if (rc)
-        return rc;
-    if (src_profile < 0 || src_profile > 3)
-        return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src_profile);
-    if (!c->src.have)
-        return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    PlaneLayout Ls, Ld;
-    plane_layout(Ls, w, h, src_profile, src_stride);
-    plane_layout(Ld, w, h, dst_profile, dst_stride);
-    int p = bad_plane(Ls, src_planes, src_stride);
-    if (p >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "source plane %d: null or stride %d < row bytes %d", p, src_stride[p], Ls.row_bytes[p]);
-    if ((p = bad_plane(Ld, dst_planes, dst_stride)) >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "destination plane %d: null or stride %d < row bytes %d", p, dst_stride[p], Ld.row_bytes[p]);
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, Ls.total + Ld.total)))
         return rc;
     if (!c->d_stats)
         HIPCHK(c, hipMalloc(&c->d_stats, 3 * sizeof(float)));
-    unsigned char *sp[3], *dp[3];
-    device_planes(sp, c->d_planes, Ls, src_stride);
-    device_planes(dp, c->d_planes + Ls.total, Ld, dst_stride);
-    for (int k = 0; k < 3; k++)
-        if ((rc = plane_h2d(c, sp, src_planes, src_stride, Ls, k, 0, h, c->stream)))
-            return rc;
-    if ((rc = transcode_impl(c, {sp, src_stride, NO_PFS, src_profile}, src_sc, 1, w, h, {dp, dst_stride, NO_PFS, dst_profile}, dst_sc,
-                             mean_lum ? c->d_stats : nullptr, {c->stream, false})))
-        return rc;
-    if ((rc = planes_d2h(c, dst_planes, dp, dst_stride, Ld, 0, h, c->stream, false)))
+    if ((rc = planes_up(c, src, h)) ||
+        (rc = transcode_impl(c, src.dev(), src_sc, 1, w, h, {dst.dp, dst_stride, NO_PFS, dst_profile}, dst_sc, mean_lum ? c->d_stats : nullptr,
+                             {c->stream, false})) ||
+        (rc = planes_d2h(c, dst_planes, dst.dp, dst_stride, dst.L, 0, h, c->stream, false)))
         return rc;
     if (!mean_lum) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1051,7 +1097,7 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
     if (mean_needs_reference_sum(*mean_lum, st[1], w, h)) {
         if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, (size_t)w * h * sizeof(float))))
             return rc;
-        if ((rc = transcode_channel0(c, {sp, src_stride, NO_PFS, src_profile}, src_sc, w, h, dst_sc, c->d_frame, c->stream)))
+        if ((rc = transcode_channel0(c, src.dev(), src_sc, w, h, dst_sc, c->d_frame, c->stream)))
             return rc;
         return seq_mean(c, c->d_frame, w, h, mean_lum);
     }
@@ -1066,34 +1112,15 @@ extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, u
         return LUMAHIP_ERR_ARG;
     if (!rgb || !planes || !stride || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, profile, c->q.cs);
-    if (rc)
-        return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    PlaneLayout L;
-    plane_layout(L, w, h, profile, stride);
-    const int p = bad_plane(L, planes, stride);
-    if (p >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "plane %d: null or stride %d < row bytes %d", p, stride[p], L.row_bytes[p]);
+    StagedPlanes given{"", planes, stride, profile};
     const size_t nfl = (size_t)3 * w * h;
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
-        (rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, L.total)) ||
-        (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, 12 * sizeof(uint64_t))))
-        return rc;
-    unsigned char *dp[3];
-    device_planes(dp, c->d_planes, L, stride);
-    if ((rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))
-        return rc;
-    for (int k = 0; k < 3; k++)
-        if ((rc = plane_h2d(c, dp, planes, stride, L, k, 0, h, c->stream)))
-            return rc;
-    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->d_arr);
-    const unsigned char *cdp[3] = {dp[0], dp[1], dp[2]};
-    if ((rc = distortion_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, {cdp, stride, NO_PFS, profile}, d_out,
+    int rc = planes_staging(c, w, h, nullptr, given, true);
+    if (rc || (rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
+        (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
+        (rc = distortion_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), reinterpret_cast<uint64_t *>(c->d_arr),
                               {c->stream, false})))
         return rc;
-    return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(d_out), 24, c->stream);   // (12 words; synchronises the stream)
+    return words_down(c, out);
 }
 
 // Source planes and given planes in host memory -> the 12 words of the transcode distortion (lumahip_transcode_distortion.hip),
@@ -1107,39 +1134,12 @@ extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const uns
         return LUMAHIP_ERR_ARG;
     if (!src_planes || !src_stride || !given_planes || !given_stride || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    int rc = check_geom(c, w, h, dst_profile, c->q.cs);
-    if (rc)
+    StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
+    int rc = planes_staging(c, w, h, &src, given, true);
+    if (rc || (rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
+        (rc = transcode_distortion_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
         return rc;
-    if (src_profile < 0 || src_profile > 3)
-        return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src_profile);
-    if (!c->src.have)
-        return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    PlaneLayout Ls, Lg;
-    plane_layout(Ls, w, h, src_profile, src_stride);
-    plane_layout(Lg, w, h, dst_profile, given_stride);
-    int p = bad_plane(Ls, src_planes, src_stride);
-    if (p >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "source plane %d: null or stride %d < row bytes %d", p, src_stride[p], Ls.row_bytes[p]);
-    if ((p = bad_plane(Lg, given_planes, given_stride)) >= 0)
-        return fail(c, LUMAHIP_ERR_ARG, "given plane %d: null or stride %d < row bytes %d", p, given_stride[p], Lg.row_bytes[p]);
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, Ls.total + Lg.total)) ||
-        (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, 12 * sizeof(uint64_t))))
-        return rc;
-    unsigned char *sp[3], *gp[3];
-    device_planes(sp, c->d_planes, Ls, src_stride);
-    device_planes(gp, c->d_planes + Ls.total, Lg, given_stride);
-    for (int k = 0; k < 3; k++)
-        if ((rc = plane_h2d(c, sp, src_planes, src_stride, Ls, k, 0, h, c->stream)) ||
-            (rc = plane_h2d(c, gp, given_planes, given_stride, Lg, k, 0, h, c->stream)))
-            return rc;
-    uint64_t *d_out = reinterpret_cast<uint64_t *>(c->d_arr);
-    const unsigned char *csp[3] = {sp[0], sp[1], sp[2]}, *cgp[3] = {gp[0], gp[1], gp[2]};
-    if ((rc = transcode_distortion_impl(c, {csp, src_stride, NO_PFS, src_profile}, src_sc, 1, w, h, {cgp, given_stride, NO_PFS, dst_profile}, dst_sc,
-                                        d_out, {c->stream, false})))
-        return rc;
-    return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(d_out), 24, c->stream);   // (12 words; synchronises the stream)
+    return words_down(c, out);
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the

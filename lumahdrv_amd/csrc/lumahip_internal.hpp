@@ -5,16 +5,17 @@
 //                       memory helpers                                                                    (no kernels)
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
-//   lumahip_pick.hpp    which k_encode / k_decode / k_transcode instantiation a launch takes: pick_enc<IN16> / pick_dec<OUT16> /
-//                       pick_trans<VW> / pick_dist<IN16>, included by the seven kernel units below and by nothing else
+//   lumahip_pick.hpp    which instantiation of the fused kernels a launch takes: pick_enc<IN16> / pick_dec<OUT16> / pick_dist<IN16> /
+//                       pick_planes<TransFamily | TransDistFamily, VW>, included by the eight kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
 //                       tables next to the kernel that builds them
 //   lumahip_encode_f16.hip / lumahip_decode_f16.hip  pick_enc<true> / pick_dec<true> (the binary16-frame kernels, exported as
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
-//   lumahip_transcode.hip  pick_trans (every k_transcode), the transcode dispatch and its two entry points
-//   lumahip_transcode_distortion.hip  pick_transdist (every k_transcode_distortion), its dispatch and device entry point
+//   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
+//                       be, for this unit and the next --, the transcode dispatch and its two entry points
+//   lumahip_transcode_distortion.hip  pick_planes<TransDistFamily, .> (every k_transcode_distortion), its dispatch and device entry point
 //   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<false> / pick_dist<true> (every k_distortion), the distortion
 //                       dispatch and the _device entry points
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
@@ -419,6 +420,19 @@ static inline size_t plane_extent(unsigned w, unsigned h, int profile, int p, in
     plane_dims(w, h, profile, p, rows, row_bytes);
     return (size_t)(nframes - 1) * pfs + (size_t)(rows - 1) * (size_t)stride + (size_t)row_bytes;
 }
+static inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+static inline bool ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
+// ---- the 12 words per frame of the measuring calls (out_dev)
+static inline size_t out_words_bytes(unsigned nframes) { return (size_t)nframes * 12 * sizeof(uint64_t); }
+static inline int check_out_words(lumahip_ctx *c, const uint64_t *out)
+{
+    return (!out || !is_aligned(out, 8)) ? fail(c, LUMAHIP_ERR_ARG, "out_dev must be non-null and 8-byte aligned") : LUMAHIP_OK;
+}
+// out_dev may not share a byte with anything the launch reads: here, plane k of a set of code planes over the batch
+static inline bool out_overlaps_plane(const uint64_t *out, const SrcPlanes &p, int k, unsigned w, unsigned h, unsigned nframes)
+{
+    return ranges_overlap((uintptr_t)out, out_words_bytes(nframes), (uintptr_t)p.planes[k], plane_extent(w, h, p.profile, k, p.stride[k], p.pfs[k], nframes));
+}
 // every base, stride and frame stride of these planes takes the vector accesses of VW pixels per thread and row
 template <typename B>
 static inline bool planes_aligned(const CodePlanesT<B> &p, int vw)
@@ -431,6 +445,45 @@ static inline bool planes_aligned(const CodePlanesT<B> &p, int vw)
             return false;
     }
     return true;
+}
+
+// code planes a kernel reads, as its DecArgs names them (the transcode's source planes, the given planes of both measuring calls)
+static inline void read_planes(DecArgs &d, const SrcPlanes &p, int vw)
+{
+    d.bps = p.profile > 1 ? 2 : 1;
+    d.aligned = planes_aligned(p, vw) ? 1 : 0;
+    for (int k = 0; k < 3; k++) {
+        d.src[k] = p.planes[k];
+        d.stride[k] = p.stride[k];
+        d.src_frame_stride[k] = p.pfs[k];
+    }
+}
+// The colour planes of frames with elements of esz bytes: loads of two pixels need 2-element alignment, else the call is refused;
+// *al4: rows, planes and frame stride also take the loads of four
+static inline int check_frame_alignment(lumahip_ctx *c, const SrcFrames &f, size_t esz, bool *al4)
+{
+    auto al = [&](size_t n) { return is_aligned(f.plane[0], n * esz) && is_aligned(f.plane[1], n * esz) && is_aligned(f.plane[2], n * esz) && (f.frame_stride % n) == 0; };
+    *al4 = (f.w % 4) == 0 && al(4);
+    return al(2) ? LUMAHIP_OK : fail(c, LUMAHIP_ERR_ARG, "colour planes must be %d-byte aligned and the frame stride even", (int)(2 * esz));
+}
+// The launch of a fused kernel (+ dynamic LDS beyond 64 KiB); the caller reads hipGetLastError once all that belongs to it is queued
+template <typename A>
+int launch_fused(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, size_t lds, hipStream_t s, const A &a)
+{
+    if (lds > 64 * 1024)
+        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
+    return LUMAHIP_OK;
+}
+// ... of a measuring kernel (A::out): its words are zeroed in front of it, and nothing follows it
+template <typename A>
+int launch_measuring(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, size_t lds, hipStream_t s, const A &a, unsigned nframes)
+{
+    HIPCHK(c, hipMemsetAsync(a.out, 0, out_words_bytes(nframes), s));
+    if (int rc = launch_fused(c, kern, grid, threads, lds, s, a))
+        return rc;
+    HIPCHK(c, hipGetLastError());
+    return LUMAHIP_OK;
 }
 
 // ---- lumahip_encode.hip / lumahip_decode.hip
@@ -458,7 +511,7 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                    float *stats, const TranscodeLaunch &o);
 typedef void (*trans_kernel_t)(const lh::TransArgs);
 // What transcode_plan decides for a launch over (source planes, target-side planes): the kernel's key (colour spaces,
-// subsamplings, vector width, the target's search mode as pick_trans takes it), the launch shape and the kernel arguments of both
+// subsamplings, vector width, the target's search mode as pick_planes takes it), the launch shape and the kernel arguments of both
 // sides except the target-side plane pointers, which the two callers fill in (written: EncArgs::dst; read: a DecArgs of their own)
 struct TranscodePlan {
     int csd, cse, kmode, vw, threads, grid;
@@ -487,7 +540,7 @@ int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
 typedef void (*dist_kernel_t)(const lh::DistArgs);
 dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode);
 
-// ---- lumahip_transcode_distortion.hip: pick_transdist of lumahip_pick.hpp (every k_transcode_distortion)
+// ---- lumahip_transcode_distortion.hip: pick_planes<TransDistFamily, .> of lumahip_pick.hpp (every k_transcode_distortion)
 // the source planes' transcode (transcode_impl's planes, never written) against the given planes: 12 words per frame at out_dev
 int transcode_distortion_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
                               float dst_sc, uint64_t *out_dev, const TranscodeLaunch &o);

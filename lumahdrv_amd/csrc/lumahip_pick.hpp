@@ -1,9 +1,10 @@
-// lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / lh::k_decode / lh::k_transcode, luma_kernels.hpp) a launch takes.
+// lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / k_decode / k_transcode / k_distortion /
+// k_transcode_distortion, luma_kernels.hpp) a launch takes.
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
-// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_trans<4> / pick_trans<2>;
-// lumahip_transcode_distortion.hip takes pick_transdist<4> / pick_transdist<2>; lumahip_distortion.hip /
+// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_planes<TransFamily, 4 | 2>;
+// lumahip_transcode_distortion.hip takes pick_planes<TransDistFamily, 4 | 2>; lumahip_distortion.hip /
 // lumahip_distortion_f16.hip take pick_dist<false> / pick_dist<true>.  Included by those eight units only.
 #pragma once
 #include "lumahip_internal.hpp"
@@ -97,59 +98,45 @@ static dec_kernel_t pick_dec(int cs, bool sub, int vw, bool gl, bool disp, bool 
     return nullptr;
 }
 
-// The transcode kernels (lh::k_transcode): source colour space / subsampling, target colour space / subsampling, the target's
-// search mode -- Lu'v': LUT_THRESH_LDS or LUT_LINKEY_LDS, YCbCr: 5 = the composite records.  nullptr: outside the supported set.
-// VW a template parameter so that, like the pickers above, only the unit that names it (lumahip_transcode.hip) compiles the kernels
-template <int VW, int CSD, bool SUBD>
-static trans_kernel_t pick_trans_src(int cse, bool sube, int mode)
+// The plane-fed kernels: lh::k_transcode (TransFamily, named by lumahip_transcode.hip only) and lh::k_transcode_distortion
+// (TransDistFamily, named by lumahip_transcode_distortion.hip only), the same keys kernel for kernel.  A family says what its kernels
+// are and how many threads per workgroup they are compiled for (transcode_plan clamps the launch to it).
+struct TransFamily {
+    using kernel_t = trans_kernel_t;
+    template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+    static kernel_t kernel() { return lh::k_transcode<CSD, SUBD, CSE, SUBE, VW, LM>; }
+    static int bound(bool) { return 1024; }
+};
+struct TransDistFamily {
+    using kernel_t = transdist_kernel_t;
+    template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+    static kernel_t kernel() { return lh::k_transcode_distortion<CSD, SUBD, CSE, SUBE, VW, LM>; }
+    static int bound(bool any_y) { return any_y ? lh::TransDistBound<lh::CS_YCBCR, lh::CS_YCBCR>::value : lh::TransDistBound<lh::CS_LUV, lh::CS_LUV>::value; }
+};
+
+// source colour space / subsampling, target colour space / subsampling, the target's search mode -- Lu'v': LUT_THRESH_LDS or
+// LUT_LINKEY_LDS, YCbCr: 5 = the composite records.  nullptr: outside the supported set.
+// VW a template parameter so that, like the pickers above, only the unit that names it compiles the kernels
+template <typename F, int VW, int CSD, bool SUBD>
+static typename F::kernel_t pick_planes_src(int cse, bool sube, int mode)
 {
     using namespace lh;
     if (cse == CS_LUV && mode == LUT_THRESH_LDS)
-        return sube ? k_transcode<CSD, SUBD, CS_LUV, true, VW, 3> : k_transcode<CSD, SUBD, CS_LUV, false, VW, 3>;
+        return sube ? F::template kernel<CSD, SUBD, CS_LUV, true, VW, 3>() : F::template kernel<CSD, SUBD, CS_LUV, false, VW, 3>();
     if (cse == CS_LUV && mode == LUT_LINKEY_LDS)
-        return sube ? k_transcode<CSD, SUBD, CS_LUV, true, VW, 7> : k_transcode<CSD, SUBD, CS_LUV, false, VW, 7>;
+        return sube ? F::template kernel<CSD, SUBD, CS_LUV, true, VW, 7>() : F::template kernel<CSD, SUBD, CS_LUV, false, VW, 7>();
     if (cse == CS_YCBCR && mode == 5)
-        return sube ? k_transcode<CSD, SUBD, CS_YCBCR, true, VW, 5> : k_transcode<CSD, SUBD, CS_YCBCR, false, VW, 5>;
+        return sube ? F::template kernel<CSD, SUBD, CS_YCBCR, true, VW, 5>() : F::template kernel<CSD, SUBD, CS_YCBCR, false, VW, 5>();
     return nullptr;
 }
 
-template <int VW>
-static trans_kernel_t pick_trans(int csd, bool subd, int cse, bool sube, int mode)
+template <typename F, int VW>
+static typename F::kernel_t pick_planes(int csd, bool subd, int cse, bool sube, int mode)
 {
     using namespace lh;
     switch (csd) {
-    case CS_LUV: return subd ? pick_trans_src<VW, CS_LUV, true>(cse, sube, mode) : pick_trans_src<VW, CS_LUV, false>(cse, sube, mode);
-    case CS_YCBCR: return subd ? pick_trans_src<VW, CS_YCBCR, true>(cse, sube, mode) : pick_trans_src<VW, CS_YCBCR, false>(cse, sube, mode);
-    }
-    return nullptr;
-}
-
-// The transcode distortion kernels (lh::k_transcode_distortion): pick_trans's keys, kernel for kernel; named by
-// lumahip_transcode_distortion.hip only.  *bound: the threads per workgroup the kernel is compiled for (lh::TransDistBound)
-template <int VW, int CSD, bool SUBD>
-static transdist_kernel_t pick_transdist_src(int cse, bool sube, int mode, int *bound)
-{
-    using namespace lh;
-    if (cse == CS_LUV && (mode == LUT_THRESH_LDS || mode == LUT_LINKEY_LDS)) {
-        *bound = TransDistBound<CSD, CS_LUV>::value;
-        if (mode == LUT_THRESH_LDS)
-            return sube ? k_transcode_distortion<CSD, SUBD, CS_LUV, true, VW, 3> : k_transcode_distortion<CSD, SUBD, CS_LUV, false, VW, 3>;
-        return sube ? k_transcode_distortion<CSD, SUBD, CS_LUV, true, VW, 7> : k_transcode_distortion<CSD, SUBD, CS_LUV, false, VW, 7>;
-    }
-    if (cse == CS_YCBCR && mode == 5) {
-        *bound = TransDistBound<CSD, CS_YCBCR>::value;
-        return sube ? k_transcode_distortion<CSD, SUBD, CS_YCBCR, true, VW, 5> : k_transcode_distortion<CSD, SUBD, CS_YCBCR, false, VW, 5>;
-    }
-    return nullptr;
-}
-
-template <int VW>
-static transdist_kernel_t pick_transdist(int csd, bool subd, int cse, bool sube, int mode, int *bound)
-{
-    using namespace lh;
-    switch (csd) {
-    case CS_LUV: return subd ? pick_transdist_src<VW, CS_LUV, true>(cse, sube, mode, bound) : pick_transdist_src<VW, CS_LUV, false>(cse, sube, mode, bound);
-    case CS_YCBCR: return subd ? pick_transdist_src<VW, CS_YCBCR, true>(cse, sube, mode, bound) : pick_transdist_src<VW, CS_YCBCR, false>(cse, sube, mode, bound);
+    case CS_LUV: return subd ? pick_planes_src<F, VW, CS_LUV, true>(cse, sube, mode) : pick_planes_src<F, VW, CS_LUV, false>(cse, sube, mode);
+    case CS_YCBCR: return subd ? pick_planes_src<F, VW, CS_YCBCR, true>(cse, sube, mode) : pick_planes_src<F, VW, CS_YCBCR, false>(cse, sube, mode);
     }
     return nullptr;
 }

@@ -9,10 +9,6 @@ using namespace lhost;
 
 namespace lhost {
 
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-static bool ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
-
 // The one place that decides what a launch over (source planes, target-side planes) may be and how it runs: argument checks, the
 // supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (tgt = the planes it
 // writes; out = nullptr) and for the transcode distortion (measure: tgt = the given planes it reads, out = its words).
@@ -47,13 +43,12 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                     return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
     } else {
         // both plane sets are read only and may overlap each other; out_dev may not share a byte with anything the launch reads
-        if (!out || !is_aligned(out, 8))
-            return fail(c, LUMAHIP_ERR_ARG, "out_dev must be non-null and 8-byte aligned");
-        const size_t out_bytes = (size_t)nframes * 12 * sizeof(uint64_t);
+        if ((rc = check_out_words(c, out)))
+            return rc;
         for (int k = 0; k < 3; k++) {
-            if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)src.planes[k], plane_extent(w, h, src.profile, k, src.stride[k], src.pfs[k], nframes)))
+            if (out_overlaps_plane(out, src, k, w, h, nframes))
                 return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps source plane %d", k);
-            if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)tgt.planes[k], plane_extent(w, h, tgt.profile, k, tgt.stride[k], tgt.pfs[k], nframes)))
+            if (out_overlaps_plane(out, tgt, k, w, h, nframes))
                 return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps given plane %d", k);
         }
     }
@@ -95,21 +90,13 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.threads = block_threads_for(c, lds, long_launch && !any_y, any_y);
     // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
     // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
-    const int bound = !measure ? 1024 : any_y ? TransDistBound<CS_YCBCR, CS_YCBCR>::value : TransDistBound<CS_LUV, CS_LUV>::value;
-    if (p.threads > bound)
-        p.threads = bound;
+    p.threads = std::min(p.threads, measure ? TransDistFamily::bound(any_y) : TransFamily::bound(any_y));
     p.d = DecArgs{};
     if (!make_geom(p.d.g, w, h, p.vw, p.threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
     p.d.q = sq.q;
     p.d.sc = src_sc;
-    p.d.bps = src.profile > 1 ? 2 : 1;
-    p.d.aligned = planes_aligned(src, p.vw) ? 1 : 0;
-    for (int k = 0; k < 3; k++) {
-        p.d.src[k] = src.planes[k];
-        p.d.stride[k] = src.stride[k];
-        p.d.src_frame_stride[k] = src.pfs[k];
-    }
+    read_planes(p.d, src, p.vw);
     p.e = EncArgs{};
     p.e.g = p.d.g;
     p.e.q = qe;
@@ -136,15 +123,15 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
         a.e.stride[k] = dst.stride[k];
         a.e.dst_frame_stride[k] = dst.pfs[k];
     }
-    const trans_kernel_t kern = p.vw == 4 ? pick_trans<4>(p.csd, p.subd, p.cse, p.sube, p.kmode) : pick_trans<2>(p.csd, p.subd, p.cse, p.sube, p.kmode);
+    const trans_kernel_t kern = p.vw == 4 ? pick_planes<TransFamily, 4>(p.csd, p.subd, p.cse, p.sube, p.kmode)
+                                          : pick_planes<TransFamily, 2>(p.csd, p.subd, p.cse, p.sube, p.kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode kernel for colour spaces %d -> %d", p.csd, p.cse);
-    if (p.lds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
     hipStream_t s = launch_stream(c, o.stream, o.lanes);
     if (stats && (rc = stats_begin(c, nframes, o.lanes, &s, &a.e.stats)))
         return rc;
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds, s, a);
+    if ((rc = launch_fused(c, kern, p.grid, p.threads, p.lds, s, a)))
+        return rc;
     if (stats)
         stats_fold(c, nframes, stats, s);
     HIPCHK(c, hipGetLastError());

@@ -22,28 +22,13 @@ int transcode_distortion_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc
     a.d = p.d;
     a.e = p.e;
     a.g.g = p.d.g;
-    a.g.bps = p.e.bps;
-    a.g.aligned = p.e.aligned;
-    for (int k = 0; k < 3; k++) {
-        a.g.src[k] = given.planes[k];
-        a.g.stride[k] = given.stride[k];
-        a.g.src_frame_stride[k] = given.pfs[k];
-    }
+    read_planes(a.g, given, p.vw);
     a.out = out;
-    int bound = 0;
-    const transdist_kernel_t kern = p.vw == 4 ? pick_transdist<4>(p.csd, p.subd, p.cse, p.sube, p.kmode, &bound)
-                                              : pick_transdist<2>(p.csd, p.subd, p.cse, p.sube, p.kmode, &bound);
+    const transdist_kernel_t kern = p.vw == 4 ? pick_planes<TransDistFamily, 4>(p.csd, p.subd, p.cse, p.sube, p.kmode)
+                                              : pick_planes<TransDistFamily, 2>(p.csd, p.subd, p.cse, p.sube, p.kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode distortion kernel for colour spaces %d -> %d", p.csd, p.cse);
-    if (p.threads > bound)   // (transcode_plan clamps to the same constants: never taken)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "transcode distortion: %d threads per workgroup, the kernel takes %d", p.threads, bound);
-    if (p.lds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
-    hipStream_t s = launch_stream(c, o.stream, o.lanes);
-    HIPCHK(c, hipMemsetAsync(out, 0, (size_t)nframes * 12 * sizeof(uint64_t), s));
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds, s, a);
-    HIPCHK(c, hipGetLastError());
-    return LUMAHIP_OK;
+    return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, nframes);
 }
 
 }  // namespace lhost
