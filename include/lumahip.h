@@ -42,7 +42,9 @@ extern "C" {
  *     lumahip_encode_frame_host_f16, lumahip_decode_frame_host_f16 and the probe lumahip_f16_narrow_probe_device; the transcode
  *     calls lumahip_set_source_quantizer, lumahip_transcode_frames_device, lumahip_transcode_frame_host; the distortion calls
  *     lumahip_distortion_frames_device / _planar / _f16 / _planar_f16 and lumahip_distortion_frame_host; the transcode
- *     distortion calls lumahip_transcode_distortion_frames_device and lumahip_transcode_distortion_frame_host.
+ *     distortion calls lumahip_transcode_distortion_frames_device and lumahip_transcode_distortion_frame_host; the distortion
+ *     map calls lumahip_distortion_map_dims, lumahip_distortion_map_frames_device / _planar / _f16 / _planar_f16 and
+ *     lumahip_distortion_map_frame_host.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -415,6 +417,44 @@ int lumahip_distortion_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t
                                                 const size_t plane_frame_stride[3], uint64_t *out_dev);
 int lumahip_distortion_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                   const unsigned char *const planes[3], const int stride[3], uint64_t out[12]);
+
+/* Distortion map: the four words of the distortion calls above, per plane, for every block of `block` x `block` luma pixels
+ * (block = 16, 32 or 64) instead of per frame -- where in the frame the error sits: a local artefact behind a fine frame PSNR, a
+ * worst-block or percentile gate, a per-superblock quantizer.  One launch, no scratch planes; e and g are exactly the distortion
+ * calls'.  With nbx = ceil(w / block), nby = ceil(h / block) (lumahip_distortion_map_dims; host-only) the words of frame f, block
+ * (bx, by), plane p are
+ *     map_dev[(((f*nby + by)*nbx + bx)*3 + p)*4 + 0..3] = sse, sad, max_abs, n_differ
+ * over the block's samples: luma pixels [bx*block, min(w, (bx+1)*block)) x [by*block, min(h, (by+1)*block)), and on a 4:2:0 chroma
+ * plane the samples co-sited with them, [bx*block/2, min(w/2, (bx+1)*block/2)) x likewise (row padding and the gaps between frames
+ * are never read).  The launch writes every one of the nframes*nby*nbx*12 words exactly once, zeros included: map_dev needs no
+ * initialisation and none is queued.  All arithmetic is integer: the map is the same from run to run whatever the launch shape,
+ * and summing its sse, sad and n_differ (taking the maximum of max_abs) over a frame's blocks gives that frame's 12 words of
+ * lumahip_distortion_frames_device.
+ * Arguments, supported set, kernel choice from the arguments alone, stream, unordered sections and the honoured lumahip_tune keys
+ * are those of the matching lumahip_distortion_frames_device form ("block": a workgroup is at most 32 * block threads for this
+ * call, since it owns whole blocks), with map_dev (required, 8-byte aligned, sharing no byte with the frames or the given planes)
+ * in the place of out_dev.  Errors, all before anything is launched (map_dev is then untouched): those of that call, and
+ * LUMAHIP_ERR_ARG for a block other than 16, 32 or 64 and, in the host form, for map_words < nbx*nby*12.
+ * The host form takes one float frame (LumaFrame layout) and the given planes in host memory, uploads them, runs one launch,
+ * downloads the nbx*nby*12 words into `map` and returns synchronously. */
+int lumahip_distortion_map_dims(unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby);
+int lumahip_distortion_map_frames_device(lumahip_ctx *ctx, const float *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                         unsigned h, float sc, int profile, const unsigned char *const planes_dev[3], const int stride[3],
+                                         const size_t plane_frame_stride[3], unsigned block, uint64_t *map_dev);
+int lumahip_distortion_map_frames_device_planar(lumahip_ctx *ctx, const float *const rgb_planes_dev[3], size_t frame_stride,
+                                                unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                                const unsigned char *const planes_dev[3], const int stride[3],
+                                                const size_t plane_frame_stride[3], unsigned block, uint64_t *map_dev);
+int lumahip_distortion_map_frames_device_f16(lumahip_ctx *ctx, const uint16_t *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                             unsigned h, float sc, int profile, const unsigned char *const planes_dev[3],
+                                             const int stride[3], const size_t plane_frame_stride[3], unsigned block, uint64_t *map_dev);
+int lumahip_distortion_map_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t *const rgb_planes_dev[3], size_t frame_stride,
+                                                    unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                                    const unsigned char *const planes_dev[3], const int stride[3],
+                                                    const size_t plane_frame_stride[3], unsigned block, uint64_t *map_dev);
+int lumahip_distortion_map_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                      const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *map,
+                                      size_t map_words);
 
 /* Transcode distortion: how far GIVEN code planes in the target's format -- what came back from the VP9 decoder on the delivery
  * side -- are from the planes the SOURCE stream's planes transcode to, in the launch that would have transcoded them; no float

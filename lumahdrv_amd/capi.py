@@ -41,6 +41,8 @@ SYMBOLS = [
     "lumahip_distortion_frames_device", "lumahip_distortion_frames_device_planar", "lumahip_distortion_frames_device_f16",
     "lumahip_distortion_frames_device_planar_f16", "lumahip_distortion_frame_host",
     "lumahip_transcode_distortion_frames_device", "lumahip_transcode_distortion_frame_host",
+    "lumahip_distortion_map_dims", "lumahip_distortion_map_frames_device", "lumahip_distortion_map_frames_device_planar",
+    "lumahip_distortion_map_frames_device_f16", "lumahip_distortion_map_frames_device_planar_f16", "lumahip_distortion_map_frame_host",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -78,7 +80,7 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
-                  "lumahip_transcode_distortion.hip")
+                  "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip")
 
 
 def kernel_source_sha() -> str:
@@ -178,6 +180,12 @@ def lib():
     L.lumahip_distortion_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
     L.lumahip_distortion_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, vp]
     L.lumahip_transcode_distortion_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, vp]
+    L.lumahip_distortion_map_dims.argtypes = [u, u, u, C.POINTER(u), C.POINTER(u)]
+    L.lumahip_distortion_map_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_distortion_map_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_distortion_map_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_distortion_map_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_distortion_map_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, u, vp, sz]
     L.lumahip_transcode_distortion_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, vp]
     L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
@@ -413,6 +421,30 @@ def code_psnr(sse, nsamples, peak) -> float:
     return 10.0 * float(np.log10(float(peak) * float(peak) * float(nsamples) / float(sse)))
 
 
+def distortion_map_dims(w: int, h: int, block: int):
+    """(nbx, nby): blocks per frame of a distortion map, ceil(w / block) x ceil(h / block); block is 16, 32 or 64"""
+    nbx, nby = C.c_uint(0), C.c_uint(0)
+    rc = lib().lumahip_distortion_map_dims(w, h, block, C.byref(nbx), C.byref(nby))
+    if rc != 0:
+        raise LumaHipError(rc, "distortion map: block must be 16, 32 or 64 (got %r)" % (block,))
+    return int(nbx.value), int(nby.value)
+
+
+def block_sample_counts(w: int, h: int, profile: int, block: int) -> np.ndarray:
+    """(nby, nbx, 3) int64: how many samples of each plane a block of a distortion map covers -- block x block luma pixels cut at
+    the frame's edges, and on the 4:2:0 chroma planes (profiles 0 and 2) the samples co-sited with them.  code_psnr(map[by, bx, p, 0],
+    counts[by, bx, p], peak) is the block's PSNR"""
+    nbx, nby = distortion_map_dims(w, h, block)
+    out = np.empty((nby, nbx, 3), dtype=np.int64)
+    for p in range(3):
+        sub = p > 0 and profile in (0, 2)
+        pw, ph, b = (w // 2, h // 2, block // 2) if sub else (w, h, block)
+        nx = np.minimum(pw, (np.arange(nbx) + 1) * b) - np.arange(nbx) * b
+        ny = np.minimum(ph, (np.arange(nby) + 1) * b) - np.arange(nby) * b
+        out[:, :, p] = ny[:, None] * nx[None, :]
+    return out
+
+
 def _arr3(ctype, vals):
     return (ctype * 3)(*vals)
 
@@ -546,6 +578,19 @@ class Context:
         self._chk(self.L.lumahip_distortion_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
                                                        _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
                                                        out.ctypes.data))
+        return out
+
+    def distortion_map_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2, block=16) -> np.ndarray:
+        """distortion_frame's words per block of block x block luma pixels (16, 32 or 64): a (nby, nbx, 3, 4) uint64 array, in one
+        launch; block_sample_counts gives the samples behind each entry"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        _, h, w = rgb.shape
+        planes = [np.ascontiguousarray(p) for p in planes]
+        nbx, nby = distortion_map_dims(w, h, block)
+        out = np.zeros((nby, nbx, 3, 4), dtype=np.uint64)
+        self._chk(self.L.lumahip_distortion_map_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
+                                                           _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
+                                                           block, out.ctypes.data, out.size))
         return out
 
     def transcode_distortion_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
@@ -687,6 +732,33 @@ class Context:
                                                                      w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
                                                                      _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
                                                                      out_ptr))
+
+    # the same per block x block luma pixels (16, 32 or 64): map_ptr receives nframes x nby x nbx x 3 planes x {sse, sad, max_abs,
+    # n_differ} as uint64, every word written by the launch (distortion_map_dims, block_sample_counts)
+    def distortion_map_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides,
+                                     block, map_ptr):
+        self._chk(self.L.lumahip_distortion_map_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                              _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                              _arr3(C.c_size_t, plane_frame_strides), block, map_ptr))
+
+    def distortion_map_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                            plane_frame_strides, block, map_ptr):
+        self._chk(self.L.lumahip_distortion_map_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w,
+                                                                     h, sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                                     _arr3(C.c_size_t, plane_frame_strides), block, map_ptr))
+
+    def distortion_map_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                         plane_frame_strides, block, map_ptr):
+        self._chk(self.L.lumahip_distortion_map_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                                  _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                                  _arr3(C.c_size_t, plane_frame_strides), block, map_ptr))
+
+    def distortion_map_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                                plane_frame_strides, block, map_ptr):
+        self._chk(self.L.lumahip_distortion_map_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
+                                                                         w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
+                                                                         _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
+                                                                         block, map_ptr))
 
     # distortion of given planes against the source planes' own transcode: the arguments are transcode_frames_device's, the
     # target-side planes are read, out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ} as uint64 (zeroed by the call)

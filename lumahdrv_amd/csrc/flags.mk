@@ -20,3 +20,6 @@ FLAGS_lumahip_transcode_distortion := $(FLAGS_lumahip_transcode)
 #   integer accumulation.  Not measured either way yet.
 FLAGS_lumahip_distortion := $(FLAGS_lumahip_encode)
 FLAGS_lumahip_distortion_f16 := $(FLAGS_lumahip_encode)
+#   lumahip_distortion_map / _f16: the same -- k_distortion_map is k_distortion with the accumulation in space.
+FLAGS_lumahip_distortion_map := $(FLAGS_lumahip_encode)
+FLAGS_lumahip_distortion_map_f16 := $(FLAGS_lumahip_encode)

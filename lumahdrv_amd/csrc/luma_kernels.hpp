@@ -641,7 +641,7 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
 // ---- THE KERNELS THAT END IN enc_codes ----------------------------------------------------------------
 // Two front ends produce a transformed unit (c0, c1, c2), two consumers take the codes enc_codes makes of it:
 //                                                        store (EncStoreUnit)   measure (DistMeasureUnit, dist_flush)
-//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion
+//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion; per block: k_distortion_map
 //   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion
 //                   enc_transform
 // A kernel is its front end, its consumer and the persistent loop that orders their loads against each other; the loops differ on
@@ -1541,11 +1541,12 @@ struct DistAcc {
 
 // the consumer of enc_codes that measures: each row handed over against the same row of the given unit, unpacked from the
 // prefetched words `g` only now (rows the vector loads could not take are loaded here, byte by byte, as dec_finish does)
-template <bool SUB, int VW>
+// Acc: where the lane's sums go -- DistAcc (a frame's) or DistBlockAcc (a map block's, k_distortion_map)
+template <bool SUB, int VW, typename Acc = DistAcc>
 struct DistMeasureUnit {
     const DecRaw<SUB, VW> &g;
     const DecArgs &d;
-    DistAcc &acc;
+    Acc &acc;
     int mask;   // 0xffff / 0xff: what store_samples keeps of a code
     template <int N>
     LH_DEVS void row(int pl, int r, const int (&codes)[N]) const
@@ -1727,6 +1728,188 @@ __global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode
         dec_load<SUBD, VW>(nxt, a.d, t + G, tx, ty, NW);
         dec_issue<SUBE, VW>(given, a.g, t + G, tx, ty, NW);
         cur = nxt;
+    }
+}
+
+// ---- DISTORTION MAP ---------------------------------------------------------------------------------
+// k_distortion's four words per plane for every B x B block of luma pixels (B = 16, 32 or 64; a 4:2:0 chroma plane: the samples
+// co-sited with them): map[(((f * nby + by) * nbx + bx) * 3 + p) * 4 + k].  Front end, given-plane prefetch and comparison are
+// k_distortion's; what differs is the accumulation in space, and it has an owner for every word: a workgroup owns whole blocks and
+// writes their words with plain stores -- no global atomic, no memset in front of the launch, every word written exactly once.
+//   - A MAP TILE is S = B / (2 NW) vertically consecutive standard tiles (64 VW pixels x 2 NW rows) of one frame: 64 VW / B blocks
+//     side by side, whole.  The workgroup walks its sub-tiles with enc_load / dec_issue (map_subtile names them; one past the last
+//     tile row of a frame is never formed), the lanes keep their sums across the S steps (DistBlockAcc).
+//   - At the end of a map tile the B / VW adjacent lanes that hold a block's columns add up among themselves (map_lanes_meet: DPP
+//     within a row of 16 lanes, one swizzle for 32), the first lane of each group adds into the block's 12 words of LDS, where the
+//     NW waves meet, and after a barrier the workgroup stores the tile's blocks that lie inside the map -- contiguous words -- and
+//     clears them for the next map tile.
+// Integers throughout: the map does not depend on the launch shape.
+struct DistMapArgs {
+    EncArgs e;         // as DistArgs::e
+    DecArgs g;         // as DistArgs::g
+    uint64_t *map;     // [nframes][nby][nbx][3 planes][sse, sad, max_abs, n_differ]; needs no zeroing
+    int B, S;          // block size in luma pixels; sub-tiles per map tile, B / (2 NW) >= 1 (the host clamps the workgroup)
+    int nbx, nby;      // blocks per frame: ceil(w / B), ceil(h / B)
+    int mapTilesPerFrame, totalMapTiles;   // nby * e.g.tilesX, * nframes
+};
+
+// a lane's share of ONE block: at most 64 rows x 4 columns, so only the squares need 64 bits -- and so do their sums over a block
+struct DistBlockAcc {
+    uint64_t sse[3];
+    uint32_t sad[3], mx[3], nd[3];
+    LH_DEVS DistBlockAcc() { reset(); }
+    LH_DEVS void reset()
+    {
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            sse[p] = 0;
+            sad[p] = mx[p] = nd[p] = 0;
+        }
+    }
+};
+
+constexpr int DIST_MAP_LDS_WORDS = 16 * 12;   // 64 VW / B <= 16 blocks per map tile
+
+// the map's LDS words, zeroed (as dist_words: before stage_tables, which synchronises; force-inlined, the array is the kernel's)
+LH_DEV unsigned long long *dist_map_words()
+{
+    __shared__ unsigned long long s_map[DIST_MAP_LDS_WORDS];
+    for (int i = threadIdx.x; i < DIST_MAP_LDS_WORDS; i += blockDim.x)
+        s_map[i] = 0;
+    return s_map;
+}
+
+// Standard tile of sub-tile s of map tile m in the frame-major geometry, or totalTiles ("no tile" to enc_load / dec_issue) past
+// the last map tile and past the frame's last tile row (h not a multiple of B: the last block row has fewer sub-tiles).  Scalar.
+LH_DEV int map_subtile(const DistMapArgs &a, int m, int s)
+{
+    if (m >= a.totalMapTiles)
+        return a.e.g.totalTiles;
+    const int f = m / a.mapTilesPerFrame, r = m - f * a.mapTilesPerFrame;
+    const int by = r / a.e.g.tilesX, bx = r - by * a.e.g.tilesX;
+    const int row = by * a.S + s;
+    if (row >= a.e.g.tilesY)
+        return a.e.g.totalTiles;
+    return f * a.e.g.tilesPerFrame + row * a.e.g.tilesX + bx;
+}
+
+template <int CTRL>
+LH_DEV uint32_t dpp_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); }
+// v of the lane 16 away within each half of the wave (bit-mask swizzle: and 0x1f, or 0, xor 0x10); moves no LDS data
+LH_DEV uint32_t swz16_lane(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401f); }
+
+// one step of the meeting of a block's lanes: every lane takes in the sums of the lane Xch names
+template <typename Xch>
+LH_DEV void map_lanes_step(DistBlockAcc &acc, Xch xch)
+{
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const uint32_t lo = xch((uint32_t)acc.sse[p]), hi = xch((uint32_t)(acc.sse[p] >> 32));
+        acc.sse[p] += ((uint64_t)hi << 32) | lo;
+        acc.sad[p] += xch(acc.sad[p]);
+        const uint32_t m = xch(acc.mx[p]);
+        acc.mx[p] = m > acc.mx[p] ? m : acc.mx[p];
+        acc.nd[p] += xch(acc.nd[p]);
+    }
+}
+
+// The `lanes` (4, 8, 16 or 32; uniform) adjacent lanes of a block, aligned to that count: afterwards every one of them holds the
+// block's sums over this wave's rows.  Pairs, then quads (quad_perm), the other quad of eight (row_half_mirror: its lanes hold the
+// same sums by then), the other eight of a row (row_mirror), the other row of 32
+LH_DEV void map_lanes_meet(DistBlockAcc &acc, int lanes)
+{
+    map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0xb1>(v); });   // quad_perm [1, 0, 3, 2]
+    map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x4e>(v); });   // quad_perm [2, 3, 0, 1]
+    if (lanes >= 8)
+        map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x141>(v); });   // row_half_mirror
+    if (lanes >= 16)
+        map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x140>(v); });   // row_mirror
+    if (lanes >= 32)
+        map_lanes_step(acc, [](uint32_t v) { return swz16_lane(v); });
+}
+
+// The end of map tile m, called by every thread of the workgroup at the same point (m is workgroup-uniform): lanes, waves, stores.
+template <int VW>
+LH_DEV void dist_map_flush(DistBlockAcc &acc, unsigned long long *s_map, const DistMapArgs &a, int m, int tx)
+{
+    const int lanes = a.B / VW;                    // of a wave per block: 4 ... 32, a power of two
+    const int lanes_log2 = __builtin_ctz(lanes);   // (uniform)
+    // (a wave that saw no difference anywhere has nothing to add: the words are zero already)
+    if (__builtin_amdgcn_ballot_w64((acc.nd[0] | acc.nd[1] | acc.nd[2]) != 0) != 0) {
+#ifndef LH_MAP_LANES_TO_LDS   // (defined: the other side of DESIGN.md 3.9's A/B -- every lane adds into LDS itself)
+        map_lanes_meet(acc, lanes);
+        if ((tx & (lanes - 1)) == 0)
+#endif
+        {
+            unsigned long long *w = s_map + (tx >> lanes_log2) * 12;
+#pragma unroll
+            for (int p = 0; p < 3; p++)
+                if (acc.nd[p] != 0) {
+                    atomicAdd(&w[4 * p + 0], (unsigned long long)acc.sse[p]);
+                    atomicAdd(&w[4 * p + 1], (unsigned long long)acc.sad[p]);
+                    atomicMax(&w[4 * p + 2], (unsigned long long)acc.mx[p]);
+                    atomicAdd(&w[4 * p + 3], (unsigned long long)acc.nd[p]);
+                }
+        }
+    }
+    __syncthreads();
+    const int f = m / a.mapTilesPerFrame, r = m - f * a.mapTilesPerFrame;
+    const int by = r / a.e.g.tilesX, bx = r - by * a.e.g.tilesX;
+    const int b0 = bx * (64 >> lanes_log2);          // the tile's first block: inside the map, as the tile is
+    const int nb = min(64 >> lanes_log2, a.nbx - b0);   // (blocks past nbx hold no pixel: their words stayed zero)
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(a.map) + (((size_t)f * a.nby + by) * a.nbx + b0) * 12;
+    for (int i = threadIdx.x; i < nb * 12; i += blockDim.x) {
+        dst[i] = s_map[i];
+        s_map[i] = 0;
+    }
+    __syncthreads();
+}
+
+// k_distortion's variants and register budget.  The loop is k_distortion's over the sub-tiles of the workgroup's map tiles: the
+// loads of the next sub-tile -- of the next map tile behind the last one -- are issued before the flush, so they are in flight
+// across its barriers.
+template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void k_distortion_map(const DistMapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(LM == 3 || LM == 7 || LM == 5 || LM == 6, "search records in LDS");
+    unsigned long long *const s_map = dist_map_words();
+    stage_tables<FrameFront<CS, LM>::WHAT>(smem, a.e.q, a.e.half);
+    const FrameFront<CS, LM> fr(smem, a.e);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    DistBlockAcc acc;
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    EncUnit<VW> u;
+    DecRaw<SUB, VW> given;
+    int m = blockIdx.x, s = 0;
+    {
+        const int t = map_subtile(a, m, 0);
+        enc_load<VW, IN16>(u, a.e, t, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
+    }
+    while (m < a.totalMapTiles) {   // workgroup-uniform
+        if (u.valid) {
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CS, VW, LM == 5 || LM == 6, LM == 6, false>(u, a.e, fr.k, c0, c1, c2, st, fr.s_half);
+            const DistMeasureUnit<SUB, VW, DistBlockAcc> out{given, a.g, acc, mask};
+            enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), fr.s_rec, out);   // (record searches: no table pointer)
+        }
+        const bool last = s + 1 == a.S;
+        const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
+        const int t = map_subtile(a, mn, sn);
+        enc_load<VW, IN16>(u, a.e, t, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
+        if (last) {
+            dist_map_flush<VW>(acc, s_map, a, m, tx);
+            acc.reset();
+        }
+        m = mn;
+        s = sn;
     }
 }
 

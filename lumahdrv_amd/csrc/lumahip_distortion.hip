@@ -10,82 +10,109 @@ using namespace lhost;
 
 namespace lhost {
 
-int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out, const DistortionLaunch &o)
+int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, size_t out_bytes, unsigned map_block,
+                    hipStream_t stream, DistortionPlan &p)
 {
+    const char *const what = map_block ? "distortion map" : "distortion";
+    const char *const out_name = map_block ? "map_dev" : "out_dev";
     const bool in16 = f.elem == Elem::F16;
     const unsigned nframes = f.nframes, w = f.w, h = f.h;
     const int profile = given.profile;
     if (!f.plane[0] || !f.plane[1] || !f.plane[2] || !given.planes || !given.stride || !given.pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    for (int p = 0; p < 3; p++)
-        if (!given.planes[p])
-            return fail(c, LUMAHIP_ERR_ARG, "null plane %d", p);
+    for (int k = 0; k < 3; k++)
+        if (!given.planes[k])
+            return fail(c, LUMAHIP_ERR_ARG, "null plane %d", k);
     const int cs = c->q.cs;
     int rc = check_geom(c, w, h, profile, cs);
     if (rc)
         return rc;
     if ((rc = check_layout(c, f, true, given.stride, given.pfs, profile)))
         return rc;
-    if ((rc = check_out_words(c, out)))
+    if (map_block) {
+        if (!out || !is_aligned(out, 8))
+            return fail(c, LUMAHIP_ERR_ARG, "map_dev must be non-null and 8-byte aligned");
+    } else if ((rc = check_out_words(c, out))) {
         return rc;
+    }
     const size_t esz = elem_size(f.elem);
     bool al4;
     if ((rc = check_frame_alignment(c, f, esz, &al4)))
         return rc;
-    // out_dev may not share a byte with anything the launch reads
+    // the words may not share a byte with anything the launch reads
     const size_t frame_span = ((size_t)(nframes - 1) * f.frame_stride + (size_t)w * h) * esz;
-    for (int p = 0; p < 3; p++) {
-        if (ranges_overlap((uintptr_t)out, out_words_bytes(nframes), (uintptr_t)f.plane[p], frame_span))
-            return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps colour plane %d of the frames", p);
-        if (out_overlaps_plane(out, given, p, w, h, nframes))
-            return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps given plane %d", p);
+    for (int k = 0; k < 3; k++) {
+        if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)f.plane[k], frame_span))
+            return fail(c, LUMAHIP_ERR_ARG, "%s overlaps colour plane %d of the frames", out_name, k);
+        if (out_overlaps_plane(out, out_bytes, given, k, w, h, nframes))
+            return fail(c, LUMAHIP_ERR_ARG, "%s overlaps given plane %d", out_name, k);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = ensure_search_index(c, o.stream)))
+    if ((rc = ensure_search_index(c, stream)))
         return rc;
     // ---- the supported set: the search records in LDS (the composite records of YCbCr exist only beside float-bit records in LDS)
     const int mode = c->q.mode;
     if (mode != LUT_THRESH_LDS && mode != LUT_LINKEY_LDS)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "distortion: the search records must be in LDS (search mode %d)", mode);
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the search records must be in LDS (search mode %d)", what, mode);
     // the kernel, from the arguments alone: YCbCr float frames -> the composite records; YCbCr binary16 frames -> + the half-input
     // table whenever it exists for (sc, Lmax) and lumahip_tune("half_table") is not 0, else the general kernel (as the encode calls)
     bool ycode = !in16 && ycbcr_composite_ready(c);
     const float *half = nullptr;
-    if (in16 && ycbcr_composite_ready(c) && c->half_mode != 0 && lds_bytes(c, true, cs, true, true) + 128 <= LUMAHIP_LDS_PER_WORKGROUP) {
+    // (+ the words the waves of a workgroup meet in: 12, or the blocks of a map tile)
+    const size_t meet = map_block ? DIST_MAP_LDS_WORDS * sizeof(uint64_t) : 128;
+    if (in16 && ycbcr_composite_ready(c) && c->half_mode != 0 && lds_bytes(c, true, cs, true, true) + meet <= LUMAHIP_LDS_PER_WORKGROUP) {
         if ((rc = half_table_for(c, sc, &half)))
             return rc;
         ycode = half != nullptr;
     }
     const size_t lds = lds_bytes(c, true, cs, ycode, half != nullptr);
-    if (lds + 128 > LUMAHIP_LDS_PER_WORKGROUP)   // (+ the 12 words the waves of a workgroup meet in)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "distortion: the tables take %zu bytes of LDS, a workgroup has %zu", lds, LUMAHIP_LDS_PER_WORKGROUP);
+    if (lds + meet > LUMAHIP_LDS_PER_WORKGROUP)
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the tables take %zu bytes of LDS, a workgroup has %zu", what, lds, LUMAHIP_LDS_PER_WORKGROUP);
 
-    const bool sub = (profile == 0 || profile == 2);
+    p.cs = cs;
+    p.in16 = in16;
+    p.sub = (profile == 0 || profile == 2);
     // four pixels per thread and row where the frames allow the 16 / 8-byte loads (the given planes fall back to byte loads by
     // themselves: DecArgs::aligned), else two
-    const int vw = al4 ? 4 : 2;
+    p.vw = al4 ? 4 : 2;
     const bool long_launch = (unsigned long long)w * h * nframes >= 60000000ull;   // as the encode dispatch
-    const int threads = block_threads_for(c, lds, long_launch && cs != CS_YCBCR, cs == CS_YCBCR && !half);
-    DistArgs a{};
-    if (!make_geom(a.e.g, w, h, vw, threads / 64, nframes))
+    p.threads = block_threads_for(c, lds, long_launch && cs != CS_YCBCR, cs == CS_YCBCR && !half);
+    // the map: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
+    if (map_block && p.threads > 64 * (int)map_block / 2)
+        p.threads = 64 * (int)map_block / 2;
+    p.lds = lds;
+    p.e = EncArgs{};
+    p.g = DecArgs{};
+    if (!make_geom(p.e.g, w, h, p.vw, p.threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
-    a.g.g = a.e.g;
-    a.e.q = ycode ? c->q_y : c->q;
-    a.e.q.cs = cs;
-    a.e.half = half;
+    p.g.g = p.e.g;
+    p.e.q = ycode ? c->q_y : c->q;
+    p.e.q.cs = cs;
+    p.e.half = half;
     for (int k = 0; k < 3; k++)
-        a.e.src[k] = static_cast<const float *>(f.plane[k]);   // (the IN16 kernels read the same pointers as halves: encode_frames_device_impl)
-    a.e.frame_stride = f.frame_stride;
-    a.e.sc = sc;
-    read_planes(a.g, given, vw);
-    a.e.bps = a.g.bps;
+        p.e.src[k] = static_cast<const float *>(f.plane[k]);   // (the IN16 kernels read the same pointers as halves: encode_frames_device_impl)
+    p.e.frame_stride = f.frame_stride;
+    p.e.sc = sc;
+    read_planes(p.g, given, p.vw);
+    p.e.bps = p.g.bps;
+    p.kmode = half ? 6 : ycode ? 5 : mode;
+    p.grid = grid_for(c, p.threads, p.e.g.totalTiles, 0, 0, half ? 2 : cs == CS_YCBCR ? 1 : 0);
+    return LUMAHIP_OK;
+}
+
+int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out, const DistortionLaunch &o)
+{
+    DistortionPlan p;
+    if (int rc = distortion_plan(c, f, sc, given, out, out_words_bytes(f.nframes), 0, o.stream, p))
+        return rc;
+    DistArgs a{};
+    a.e = p.e;
+    a.g = p.g;
     a.out = out;
-    const int kmode = half ? 6 : ycode ? 5 : mode;
-    const dist_kernel_t kern = in16 ? pick_dist_f16(cs, sub, vw, kmode) : pick_dist<false>(cs, sub, vw, kmode);
+    const dist_kernel_t kern = p.in16 ? pick_dist_f16(p.cs, p.sub, p.vw, p.kmode) : pick_dist<DistFamily, false>(p.cs, p.sub, p.vw, p.kmode);
     if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no distortion kernel for colour space %d%s", cs, in16 ? " with binary16 frames" : "");
-    const int grid = grid_for(c, threads, a.e.g.totalTiles, 0, 0, half ? 2 : cs == CS_YCBCR ? 1 : 0);
-    return launch_measuring(c, kern, grid, threads, lds, launch_stream(c, o.stream, o.lanes), a, nframes);
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no distortion kernel for colour space %d%s", p.cs, p.in16 ? " with binary16 frames" : "");
+    return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, f.nframes);
 }
 
 }  // namespace lhost

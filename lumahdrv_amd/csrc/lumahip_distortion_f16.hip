@@ -8,7 +8,7 @@ using namespace lh;
 using namespace lhost;
 
 namespace lhost {
-dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode) { return pick_dist<true>(cs, sub, vw, mode); }
+dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode) { return pick_dist<DistFamily, true>(cs, sub, vw, mode); }
 }  // namespace lhost
 
 extern "C" int lumahip_distortion_frames_device_f16(lumahip_ctx *c, const uint16_t *rgb, size_t frame_stride, unsigned nframes, unsigned w,

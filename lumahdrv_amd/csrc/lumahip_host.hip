@@ -1010,9 +1010,9 @@ struct StagedPlanes {
 };
 
 // What those calls open with, after their null checks: the geometry against the target-side set `tgt`, the source set's profile and
-// quantizer (src = nullptr: frames in, one set), both layouts, d_planes large enough for [src][tgt] and -- words -- d_arr for the 12
-// words of a measuring call
-static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes &tgt, bool words)
+// quantizer (src = nullptr: frames in, one set), both layouts, d_planes large enough for [src][tgt] and d_arr for the `words`
+// 64-bit words of a measuring call (12; a map's; 0: none)
+static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes &tgt, size_t words)
 {
     int rc = check_geom(c, w, h, tgt.profile, c->q.cs);
     if (rc)
@@ -1035,7 +1035,7 @@ static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *
         total += s->L.total;
     }
     if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, total)) ||
-        (words && (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, 12 * sizeof(uint64_t)))))
+        (words && (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, words * sizeof(uint64_t)))))
         return rc;
     size_t off = 0;
     for (StagedPlanes *s : sets) {
@@ -1076,7 +1076,7 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
     if (!src_planes || !src_stride || !dst_planes || !dst_stride)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, dst{"destination ", dst_planes, dst_stride, dst_profile};
-    int rc = planes_staging(c, w, h, &src, dst, false);
+    int rc = planes_staging(c, w, h, &src, dst, 0);
     if (rc)
         return rc;
     if (!c->d_stats)
@@ -1114,13 +1114,41 @@ extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, u
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     StagedPlanes given{"", planes, stride, profile};
     const size_t nfl = (size_t)3 * w * h;
-    int rc = planes_staging(c, w, h, nullptr, given, true);
+    int rc = planes_staging(c, w, h, nullptr, given, 12);
     if (rc || (rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
         (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
         (rc = distortion_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), reinterpret_cast<uint64_t *>(c->d_arr),
                               {c->stream, false})))
         return rc;
     return words_down(c, out);
+}
+
+// ... -> the frame's distortion map (lumahip_distortion_map.hip): nbx * nby * 12 words, synchronously
+extern "C" int lumahip_distortion_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                                 const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *map,
+                                                 size_t map_words)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!rgb || !planes || !stride || !map)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (!dist_map_block_ok(block))
+        return fail(c, LUMAHIP_ERR_ARG, "distortion map: block must be 16, 32 or 64 (got %u)", block);
+    StagedPlanes given{"", planes, stride, profile};
+    const size_t nfl = (size_t)3 * w * h, words = dist_map_words(w, h, block);
+    int rc = planes_staging(c, w, h, nullptr, given, words);
+    if (rc)
+        return rc;
+    if (map_words < words)
+        return fail(c, LUMAHIP_ERR_ARG, "distortion map: %zu words for a map of %zu", map_words, words);
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
+        (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
+        (rc = distortion_map_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), block,
+                                  reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})) ||
+        (rc = xfer_d2h(c, map, c->d_arr, words * sizeof(uint64_t), c->stream)))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LUMAHIP_OK;
 }
 
 // Source planes and given planes in host memory -> the 12 words of the transcode distortion (lumahip_transcode_distortion.hip),
@@ -1135,7 +1163,7 @@ extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const uns
     if (!src_planes || !src_stride || !given_planes || !given_stride || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
-    int rc = planes_staging(c, w, h, &src, given, true);
+    int rc = planes_staging(c, w, h, &src, given, 12);
     if (rc || (rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
         (rc = transcode_distortion_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
         return rc;

@@ -16,8 +16,10 @@
 //   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
 //                       be, for this unit and the next --, the transcode dispatch and its two entry points
 //   lumahip_transcode_distortion.hip  pick_planes<TransDistFamily, .> (every k_transcode_distortion), its dispatch and device entry point
-//   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<false> / pick_dist<true> (every k_distortion), the distortion
-//                       dispatch and the _device entry points
+//   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<DistFamily, false / true> (every k_distortion), distortion_plan -- what a launch that scores given
+//                       planes against frames may be, for these units and the next --, the distortion dispatch and the _device entry points
+//   lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip  pick_dist<DistMapFamily, .> (every k_distortion_map), the map's dispatch
+//                       and its _device entry points
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -429,9 +431,10 @@ static inline int check_out_words(lumahip_ctx *c, const uint64_t *out)
     return (!out || !is_aligned(out, 8)) ? fail(c, LUMAHIP_ERR_ARG, "out_dev must be non-null and 8-byte aligned") : LUMAHIP_OK;
 }
 // out_dev may not share a byte with anything the launch reads: here, plane k of a set of code planes over the batch
-static inline bool out_overlaps_plane(const uint64_t *out, const SrcPlanes &p, int k, unsigned w, unsigned h, unsigned nframes)
+// (out_bytes: out_words_bytes(nframes), or the bytes of a distortion map)
+static inline bool out_overlaps_plane(const uint64_t *out, size_t out_bytes, const SrcPlanes &p, int k, unsigned w, unsigned h, unsigned nframes)
 {
-    return ranges_overlap((uintptr_t)out, out_words_bytes(nframes), (uintptr_t)p.planes[k], plane_extent(w, h, p.profile, k, p.stride[k], p.pfs[k], nframes));
+    return ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)p.planes[k], plane_extent(w, h, p.profile, k, p.stride[k], p.pfs[k], nframes));
 }
 // every base, stride and frame stride of these planes takes the vector accesses of VW pixels per thread and row
 template <typename B>
@@ -529,7 +532,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 
-// ---- lumahip_distortion.hip / lumahip_distortion_f16.hip: pick_dist<false> / pick_dist<true> of lumahip_pick.hpp (every
+// ---- lumahip_distortion.hip / lumahip_distortion_f16.hip: pick_dist<DistFamily, false / true> of lumahip_pick.hpp (every
 // k_distortion; the binary16-frame ones compile side by side with the float ones and are exported as pick_dist_f16)
 struct DistortionLaunch {
     hipStream_t stream;
@@ -539,6 +542,30 @@ struct DistortionLaunch {
 int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out_dev, const DistortionLaunch &o);
 typedef void (*dist_kernel_t)(const lh::DistArgs);
 dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode);
+// What distortion_plan decides for a launch that scores given planes against the frames' encode: the kernel's key as pick_dist
+// takes it, the launch shape and the kernel arguments of both sides
+struct DistortionPlan {
+    int cs, kmode, vw, threads, grid;
+    bool sub, in16;
+    size_t lds;      // dynamic LDS of the launch (the words the waves meet in are static and counted in the budget)
+    lh::EncArgs e;   // DistArgs::e
+    lh::DecArgs g;   // DistArgs::g
+};
+// out: the launch's words (non-null, 8-byte aligned, out_bytes of them sharing no byte with the frames or the given planes);
+// map_block: 0 = the 12 words per frame, else the block size of the distortion map -- 16, 32 or 64 -- whose kernels meet in
+// lh::DIST_MAP_LDS_WORDS of LDS and whose workgroup is clamped to a power of two of at most 64 * map_block / 2 threads (a map tile
+// is a whole number of standard tiles).  Every error is raised here, before anything of the launch is queued.
+int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, size_t out_bytes, unsigned map_block,
+                    hipStream_t stream, DistortionPlan &p);
+
+// ---- lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip: pick_dist<DistMapFamily, false / true> of lumahip_pick.hpp (every
+// k_distortion_map; the binary16-frame ones are exported as pick_dist_map_f16)
+// the same comparison per block x block luma pixels: nframes * nby * nbx * 12 words at map_dev, every one written by the launch
+int distortion_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *map_dev, const DistortionLaunch &o);
+typedef void (*dist_map_kernel_t)(const lh::DistMapArgs);
+dist_map_kernel_t pick_dist_map_f16(int cs, bool sub, int vw, int mode);
+static inline bool dist_map_block_ok(unsigned block) { return block == 16 || block == 32 || block == 64; }
+static inline size_t dist_map_words(unsigned w, unsigned h, unsigned block) { return (size_t)((w + block - 1) / block) * ((h + block - 1) / block) * 12; }
 
 // ---- lumahip_transcode_distortion.hip: pick_planes<TransDistFamily, .> of lumahip_pick.hpp (every k_transcode_distortion)
 // the source planes' transcode (transcode_impl's planes, never written) against the given planes: 12 words per frame at out_dev

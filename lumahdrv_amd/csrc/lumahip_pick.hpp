@@ -1,11 +1,12 @@
 // lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / k_decode / k_transcode / k_distortion /
-// k_transcode_distortion, luma_kernels.hpp) a launch takes.
+// k_distortion_map / k_transcode_distortion, luma_kernels.hpp) a launch takes.
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
 // export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_planes<TransFamily, 4 | 2>;
 // lumahip_transcode_distortion.hip takes pick_planes<TransDistFamily, 4 | 2>; lumahip_distortion.hip /
-// lumahip_distortion_f16.hip take pick_dist<false> / pick_dist<true>.  Included by those eight units only.
+// lumahip_distortion_f16.hip take pick_dist<DistFamily, false / true>; lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip
+// take pick_dist<DistMapFamily, false / true>.  Included by those ten units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -141,37 +142,51 @@ static typename F::kernel_t pick_planes(int csd, bool subd, int cse, bool sube, 
     return nullptr;
 }
 
-// The distortion kernels (lh::k_distortion): search records in LDS only. mode: LUT_THRESH_LDS or LUT_LINKEY_LDS, or for YCbCr
-// 5 = the composite records (float frames), 6 = the same + the half-input table (binary16 frames).  nullptr: outside that set.
-template <bool IN16, int CS, bool SUB>
-static dist_kernel_t pick_dist_cs(int vw, int mode)
+// The frame-fed measuring kernels: lh::k_distortion (DistFamily, named by lumahip_distortion.hip / lumahip_distortion_f16.hip only) and
+// lh::k_distortion_map (DistMapFamily, named by lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip only), the same keys kernel
+// for kernel.
+struct DistFamily {
+    using kernel_t = dist_kernel_t;
+    template <int CS, bool SUB, int VW, int LM, bool IN16>
+    static kernel_t kernel() { return lh::k_distortion<CS, SUB, VW, LM, IN16>; }
+};
+struct DistMapFamily {
+    using kernel_t = dist_map_kernel_t;
+    template <int CS, bool SUB, int VW, int LM, bool IN16>
+    static kernel_t kernel() { return lh::k_distortion_map<CS, SUB, VW, LM, IN16>; }
+};
+
+// Search records in LDS only.  mode: LUT_THRESH_LDS or LUT_LINKEY_LDS, or for YCbCr 5 = the composite records (float frames),
+// 6 = the same + the half-input table (binary16 frames).  nullptr: outside that set.
+template <typename F, bool IN16, int CS, bool SUB>
+static typename F::kernel_t pick_dist_cs(int vw, int mode)
 {
     using namespace lh;
     if constexpr (CS == CS_YCBCR) {
         if constexpr (!IN16) {
             if (mode == 5)
-                return vw == 4 ? k_distortion<CS, SUB, 4, 5> : k_distortion<CS, SUB, 2, 5>;
+                return vw == 4 ? F::template kernel<CS, SUB, 4, 5, false>() : F::template kernel<CS, SUB, 2, 5, false>();
         } else {
             if (mode == 6)
-                return vw == 4 ? k_distortion<CS, SUB, 4, 6, true> : k_distortion<CS, SUB, 2, 6, true>;
+                return vw == 4 ? F::template kernel<CS, SUB, 4, 6, true>() : F::template kernel<CS, SUB, 2, 6, true>();
         }
     }
     if (mode == LUT_THRESH_LDS)
-        return vw == 4 ? k_distortion<CS, SUB, 4, 3, IN16> : k_distortion<CS, SUB, 2, 3, IN16>;
+        return vw == 4 ? F::template kernel<CS, SUB, 4, 3, IN16>() : F::template kernel<CS, SUB, 2, 3, IN16>();
     if (mode == LUT_LINKEY_LDS)
-        return vw == 4 ? k_distortion<CS, SUB, 4, 7, IN16> : k_distortion<CS, SUB, 2, 7, IN16>;
+        return vw == 4 ? F::template kernel<CS, SUB, 4, 7, IN16>() : F::template kernel<CS, SUB, 2, 7, IN16>();
     return nullptr;
 }
 
-template <bool IN16>
-static dist_kernel_t pick_dist(int cs, bool sub, int vw, int mode)
+template <typename F, bool IN16>
+static typename F::kernel_t pick_dist(int cs, bool sub, int vw, int mode)
 {
     using namespace lh;
     switch (cs) {
-    case CS_LUV: return sub ? pick_dist_cs<IN16, CS_LUV, true>(vw, mode) : pick_dist_cs<IN16, CS_LUV, false>(vw, mode);
-    case CS_RGB: return sub ? pick_dist_cs<IN16, CS_RGB, true>(vw, mode) : pick_dist_cs<IN16, CS_RGB, false>(vw, mode);
-    case CS_YCBCR: return sub ? pick_dist_cs<IN16, CS_YCBCR, true>(vw, mode) : pick_dist_cs<IN16, CS_YCBCR, false>(vw, mode);
-    case CS_XYZ: return sub ? pick_dist_cs<IN16, CS_XYZ, true>(vw, mode) : pick_dist_cs<IN16, CS_XYZ, false>(vw, mode);
+    case CS_LUV: return sub ? pick_dist_cs<F, IN16, CS_LUV, true>(vw, mode) : pick_dist_cs<F, IN16, CS_LUV, false>(vw, mode);
+    case CS_RGB: return sub ? pick_dist_cs<F, IN16, CS_RGB, true>(vw, mode) : pick_dist_cs<F, IN16, CS_RGB, false>(vw, mode);
+    case CS_YCBCR: return sub ? pick_dist_cs<F, IN16, CS_YCBCR, true>(vw, mode) : pick_dist_cs<F, IN16, CS_YCBCR, false>(vw, mode);
+    case CS_XYZ: return sub ? pick_dist_cs<F, IN16, CS_XYZ, true>(vw, mode) : pick_dist_cs<F, IN16, CS_XYZ, false>(vw, mode);
     }
     return nullptr;
 }

@@ -46,9 +46,9 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
         if ((rc = check_out_words(c, out)))
             return rc;
         for (int k = 0; k < 3; k++) {
-            if (out_overlaps_plane(out, src, k, w, h, nframes))
+            if (out_overlaps_plane(out, out_words_bytes(nframes), src, k, w, h, nframes))
                 return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps source plane %d", k);
-            if (out_overlaps_plane(out, tgt, k, w, h, nframes))
+            if (out_overlaps_plane(out, out_words_bytes(nframes), tgt, k, w, h, nframes))
                 return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps given plane %d", k);
         }
     }
