@@ -44,7 +44,8 @@ extern "C" {
  *     lumahip_distortion_frames_device / _planar / _f16 / _planar_f16 and lumahip_distortion_frame_host; the transcode
  *     distortion calls lumahip_transcode_distortion_frames_device and lumahip_transcode_distortion_frame_host; the distortion
  *     map calls lumahip_distortion_map_dims, lumahip_distortion_map_frames_device / _planar / _f16 / _planar_f16 and
- *     lumahip_distortion_map_frame_host.
+ *     lumahip_distortion_map_frame_host; the transcode distortion map calls lumahip_transcode_distortion_map_frames_device and
+ *     lumahip_transcode_distortion_map_frame_host.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -486,6 +487,36 @@ int lumahip_transcode_distortion_frame_host(lumahip_ctx *ctx, const unsigned cha
                                             int src_profile, float src_sc, unsigned w, unsigned h,
                                             const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
                                             float dst_sc, uint64_t out[12]);
+
+/* Transcode distortion map: the four words of the transcode distortion calls above, per plane, for every block of `block` x `block`
+ * luma pixels (block = 16, 32 or 64) of the target instead of per frame -- the distortion map for a pipeline that holds code planes
+ * and never float frames.  One launch, no float frames, no scratch planes; e and g are exactly the transcode distortion calls'.
+ * Layout and block membership are exactly the distortion map's: with nbx = ceil(w / block), nby = ceil(h / block)
+ * (lumahip_distortion_map_dims) the words of frame f, block (bx, by), plane p are
+ *     map_dev[(((f*nby + by)*nbx + bx)*3 + p)*4 + 0..3] = sse, sad, max_abs, n_differ
+ * over the block's samples of the GIVEN planes: luma pixels [bx*block, min(w, (bx+1)*block)) x [by*block, min(h, (by+1)*block)), and
+ * on a 4:2:0 plane of dst_profile the samples co-sited with them (the source's subsampling plays no part).  The launch writes every
+ * one of the nframes*nby*nbx*12 words exactly once, zeros included: map_dev needs no initialisation and none is queued.  All
+ * arithmetic is integer: the map is the same from run to run whatever the launch shape, and summing its sse, sad and n_differ
+ * (taking the maximum of max_abs) over a frame's blocks gives that frame's 12 words of lumahip_transcode_distortion_frames_device.
+ * Arguments, supported set, stream, unordered sections and the honoured lumahip_tune keys are those of
+ * lumahip_transcode_distortion_frames_device ("block": a workgroup is at most 32 * block threads for this call, since it owns
+ * whole blocks, and at most 512 with YCbCr on either side), with map_dev (required, 8-byte aligned, its nframes*nby*nbx*96 bytes
+ * sharing no byte with either plane set; the two plane sets may overlap each other) in the place of out_dev, and the 192 words in
+ * which a workgroup's waves meet counted into its LDS beside both sides' tables.  Never waits on the host.  Errors, all before
+ * anything is launched (map_dev is then untouched): those of that call, and LUMAHIP_ERR_ARG for a block other than 16, 32 or 64
+ * and, in the host form, for map_words < nbx*nby*12.
+ * The host form uploads both plane sets of one frame, runs one launch, downloads the nbx*nby*12 words into `map` and returns
+ * synchronously. */
+int lumahip_transcode_distortion_map_frames_device(lumahip_ctx *ctx, const unsigned char *const src_planes_dev[3], const int src_stride[3],
+                                                   const size_t src_plane_frame_stride[3], int src_profile, float src_sc, unsigned nframes,
+                                                   unsigned w, unsigned h, const unsigned char *const given_planes_dev[3],
+                                                   const int given_stride[3], const size_t given_plane_frame_stride[3], int dst_profile,
+                                                   float dst_sc, unsigned block, uint64_t *map_dev);
+int lumahip_transcode_distortion_map_frame_host(lumahip_ctx *ctx, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                int src_profile, float src_sc, unsigned w, unsigned h,
+                                                const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
+                                                float dst_sc, unsigned block, uint64_t *map, size_t map_words);
 
 /* Unordered section.  Frames -- and therefore batches of frames -- are independent in this path (the quantizer is
  * read-only state, src/luma_quantizer.cpp:215-264,267-482 keep nothing between frames), so a caller with several batches to

@@ -43,6 +43,7 @@ SYMBOLS = [
     "lumahip_transcode_distortion_frames_device", "lumahip_transcode_distortion_frame_host",
     "lumahip_distortion_map_dims", "lumahip_distortion_map_frames_device", "lumahip_distortion_map_frames_device_planar",
     "lumahip_distortion_map_frames_device_f16", "lumahip_distortion_map_frames_device_planar_f16", "lumahip_distortion_map_frame_host",
+    "lumahip_transcode_distortion_map_frames_device", "lumahip_transcode_distortion_map_frame_host",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -80,7 +81,8 @@ def build_library(force: bool = False, nofastdiv: bool = False) -> str:
 KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumahip_launch.hip", "lumahip_encode.hip",
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
-                  "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip")
+                  "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
+                  "lumahip_transcode_distortion_map.hip")
 
 
 def kernel_source_sha() -> str:
@@ -187,6 +189,8 @@ def lib():
     L.lumahip_distortion_map_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
     L.lumahip_distortion_map_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, u, vp, sz]
     L.lumahip_transcode_distortion_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, vp]
+    L.lumahip_transcode_distortion_map_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, u, vp]
+    L.lumahip_transcode_distortion_map_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, u, vp, sz]
     L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
     L.lumahip_host_register.argtypes = [vp, vp, sz]
@@ -606,6 +610,20 @@ class Context:
             _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc, out.ctypes.data))
         return out
 
+    def transcode_distortion_map_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
+                                       dst_profile=2, block=16) -> np.ndarray:
+        """transcode_distortion_frame's words per block of block x block luma pixels (16, 32 or 64) of the target: a
+        (nby, nbx, 3, 4) uint64 array, in one launch; block_sample_counts(w, h, dst_profile, block) gives the samples behind each entry"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        given_planes = [np.ascontiguousarray(p) for p in given_planes]
+        nbx, nby = distortion_map_dims(w, h, block)
+        out = np.zeros((nby, nbx, 3, 4), dtype=np.uint64)
+        self._chk(self.L.lumahip_transcode_distortion_map_frame_host(
+            self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
+            _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc, block,
+            out.ctypes.data, out.size))
+        return out
+
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
         mean_lum), equal to encode_frame of the same frame widened to float32."""
@@ -768,6 +786,16 @@ class Context:
             self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides), _arr3(C.c_size_t, src_plane_frame_strides), src_profile,
             src_sc, nframes, w, h, _arr3(C.c_void_p, given_plane_ptrs), _arr3(C.c_int, given_strides),
             _arr3(C.c_size_t, given_plane_frame_strides), dst_profile, dst_sc, out_ptr))
+
+    # the same per block x block luma pixels of the target (16, 32 or 64): map_ptr receives nframes x nby x nbx x 3 planes x {sse, sad,
+    # max_abs, n_differ} as uint64, every word written by the launch
+    def transcode_distortion_map_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w,
+                                               h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, block,
+                                               map_ptr):
+        self._chk(self.L.lumahip_transcode_distortion_map_frames_device(
+            self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides), _arr3(C.c_size_t, src_plane_frame_strides), src_profile,
+            src_sc, nframes, w, h, _arr3(C.c_void_p, given_plane_ptrs), _arr3(C.c_int, given_strides),
+            _arr3(C.c_size_t, given_plane_frame_strides), dst_profile, dst_sc, block, map_ptr))
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

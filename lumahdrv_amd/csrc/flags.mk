@@ -16,6 +16,8 @@ FLAGS_lumahip_encode_f16 := $(FLAGS_lumahip_encode)
 FLAGS_lumahip_transcode :=
 #   lumahip_transcode_distortion: the transcode unit's -- its kernels are k_transcode's front end with the measuring consumer.
 FLAGS_lumahip_transcode_distortion := $(FLAGS_lumahip_transcode)
+#   lumahip_transcode_distortion_map: the same -- k_transcode_distortion_map is k_transcode_distortion with the accumulation in space.
+FLAGS_lumahip_transcode_distortion_map := $(FLAGS_lumahip_transcode)
 #   lumahip_distortion / _f16: the encode units' strategy -- k_distortion is k_encode up to the codes, with the stores replaced by
 #   integer accumulation.  Not measured either way yet.
 FLAGS_lumahip_distortion := $(FLAGS_lumahip_encode)

@@ -639,10 +639,11 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
 }
 
 // ---- THE KERNELS THAT END IN enc_codes ----------------------------------------------------------------
-// Two front ends produce a transformed unit (c0, c1, c2), two consumers take the codes enc_codes makes of it:
-//                                                        store (EncStoreUnit)   measure (DistMeasureUnit, dist_flush)
-//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion; per block: k_distortion_map
-//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion
+// Two front ends produce a transformed unit (c0, c1, c2), two consumers take the codes enc_codes makes of it, and the measuring one
+// sums per frame (DistAcc, dist_flush) or per block (DistBlockAcc, dist_map_flush):
+//                                                        store (EncStoreUnit)   measure (DistMeasureUnit)   ... per block
+//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion                k_distortion_map
+//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion      k_transcode_distortion_map
 //                   enc_transform
 // A kernel is its front end, its consumer and the persistent loop that orders their loads against each other; the loops differ on
 // purpose (stores before the next loads / the given words travelling along, one flush site) and stay written out.  Also written
@@ -1744,13 +1745,19 @@ __global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode
 //     NW waves meet, and after a barrier the workgroup stores the tile's blocks that lie inside the map -- contiguous words -- and
 //     clears them for the next map tile.
 // Integers throughout: the map does not depend on the launch shape.
+// What the map's helpers read beside the launch's frame-major FrameGeom, which they take from either front end's arguments (the
+// frame-fed kernel's is EncArgs::g, the plane-fed one's DecArgs::g)
+struct MapGeom {
+    int B, S;          // block size in luma pixels; sub-tiles per map tile, B / (2 NW) >= 1 (the host clamps the workgroup)
+    int nbx, nby;      // blocks per frame: ceil(w / B), ceil(h / B)
+    int mapTilesPerFrame, totalMapTiles;   // nby * g.tilesX, * nframes
+};
+
 struct DistMapArgs {
     EncArgs e;         // as DistArgs::e
     DecArgs g;         // as DistArgs::g
     uint64_t *map;     // [nframes][nby][nbx][3 planes][sse, sad, max_abs, n_differ]; needs no zeroing
-    int B, S;          // block size in luma pixels; sub-tiles per map tile, B / (2 NW) >= 1 (the host clamps the workgroup)
-    int nbx, nby;      // blocks per frame: ceil(w / B), ceil(h / B)
-    int mapTilesPerFrame, totalMapTiles;   // nby * e.g.tilesX, * nframes
+    MapGeom m;
 };
 
 // a lane's share of ONE block: at most 64 rows x 4 columns, so only the squares need 64 bits -- and so do their sums over a block
@@ -1779,18 +1786,18 @@ LH_DEV unsigned long long *dist_map_words()
     return s_map;
 }
 
-// Standard tile of sub-tile s of map tile m in the frame-major geometry, or totalTiles ("no tile" to enc_load / dec_issue) past
+// Standard tile of sub-tile s of map tile m in the frame-major geometry, or totalTiles ("no tile" to enc_load / dec_load / dec_issue) past
 // the last map tile and past the frame's last tile row (h not a multiple of B: the last block row has fewer sub-tiles).  Scalar.
-LH_DEV int map_subtile(const DistMapArgs &a, int m, int s)
+LH_DEV int map_subtile(const MapGeom &a, const FrameGeom &g, int m, int s)
 {
     if (m >= a.totalMapTiles)
-        return a.e.g.totalTiles;
+        return g.totalTiles;
     const int f = m / a.mapTilesPerFrame, r = m - f * a.mapTilesPerFrame;
-    const int by = r / a.e.g.tilesX, bx = r - by * a.e.g.tilesX;
+    const int by = r / g.tilesX, bx = r - by * g.tilesX;
     const int row = by * a.S + s;
-    if (row >= a.e.g.tilesY)
-        return a.e.g.totalTiles;
-    return f * a.e.g.tilesPerFrame + row * a.e.g.tilesX + bx;
+    if (row >= g.tilesY)
+        return g.totalTiles;
+    return f * g.tilesPerFrame + row * g.tilesX + bx;
 }
 
 template <int CTRL>
@@ -1830,17 +1837,14 @@ LH_DEV void map_lanes_meet(DistBlockAcc &acc, int lanes)
 
 // The end of map tile m, called by every thread of the workgroup at the same point (m is workgroup-uniform): lanes, waves, stores.
 template <int VW>
-LH_DEV void dist_map_flush(DistBlockAcc &acc, unsigned long long *s_map, const DistMapArgs &a, int m, int tx)
+LH_DEV void dist_map_flush(DistBlockAcc &acc, unsigned long long *s_map, const MapGeom &a, const FrameGeom &g, uint64_t *map, int m, int tx)
 {
     const int lanes = a.B / VW;                    // of a wave per block: 4 ... 32, a power of two
     const int lanes_log2 = __builtin_ctz(lanes);   // (uniform)
     // (a wave that saw no difference anywhere has nothing to add: the words are zero already)
     if (__builtin_amdgcn_ballot_w64((acc.nd[0] | acc.nd[1] | acc.nd[2]) != 0) != 0) {
-#ifndef LH_MAP_LANES_TO_LDS   // (defined: the other side of DESIGN.md 3.9's A/B -- every lane adds into LDS itself)
         map_lanes_meet(acc, lanes);
-        if ((tx & (lanes - 1)) == 0)
-#endif
-        {
+        if ((tx & (lanes - 1)) == 0) {   // (every lane adding into LDS itself measured no better: profiles/map_lanes_ab.txt)
             unsigned long long *w = s_map + (tx >> lanes_log2) * 12;
 #pragma unroll
             for (int p = 0; p < 3; p++)
@@ -1854,10 +1858,10 @@ LH_DEV void dist_map_flush(DistBlockAcc &acc, unsigned long long *s_map, const D
     }
     __syncthreads();
     const int f = m / a.mapTilesPerFrame, r = m - f * a.mapTilesPerFrame;
-    const int by = r / a.e.g.tilesX, bx = r - by * a.e.g.tilesX;
+    const int by = r / g.tilesX, bx = r - by * g.tilesX;
     const int b0 = bx * (64 >> lanes_log2);          // the tile's first block: inside the map, as the tile is
     const int nb = min(64 >> lanes_log2, a.nbx - b0);   // (blocks past nbx hold no pixel: their words stayed zero)
-    unsigned long long *dst = reinterpret_cast<unsigned long long *>(a.map) + (((size_t)f * a.nby + by) * a.nbx + b0) * 12;
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(map) + (((size_t)f * a.nby + by) * a.nbx + b0) * 12;
     for (int i = threadIdx.x; i < nb * 12; i += blockDim.x) {
         dst[i] = s_map[i];
         s_map[i] = 0;
@@ -1888,26 +1892,102 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
     DecRaw<SUB, VW> given;
     int m = blockIdx.x, s = 0;
     {
-        const int t = map_subtile(a, m, 0);
+        const int t = map_subtile(a.m, a.e.g, m, 0);
         enc_load<VW, IN16>(u, a.e, t, tx, ty, NW);
         dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
     }
-    while (m < a.totalMapTiles) {   // workgroup-uniform
+    while (m < a.m.totalMapTiles) {   // workgroup-uniform
         if (u.valid) {
             float c0[2 * VW], c1[2 * VW], c2[2 * VW];
             enc_transform<CS, VW, LM == 5 || LM == 6, LM == 6, false>(u, a.e, fr.k, c0, c1, c2, st, fr.s_half);
             const DistMeasureUnit<SUB, VW, DistBlockAcc> out{given, a.g, acc, mask};
             enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), fr.s_rec, out);   // (record searches: no table pointer)
         }
-        const bool last = s + 1 == a.S;
+        const bool last = s + 1 == a.m.S;
         const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
-        const int t = map_subtile(a, mn, sn);
+        const int t = map_subtile(a.m, a.e.g, mn, sn);
         enc_load<VW, IN16>(u, a.e, t, tx, ty, NW);
         dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
         if (last) {
-            dist_map_flush<VW>(acc, s_map, a, m, tx);
+            dist_map_flush<VW>(acc, s_map, a.m, a.e.g, a.map, m, tx);
             acc.reset();
         }
+        m = mn;
+        s = sn;
+    }
+}
+
+// ---- TRANSCODE DISTORTION MAP -----------------------------------------------------------------------
+// k_transcode_distortion's four words per plane for every B x B block of luma pixels of the TARGET (a 4:2:0 target plane: the
+// samples co-sited with them; the source's subsampling plays no part): k_transcode_distortion's front end and launch bound,
+// k_distortion_map's accumulation, owner per word and loop -- the next source unit and, right behind it, the next given words are
+// issued before the flush and are in flight across its barriers.  Reads 3 + 3 B per pixel (profile 2 on both sides), writes 96 B
+// per block; no float frame, no scratch planes, no global atomic, no memset.
+struct TransDistMapArgs {
+    DecArgs d;         // the source planes, as TransArgs::d
+    EncArgs e;         // the target quantizer, as TransDistArgs::e
+    DecArgs g;         // the given planes, as TransDistArgs::g
+    uint64_t *map;     // as DistMapArgs::map
+    MapGeom m;
+};
+
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode_distortion_map(const TransDistMapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *const s_map = dist_map_words();
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    DistBlockAcc acc;
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    DecUnit<SUBD, VW> cur, nxt;
+    DecRaw<SUBE, VW> given;
+    int m = blockIdx.x, s = 0;
+    {
+        const int t = map_subtile(a.m, a.d.g, m, 0);
+        dec_load<SUBD, VW>(cur, a.d, t, tx, ty, NW);
+        dec_issue<SUBE, VW>(given, a.g, t, tx, ty, NW);
+    }
+    while (m < a.m.totalMapTiles) {   // workgroup-uniform
+        if (cur.valid) {
+            EncUnit<VW> u;
+            if constexpr (Front::YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    dec_values<CSD, SUBD, VW, false, true, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+                else
+                    dec_values<CSD, SUBD, VW, false, true, false>(cur, a.d, kd, s_lut, s_uv, u.in);
+            } else {
+                dec_values<CSD, SUBD, VW, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, Front::YE, false, false>(u, a.e, ke, c0, c1, c2, st);
+            const DistMeasureUnit<SUBE, VW, DistBlockAcc> out{given, a.g, acc, mask};
+            enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+        }
+        const bool last = s + 1 == a.m.S;
+        const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
+        const int t = map_subtile(a.m, a.d.g, mn, sn);
+        dec_load<SUBD, VW>(nxt, a.d, t, tx, ty, NW);
+        dec_issue<SUBE, VW>(given, a.g, t, tx, ty, NW);
+        if (last) {
+            dist_map_flush<VW>(acc, s_map, a.m, a.d.g, a.map, m, tx);
+            acc.reset();
+        }
+        cur = nxt;
         m = mn;
         s = sn;
     }

@@ -21,17 +21,12 @@ int distortion_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcP
     a.e = p.e;
     a.g = p.g;
     a.map = map;
-    a.B = (int)block;
-    a.S = (int)block / (2 * (p.threads / 64));   // >= 1: distortion_plan has clamped the workgroup
-    a.nbx = (int)((f.w + block - 1) / block);
-    a.nby = (int)((f.h + block - 1) / block);
-    a.mapTilesPerFrame = a.nby * a.e.g.tilesX;
-    a.totalMapTiles = a.mapTilesPerFrame * (int)f.nframes;   // (<= the standard tiles, which make_geom has bounded)
+    a.m = make_map_geom(p.e.g, f.w, f.h, block, p.threads);   // (S >= 1: distortion_plan has clamped the workgroup)
     const dist_map_kernel_t kern = p.in16 ? pick_dist_map_f16(p.cs, p.sub, p.vw, p.kmode) : pick_dist<DistMapFamily, false>(p.cs, p.sub, p.vw, p.kmode);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no distortion map kernel for colour space %d%s", p.cs, p.in16 ? " with binary16 frames" : "");
     // grid_for's encode rule over the standard tiles; a workgroup takes whole map tiles
-    const int grid = p.grid < a.totalMapTiles ? p.grid : a.totalMapTiles;
+    const int grid = p.grid < a.m.totalMapTiles ? p.grid : a.m.totalMapTiles;
     if (int rc = launch_fused(c, kern, grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
         return rc;
     HIPCHK(c, hipGetLastError());

@@ -1057,10 +1057,15 @@ static int planes_up(lumahip_ctx *c, const StagedPlanes &s, unsigned h)
     return LUMAHIP_OK;
 }
 
-// what the measuring calls close with: the 12 words down (synchronises the stream)
-static int words_down(lumahip_ctx *c, uint64_t out[12])
+// what the measuring calls close with: the 12 words, or a map's, down (synchronises the stream)
+static int words_down(lumahip_ctx *c, uint64_t *out, size_t words = 12)
 {
-    return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(c->d_arr), 24, c->stream);
+    if (words == 12)
+        return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(c->d_arr), 24, c->stream);
+    if (int rc = xfer_d2h(c, out, c->d_arr, words * sizeof(uint64_t), c->stream))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LUMAHIP_OK;
 }
 
 // Source planes up, one transcode launch, destination planes down, synchronously on the context's stream; the context's plane
@@ -1144,11 +1149,9 @@ extern "C" int lumahip_distortion_map_frame_host(lumahip_ctx *c, const float *rg
     if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
         (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
         (rc = distortion_map_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), block,
-                                  reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})) ||
-        (rc = xfer_d2h(c, map, c->d_arr, words * sizeof(uint64_t), c->stream)))
+                                  reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
         return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return LUMAHIP_OK;
+    return words_down(c, map, words);
 }
 
 // Source planes and given planes in host memory -> the 12 words of the transcode distortion (lumahip_transcode_distortion.hip),
@@ -1168,6 +1171,32 @@ extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const uns
         (rc = transcode_distortion_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
         return rc;
     return words_down(c, out);
+}
+
+// ... -> the frame's transcode distortion map (lumahip_transcode_distortion_map.hip): nbx * nby * 12 words, synchronously
+extern "C" int lumahip_transcode_distortion_map_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                           int src_profile, float src_sc, unsigned w, unsigned h,
+                                                           const unsigned char *const given_planes[3], const int given_stride[3],
+                                                           int dst_profile, float dst_sc, unsigned block, uint64_t *map, size_t map_words)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!src_planes || !src_stride || !given_planes || !given_stride || !map)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (!dist_map_block_ok(block))
+        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: block must be 16, 32 or 64 (got %u)", block);
+    StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
+    const size_t words = dist_map_words(w, h, block);
+    int rc = planes_staging(c, w, h, &src, given, words);
+    if (rc)
+        return rc;
+    if (map_words < words)
+        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: %zu words for a map of %zu", map_words, words);
+    if ((rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
+        (rc = transcode_distortion_map_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, block, reinterpret_cast<uint64_t *>(c->d_arr),
+                                            {c->stream, false})))
+        return rc;
+    return words_down(c, map, words);
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the

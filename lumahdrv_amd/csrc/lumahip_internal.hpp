@@ -6,7 +6,7 @@
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which instantiation of the fused kernels a launch takes: pick_enc<IN16> / pick_dec<OUT16> / pick_dist<IN16> /
-//                       pick_planes<TransFamily | TransDistFamily, VW>, included by the eight kernel units below and by nothing else
+//                       pick_planes<TransFamily | TransDistFamily | TransDistMapFamily, VW>, included by the kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
 //                       tables next to the kernel that builds them
@@ -14,8 +14,9 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
-//                       be, for this unit and the next --, the transcode dispatch and its two entry points
+//                       be, for this unit and the next two --, the transcode dispatch and its two entry points
 //   lumahip_transcode_distortion.hip  pick_planes<TransDistFamily, .> (every k_transcode_distortion), its dispatch and device entry point
+//   lumahip_transcode_distortion_map.hip  pick_planes<TransDistMapFamily, .> (every k_transcode_distortion_map), its dispatch and device entry point
 //   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<DistFamily, false / true> (every k_distortion), distortion_plan -- what a launch that scores given
 //                       planes against frames may be, for these units and the next --, the distortion dispatch and the _device entry points
 //   lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip  pick_dist<DistMapFamily, .> (every k_distortion_map), the map's dispatch
@@ -519,16 +520,21 @@ typedef void (*trans_kernel_t)(const lh::TransArgs);
 struct TranscodePlan {
     int csd, cse, kmode, vw, threads, grid;
     bool subd, sube, any_y;
-    size_t lds;      // dynamic LDS of the launch (the measuring kernels' 12 words are static and counted in the budget)
+    size_t lds;      // dynamic LDS of the launch (the measuring kernels' words are static and counted in the budget)
     lh::DecArgs d;   // q, g, src, stride, src_frame_stride, sc, bps, aligned of the source planes
     lh::EncArgs e;   // q (the composite records for kmode 5), g, sc, bps, aligned of the target side
+    lh::MapGeom m;   // TransWhat::Map only
 };
-// measure = false: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one), out is ignored;
-// measure = true: tgt are the given planes of lumahip_transcode_distortion_frames_device (read only: any overlap with the source
+enum class TransWhat { Store, Measure, Map };
+// Store: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one), out is ignored;
+// Measure: tgt are the given planes of lumahip_transcode_distortion_frames_device (read only: any overlap with the source
 // is fine), out its 12 * nframes words (non-null, 8-byte aligned, sharing no byte with either plane set), the workgroup is
-// clamped to the measuring kernels' launch bound.  Every error is raised here, before anything of the launch is queued.
+// clamped to the measuring kernels' launch bound;
+// Map: as Measure with out = the map of lumahip_transcode_distortion_map_frames_device (its own byte count is what may not
+// overlap), map_block 16, 32 or 64, lh::DIST_MAP_LDS_WORDS of LDS to meet in, the workgroup clamped further to 32 * map_block
+// threads and the grid to the number of map tiles.  Every error is raised here, before anything of the launch is queued.
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
-                   bool measure, const uint64_t *out, hipStream_t stream, TranscodePlan &p);
+                   TransWhat mode, const uint64_t *out, unsigned map_block, hipStream_t stream, TranscodePlan &p);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 
@@ -566,12 +572,30 @@ typedef void (*dist_map_kernel_t)(const lh::DistMapArgs);
 dist_map_kernel_t pick_dist_map_f16(int cs, bool sub, int vw, int mode);
 static inline bool dist_map_block_ok(unsigned block) { return block == 16 || block == 32 || block == 64; }
 static inline size_t dist_map_words(unsigned w, unsigned h, unsigned block) { return (size_t)((w + block - 1) / block) * ((h + block - 1) / block) * 12; }
+// what the map kernels' helpers read beside g, the launch's frame-major geometry; threads = its workgroup, a power of two of at most 32 * block
+static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsigned h, unsigned block, int threads)
+{
+    lh::MapGeom m{};
+    m.B = (int)block;
+    m.S = (int)block / (2 * (threads / 64));
+    m.nbx = (int)((w + block - 1) / block);
+    m.nby = (int)((h + block - 1) / block);
+    m.mapTilesPerFrame = m.nby * g.tilesX;
+    m.totalMapTiles = m.mapTilesPerFrame * g.nframes;   // (<= the standard tiles, which make_geom has bounded)
+    return m;
+}
 
 // ---- lumahip_transcode_distortion.hip: pick_planes<TransDistFamily, .> of lumahip_pick.hpp (every k_transcode_distortion)
 // the source planes' transcode (transcode_impl's planes, never written) against the given planes: 12 words per frame at out_dev
 int transcode_distortion_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
                               float dst_sc, uint64_t *out_dev, const TranscodeLaunch &o);
 typedef void (*transdist_kernel_t)(const lh::TransDistArgs);
+
+// ---- lumahip_transcode_distortion_map.hip: pick_planes<TransDistMapFamily, .> of lumahip_pick.hpp (every k_transcode_distortion_map)
+// the same comparison per block x block luma pixels: nframes * nby * nbx * 12 words at map_dev, every one written by the launch
+int transcode_distortion_map_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
+                                  float dst_sc, unsigned block, uint64_t *map_dev, const TranscodeLaunch &o);
+typedef void (*transdist_map_kernel_t)(const lh::TransDistMapArgs);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

@@ -10,12 +10,17 @@ using namespace lhost;
 namespace lhost {
 
 // The one place that decides what a launch over (source planes, target-side planes) may be and how it runs: argument checks, the
-// supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (tgt = the planes it
-// writes; out = nullptr) and for the transcode distortion (measure: tgt = the given planes it reads, out = its words).
+// supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (TransWhat::Store: tgt =
+// the planes it writes; out = nullptr), for the transcode distortion (Measure: tgt = the given planes it reads, out = its words)
+// and for the transcode distortion map (Map: the same, out = the map of blocks of map_block luma pixels).
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
-                   bool measure, const uint64_t *out, hipStream_t stream, TranscodePlan &p)
+                   TransWhat mode, const uint64_t *out, unsigned map_block, hipStream_t stream, TranscodePlan &p)
 {
-    const char *const what = measure ? "transcode distortion" : "transcode";
+    const bool map = mode == TransWhat::Map, measure = mode != TransWhat::Store;
+    const char *const what = map ? "transcode distortion map" : measure ? "transcode distortion" : "transcode";
+    const char *const out_name = map ? "map_dev" : "out_dev";
+    if (map && !dist_map_block_ok(map_block))
+        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be 16, 32 or 64 (got %u)", what, map_block);
     if (!src.planes || !src.stride || !src.pfs || !tgt.planes || !tgt.stride || !tgt.pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     for (int k = 0; k < 3; k++)
@@ -42,14 +47,19 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                                    (uintptr_t)tgt.planes[j], plane_extent(w, h, tgt.profile, j, tgt.stride[j], tgt.pfs[j], nframes)))
                     return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
     } else {
-        // both plane sets are read only and may overlap each other; out_dev may not share a byte with anything the launch reads
-        if ((rc = check_out_words(c, out)))
+        // both plane sets are read only and may overlap each other; the words may not share a byte with anything the launch reads
+        if (map) {
+            if (!out || !is_aligned(out, 8))
+                return fail(c, LUMAHIP_ERR_ARG, "map_dev must be non-null and 8-byte aligned");
+        } else if ((rc = check_out_words(c, out))) {
             return rc;
+        }
+        const size_t out_bytes = map ? (size_t)nframes * dist_map_words(w, h, map_block) * sizeof(uint64_t) : out_words_bytes(nframes);
         for (int k = 0; k < 3; k++) {
-            if (out_overlaps_plane(out, out_words_bytes(nframes), src, k, w, h, nframes))
-                return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps source plane %d", k);
-            if (out_overlaps_plane(out, out_words_bytes(nframes), tgt, k, w, h, nframes))
-                return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps given plane %d", k);
+            if (out_overlaps_plane(out, out_bytes, src, k, w, h, nframes))
+                return fail(c, LUMAHIP_ERR_ARG, "%s overlaps source plane %d", out_name, k);
+            if (out_overlaps_plane(out, out_bytes, tgt, k, w, h, nframes))
+                return fail(c, LUMAHIP_ERR_ARG, "%s overlaps given plane %d", out_name, k);
         }
     }
     // ---- the supported set; everything else is refused here, before anything is launched
@@ -72,7 +82,8 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     // [powf tables once][source: luminance table + u'v' table | + y table + two chroma-term tables][target: records]  (k_transcode)
     const size_t lds = (any_y ? sizeof(PowfTablesWide) : 0) + lut_lds_bytes(sq.q) + (csd == CS_YCBCR ? lut_lds_bytes(sq.q) + 2 * col : col) +
                        round16((size_t)qe.nbuckets * (qe.mode == LUT_LINKEY_LDS ? 8 : 4));
-    const size_t acc_lds = measure ? 128 : 0;   // the 12 words the waves of a measuring workgroup meet in
+    // the words the waves of a measuring workgroup meet in: 12, or the blocks of a map tile
+    const size_t acc_lds = map ? DIST_MAP_LDS_WORDS * sizeof(uint64_t) : measure ? 128 : 0;
     if (lds + acc_lds > LUMAHIP_LDS_PER_WORKGROUP)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the tables of both sides take %zu bytes of LDS, a workgroup has %zu", what, lds + acc_lds,
                     LUMAHIP_LDS_PER_WORKGROUP);
@@ -91,6 +102,9 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
     // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
     p.threads = std::min(p.threads, measure ? TransDistFamily::bound(any_y) : TransFamily::bound(any_y));
+    // the map: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
+    if (map)
+        p.threads = std::min(p.threads, 32 * (int)map_block);
     p.d = DecArgs{};
     if (!make_geom(p.d.g, w, h, p.vw, p.threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
@@ -105,6 +119,11 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.e.bps = tgt.profile > 1 ? 2 : 1;
     p.e.aligned = planes_aligned(tgt, p.vw) ? 1 : 0;
     p.grid = grid_for(c, p.threads, p.d.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
+    if (map) {
+        // the launch rule over the standard tiles; a workgroup takes whole map tiles
+        p.m = make_map_geom(p.d.g, w, h, map_block, p.threads);
+        p.grid = std::min(p.grid, p.m.totalMapTiles);
+    }
     return LUMAHIP_OK;
 }
 
@@ -112,7 +131,7 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                    float *stats, const TranscodeLaunch &o)
 {
     TranscodePlan p;
-    int rc = transcode_plan(c, src, src_sc, nframes, w, h, {dst.planes, dst.stride, dst.pfs, dst.profile}, dst_sc, false, nullptr, o.stream, p);
+    int rc = transcode_plan(c, src, src_sc, nframes, w, h, {dst.planes, dst.stride, dst.pfs, dst.profile}, dst_sc, TransWhat::Store, nullptr, 0, o.stream, p);
     if (rc)
         return rc;
     TransArgs a{};

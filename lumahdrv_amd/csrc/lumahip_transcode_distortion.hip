@@ -15,7 +15,7 @@ int transcode_distortion_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc
                               float dst_sc, uint64_t *out, const TranscodeLaunch &o)
 {
     TranscodePlan p;
-    int rc = transcode_plan(c, src, src_sc, nframes, w, h, given, dst_sc, true, out, o.stream, p);
+    int rc = transcode_plan(c, src, src_sc, nframes, w, h, given, dst_sc, TransWhat::Measure, out, 0, o.stream, p);
     if (rc)
         return rc;
     TransDistArgs a{};
