@@ -1,5 +1,5 @@
-"""Code-domain distortion without a GPU: the exported symbols, code_psnr, and the numpy expectation the GPU test
-(tests/test_gpu_distortion.py) holds the kernels to -- checked here on the reference's own planes in tests/golden/ref_planes.npz:
+"""Code-domain distortion without a GPU: the exported symbols, code_psnr, and the numpy expectation (tests/support/host.py
+expected_distortion) the GPU test (tests/test_gpu_distortion.py) holds the kernels to -- checked here on the reference's own planes in tests/golden/ref_planes.npz:
 zeros for `_plane*` against itself, something else than zeros against the garbled `_dec_plane*` copies, for every key (so that
 the fixture cases of the GPU test are not vacuous)."""
 import math
@@ -8,37 +8,10 @@ import os
 import numpy as np
 import pytest
 
+from tests.support.host import expected_distortion, fixture_keys, key_parts
+
 DIST_SYMBOLS = ["lumahip_distortion_frames_device", "lumahip_distortion_frames_device_planar", "lumahip_distortion_frames_device_f16",
                 "lumahip_distortion_frames_device_planar_f16", "lumahip_distortion_frame_host"]
-
-
-def plane_samples(plane, w, h, profile, p):
-    """the samples of plane p -- a (rows, stride) uint8 array -- as a (rows, columns) integer array: one byte, or two bytes
-    little-endian, over the sample columns only"""
-    sub, bps = profile in (0, 2), 2 if profile > 1 else 1
-    rows, cols = (h // 2, w // 2) if (p and sub) else (h, w)
-    a = np.ascontiguousarray(np.asarray(plane)[:rows, :cols * bps])
-    return (a.view("<u2") if bps == 2 else a).astype(np.int64)
-
-
-def expected_distortion(planes_e, planes_g, w, h, profile):
-    """(3, 4) uint64: per plane {sum (e-g)^2, sum |e-g|, max |e-g|, #(e != g)} of two sets of three (rows, stride) uint8 planes"""
-    out = np.zeros((3, 4), dtype=np.uint64)
-    for p in range(3):
-        d = np.abs(plane_samples(planes_e[p], w, h, profile, p) - plane_samples(planes_g[p], w, h, profile, p)).astype(np.uint64)
-        out[p] = (np.sum(d * d, dtype=np.uint64), np.sum(d, dtype=np.uint64), d.max(), np.count_nonzero(d))
-    return out
-
-
-def fixture_keys(gp):
-    return sorted(k[:-3] for k in gp.files if k.endswith("_in"))
-
-
-def key_parts(key):
-    """'pq11_luv8_34x18_p2' -> ('pq11_luv8', 34, 18, 2)"""
-    name, size, prof = key.rsplit("_", 2)
-    w, h = (int(x) for x in size.split("x"))
-    return name, w, h, int(prof[1])
 
 
 def test_library_exports_the_distortion_symbols():

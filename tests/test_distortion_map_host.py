@@ -1,6 +1,6 @@
 """The distortion map without a GPU: the exported symbols, lumahip_distortion_map_dims, block_sample_counts, and the numpy
-expectation the GPU test (tests/test_gpu_distortion_map.py) holds the kernels to -- checked here against the per-frame expectation of
-tests/test_distortion_host.py on the reference's own planes in tests/golden/ref_planes.npz, and on a hand-made case that pins which
+expectation the GPU test (tests/test_gpu_distortion_map.py) holds the kernels to -- checked here against the per-frame expectation
+(both in tests/support/host.py) on the reference's own planes in tests/golden/ref_planes.npz, and on a hand-made case that pins which
 block a 4:2:0 chroma sample belongs to."""
 import ctypes as C
 import os
@@ -8,35 +8,11 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_distortion_host import expected_distortion, fixture_keys, key_parts, plane_samples
+from tests.support.host import BLOCKS, expected_distortion, expected_distortion_map, fixture_keys, fold_map, key_parts
 
 MAP_SYMBOLS = ["lumahip_distortion_map_dims", "lumahip_distortion_map_frames_device", "lumahip_distortion_map_frames_device_planar",
                "lumahip_distortion_map_frames_device_f16", "lumahip_distortion_map_frames_device_planar_f16",
                "lumahip_distortion_map_frame_host"]
-BLOCKS = (16, 32, 64)
-
-
-def expected_distortion_map(planes_e, planes_g, w, h, profile, block):
-    """(nby, nbx, 3, 4) uint64: expected_distortion per block of block x block luma pixels -- on a 4:2:0 chroma plane the
-    block/2 x block/2 samples co-sited with them -- cut at the frame's edges"""
-    nbx, nby = -(-w // block), -(-h // block)
-    out = np.zeros((nby, nbx, 3, 4), dtype=np.uint64)
-    for p in range(3):
-        b = block // 2 if (p and profile in (0, 2)) else block
-        d = np.abs(plane_samples(planes_e[p], w, h, profile, p) - plane_samples(planes_g[p], w, h, profile, p)).astype(np.uint64)
-        for by in range(nby):
-            for bx in range(nbx):
-                t = d[by * b:(by + 1) * b, bx * b:(bx + 1) * b]
-                assert t.size > 0
-                out[by, bx, p] = (np.sum(t * t, dtype=np.uint64), np.sum(t, dtype=np.uint64), t.max(), np.count_nonzero(t))
-    return out
-
-
-def fold_map(m):
-    """the (3, 4) words of a frame from its (nby, nbx, 3, 4) map: sum, sum, max, sum over the blocks"""
-    out = m.sum(axis=(0, 1), dtype=np.uint64)
-    out[:, 2] = m[:, :, :, 2].max(axis=(0, 1))
-    return out
 
 
 def test_library_exports_the_map_symbols():

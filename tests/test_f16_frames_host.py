@@ -3,7 +3,7 @@
 1. liblumahip.so exports the seven new symbols and include/lumahip.h declares them.
 2. The kernels' narrowing (lumahdrv_amd/csrc/f16_narrow.hpp), compiled by the host compilers into tests/cpp/f16_narrow_check.cpp,
    equals ExrInterface::floatToHalf for all 2^32 float bit patterns.
-3. A numpy restatement of floatToHalf (float_to_half_np, which the GPU tests use as their expectation) equals numpy's own
+3. A numpy restatement of floatToHalf (tests/support/host.py float_to_half_np, which the GPU tests use as their expectation) equals numpy's own
    float32 -> float16 conversion for non-NaN floats, on a dense sample and on every rounding boundary; its NaN rule is checked
    separately (numpy keeps a signalling NaN signalling, floatToHalf sets the quiet bit).
 """
@@ -15,47 +15,14 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.support.device import L  # noqa: F401  (the module fixture)
+from tests.support.host import float_to_half_np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 F16_SYMBOLS = ["lumahip_encode_frames_device_f16", "lumahip_encode_frames_device_planar_f16", "lumahip_decode_frames_device_f16",
                "lumahip_decode_frames_device_planar_f16", "lumahip_encode_frame_host_f16", "lumahip_decode_frame_host_f16",
                "lumahip_f16_narrow_probe_device"]
-
-
-def float_to_half_np(x) -> np.ndarray:
-    """ExrInterface::floatToHalf (lumahdrv_amd/csrc/facade/exr_interface.cpp) over a float32 array -> uint16 bit patterns"""
-    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.int64)
-    sign = (b >> 16) & 0x8000
-    e = (b >> 23) & 0xff
-    m = b & 0x7fffff
-    he = e - 127 + 15
-    out = np.zeros(b.shape, dtype=np.int64)
-    # normal results (may round up into the next binade, or to infinity)
-    r = (he << 10) | (m >> 13)
-    rem = m & 0x1fff
-    r = r + ((rem > 0x1000) | ((rem == 0x1000) & ((r & 1) == 1)))
-    normal = (he > 0) & (he < 31)
-    out[normal] = r[normal]
-    # denormal results: shift the full significand with round-to-nearest-even
-    den = (he <= 0) & (he >= -10)
-    shift = np.where(den, 14 - he, 1)
-    mm = m | 0x800000
-    q = mm >> shift
-    rr = mm & ((np.int64(1) << shift) - 1)
-    hw = np.int64(1) << (shift - 1)
-    rd = q + ((rr > hw) | ((rr == hw) & ((q & 1) == 1)))
-    out[den] = rd[den]
-    out[(he >= 31) & (e != 255)] = 0x7c00
-    special = e == 255
-    out[special] = np.where(m[special] != 0, 0x7e00 | (m[special] >> 13), 0x7c00)
-    return (out | sign).astype(np.uint16)
-
-
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    lumahdrv_amd.build_library()
-    return lumahdrv_amd
 
 
 def test_f16_symbols_exported_and_declared(L):

@@ -21,8 +21,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from tests.golden.make_golden import CONFIGS  # noqa: E402
-from tests.test_gpu_parity import L, pair, same_bits  # noqa: E402,F401  (L is the module fixture)
-from tests.test_gpu_multi import ROOT, _bench  # noqa: E402
+from tests.support.device import L, pair  # noqa: E402,F401  (L is the module fixture)
+from tests.support.host import same_bits  # noqa: E402
+from tests.support.tools import ROOT, bench  # noqa: E402
 
 
 def test_survey_testframe_digests(L, oracle_mod):
@@ -188,7 +189,7 @@ def test_config5_full_size_stream(driver, oracle_mod, tmp_path):
     # (a GPU that cannot hold its whole shard at once -- 249 GB at N = 1 -- encodes it in consecutive resident blocks: same digest)
     n = torch.cuda.device_count()
     dump = str(tmp_path / "digests.json")
-    p = _bench("--gpus", str(n), "--stream-frames", "2000", "--driver", driver, "--min-seconds", "0.2", "--dump-digests", dump)
+    p = bench("--gpus", str(n), "--stream-frames", "2000", "--driver", driver, "--min-seconds", "0.2", "--dump-digests", dump)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     assert r["n_gpus"] == n and r["digests"]["gathered_in_stream_order"] == 2000

@@ -1,7 +1,7 @@
 """Distortion map (include/lumahip.h lumahip_distortion_map_frames_device / _planar / _f16 / _planar_f16 /
 lumahip_distortion_map_frame_host): lumahip_distortion_frames_device's four words per plane for every block of 16, 32 or 64 luma
 pixels squared, written by one launch.  Every expectation is exact equality of integers
-(tests/test_distortion_map_host.py expected_distortion_map); before every call the map buffer holds the 0xC3 pattern with 16 guard
+(tests/support/host.py expected_distortion_map); before every call the map buffer holds the 0xC3 pattern with 16 guard
 words behind it, which must survive.
 
 1. The reference's planes (tests/golden/ref_planes.npz): zeros written over the fill, and numpy's map of the garbled copies.
@@ -18,91 +18,13 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_distortion_host import fixture_keys, key_parts
-from tests.test_distortion_map_host import BLOCKS, expected_distortion_map, fold_map
-from tests.test_gpu_distortion import (CFG, ENC_CASES, ERR_ARG, ERR_STATE, ERR_UNSUPPORTED, OUT_FILL, Frames, Planes, _ctx, _dev, _dist,
-                                       _encode, _frames, _from_frames, _perturb, _row_bytes)
 from tests.golden.make_golden import CONFIGS
+from tests.support.device import Frames, L, Planes, ctx, dist, dist_map, encode, from_frames, map_buf  # noqa: F401  (L is the module fixture)
+from tests.support.host import (BLOCKS, CFG, ENC_CASES, ERR_ARG, ERR_STATE, ERR_UNSUPPORTED, GUARD, MAP_SIZES, OUT_FILL, expect_map,
+                                expected_distortion_map, fixture_keys, float_frames, fold_map, key_parts, map_perturbed, map_words,
+                                neither_path_is_vacuous, nwords, perturb)
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 16
-SIZES = [(34, 18), (260, 6), (258, 6), (264, 70), (64, 32), (6, 4)]
-
-
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    return lumahdrv_amd
-
-
-def _nwords(nf, w, h, block):
-    return nf * (-(-w // block)) * (-(-h // block)) * 12
-
-
-def _map_buf(nwords):
-    import torch
-    return torch.full((nwords + GUARD,), OUT_FILL, dtype=torch.int64, device=_dev())
-
-
-def _map_words(buf, nf, w, h, block):
-    """the map of a call as (nf, nby, nbx, 3, 4) uint64, after checking the guard words behind it"""
-    a = buf.cpu().numpy()
-    assert np.all(a[-GUARD:] == OUT_FILL), "guard words behind the map"
-    return a[:-GUARD].view(np.uint64).reshape(nf, -(-h // block), -(-w // block), 3, 4)
-
-
-def _map(c, fr, sc, given, block, form="packed"):
-    import torch
-    buf = _map_buf(_nwords(fr.nf, fr.w, fr.h, block))
-    args = (fr.fs, fr.nf, fr.w, fr.h, sc, given.profile, given.ptrs, given.st, given.pfs, block, buf.data_ptr())
-    esz = fr.t.element_size() * fr.host.dtype.itemsize
-    planar = [fr.ptr + k * fr.n * esz for k in range(3)]
-    if form == "packed":
-        c.distortion_map_frames_device(fr.ptr, *args)
-    elif form == "planar":
-        c.distortion_map_frames_device_planar(planar, *args)
-    elif form == "f16":
-        c.distortion_map_frames_device_f16(fr.ptr, *args)
-    else:
-        c.distortion_map_frames_device_planar_f16(planar, *args)
-    torch.cuda.synchronize()
-    return _map_words(buf, fr.nf, fr.w, fr.h, block)
-
-
-def _expect_map(enc, ebufs, given, w, h, profile, block):
-    return np.stack([expected_distortion_map(enc.frame(ebufs, f), given.frame(given.fill, f), w, h, profile, block)
-                     for f in range(enc.nf)])
-
-
-def _perturbed(rng, enc, ebufs, w, h, profile, block):
-    """the encode call's planes, every frame perturbed densely (about half the samples, so that blocks of a few samples differ too);
-    frame 1 keeps its rightmost block column and its bottom block row as encoded"""
-    frames = []
-    bps = 2 if profile > 1 else 1
-    nbx, nby = -(-w // block), -(-h // block)
-    for f in range(enc.nf):
-        orig = enc.frame(ebufs, f)
-        g = _perturb(rng, orig, w, h, profile, frac=0.5)
-        if f == 1:
-            for p in range(3):
-                b = block // 2 if (p and profile in (0, 2)) else block
-                rb = _row_bytes(w, h, profile, p)
-                x0, y0 = (nbx - 1) * b * bps, (nby - 1) * b
-                g[p][:, x0:rb] = orig[p][:, x0:rb]
-                g[p][y0:, :rb] = orig[p][y0:, :rb]
-        frames.append(g)
-    return frames
-
-
-def _neither_path_is_vacuous(exp, w, h):
-    """asserted on the numpy expectation: with more than one block column and row, every plane has a block without a difference and at
-    least half of its blocks differ"""
-    nd = exp[:, :, :, :, 3]                       # (nf, nby, nbx, 3)
-    if nd.shape[1] > 1 and nd.shape[2] > 1:
-        for p in range(3):
-            assert (nd[..., p] == 0).any(), (w, h, p, "no block without a difference")
-            assert 2 * np.count_nonzero(nd[..., p]) >= nd[..., p].size, (w, h, p, "fewer than half the blocks differ")
 
 
 # ---- 1. the reference's planes
@@ -114,17 +36,17 @@ def test_reference_planes_and_their_garbled_copies(L, golden_dir):
         name, w, h, profile = key_parts(key)
         cfg = CONFIGS[name]
         sc = 20.0 if cfg[2] == 2 else 1.0
-        c = _ctx(L, cfg)
+        c = ctx(L, cfg)
         fr = Frames(gp[key + "_in"][None])
         pl = [gp[key + "_plane%d" % p] for p in range(3)]
         dpl = [gp[key + "_dec_plane%d" % p] for p in range(3)]
-        same = _from_frames(L, [pl], w, h, profile, strides=gp[key + "_stride"])
-        garbled = _from_frames(L, [dpl], w, h, profile, strides=gp[key + "_dec_stride"])
+        same = from_frames(L, [pl], w, h, profile, strides=gp[key + "_stride"], padding="sentinel")
+        garbled = from_frames(L, [dpl], w, h, profile, strides=gp[key + "_dec_stride"], padding="sentinel")
         for block in BLOCKS:
-            got = _map(c, fr, sc, same, block)
+            got = dist_map(c, fr, sc, same, block)
             assert not got.any(), (key, block, got)
             exp = expected_distortion_map(pl, dpl, w, h, profile, block)
-            got = _map(c, fr, sc, garbled, block)
+            got = dist_map(c, fr, sc, garbled, block)
             assert exp.any() and np.array_equal(got[0], exp), (key, block, got, exp)
 
 
@@ -133,32 +55,32 @@ def test_reference_planes_and_their_garbled_copies(L, golden_dir):
 def test_equals_numpy_on_the_encode_calls_planes(L, name):
     cfg = CFG[name]
     rng = np.random.default_rng(len(name) * 5 + cfg[1])
-    c = _ctx(L, cfg)
+    c = ctx(L, cfg)
     nf = 3
     scs = (1.0, 20.0, 0.01)
     for profile in range(4):
-        for i, (w, h) in enumerate(SIZES):
+        for i, (w, h) in enumerate(MAP_SIZES):
             sc = scs[(i + profile) % 3]
-            fr = Frames(_frames(rng, nf, w, h), pad=4 if i % 2 == 0 else 2)
-            enc, ebufs = _encode(c, L, fr, sc, profile)
+            fr = Frames(float_frames(rng, nf, w, h), pad=4 if i % 2 == 0 else 2)
+            enc, ebufs = encode(c, L, fr, sc, profile)
             assert c.quantizer_info()["mode"] in (3, 7), "the six configurations are the supported ones"
             for block in BLOCKS:
-                given = _from_frames(L, _perturbed(rng, enc, ebufs, w, h, profile, block), w, h, profile)
-                exp = _expect_map(enc, ebufs, given, w, h, profile, block)
-                _neither_path_is_vacuous(exp, w, h)
+                given = from_frames(L, map_perturbed(rng, enc, ebufs, w, h, profile, block), w, h, profile, padding="sentinel")
+                exp = expect_map(enc, ebufs, given, given.fill, block)
+                neither_path_is_vacuous(exp, (w, h))
                 assert exp[..., 3].any()
-                got = _map(c, fr, sc, given, block)
+                got = dist_map(c, fr, sc, given, block)
                 assert np.array_equal(got, exp), (name, profile, w, h, sc, block, got, exp)
-                frame_words = _dist(c, fr, sc, given)
+                frame_words = dist(c, fr, sc, given)
                 assert np.array_equal(np.stack([fold_map(m) for m in got]), frame_words), (name, profile, w, h, sc, block)
                 assert fr.unchanged() and given.unchanged()
-            assert not _map(c, fr, sc, enc, BLOCKS[(i + profile) % 3]).any(), (name, profile, w, h, sc, "its own planes")
+            assert not dist_map(c, fr, sc, enc, BLOCKS[(i + profile) % 3]).any(), (name, profile, w, h, sc, "its own planes")
             # rows the vector loads cannot take: odd strides
             if profile in (1, 2) and (w, h) in ((34, 18), (260, 6), (264, 70)):
                 block = BLOCKS[(i + profile) % 3]
-                odd = _from_frames(L, [given.frame(given.fill, f) for f in range(nf)], w, h, profile,
-                                   strides=[given.st[p] + 3 for p in range(3)])
-                assert np.array_equal(_map(c, fr, sc, odd, block), _expect_map(enc, ebufs, odd, w, h, profile, block)), \
+                odd = from_frames(L, [given.frame(given.fill, f) for f in range(nf)], w, h, profile,
+                                  strides=[given.st[p] + 3 for p in range(3)], padding="sentinel")
+                assert np.array_equal(dist_map(c, fr, sc, odd, block), expect_map(enc, ebufs, odd, odd.fill, block)), \
                     (name, profile, w, h, "odd strides")
 
 
@@ -166,22 +88,22 @@ def test_equals_numpy_on_the_encode_calls_planes(L, name):
 def test_planar_and_binary16_forms_equal_the_float_call(L, name, half_table):
     cfg = CFG[name]
     rng = np.random.default_rng(17 + half_table)
-    c = _ctx(L, cfg)
+    c = ctx(L, cfg)
     c.tune("half_table", half_table)
     nf = 3
     for profile in (2, 3, 0):
-        for i, (w, h) in enumerate(SIZES):
+        for i, (w, h) in enumerate(MAP_SIZES):
             sc = 20.0 if cfg[2] == 2 else 1.0
-            frames = _frames(rng, nf, w, h, halves=True)
+            frames = float_frames(rng, nf, w, h, halves=True)
             fr = Frames(frames)
             fr16 = Frames(frames, dtype=np.float16)
-            enc, ebufs = _encode(c, L, fr, sc, profile)
+            enc, ebufs = encode(c, L, fr, sc, profile)
             for block in BLOCKS:
-                given = _from_frames(L, _perturbed(rng, enc, ebufs, w, h, profile, block), w, h, profile)
-                exp = _expect_map(enc, ebufs, given, w, h, profile, block)
-                _neither_path_is_vacuous(exp, w, h)
+                given = from_frames(L, map_perturbed(rng, enc, ebufs, w, h, profile, block), w, h, profile, padding="sentinel")
+                exp = expect_map(enc, ebufs, given, given.fill, block)
+                neither_path_is_vacuous(exp, (w, h))
                 for form, src in (("packed", fr), ("planar", fr), ("f16", fr16), ("planar_f16", fr16)):
-                    got = _map(c, src, sc, given, block, form)
+                    got = dist_map(c, src, sc, given, block, form)
                     assert np.array_equal(got, exp), (name, half_table, profile, w, h, block, form, got, exp)
             assert fr16.unchanged()
     if cfg[2] == 2:
@@ -192,16 +114,16 @@ def test_planar_and_binary16_forms_equal_the_float_call(L, name, half_table):
 # ---- 4. the 64-bit path: one block's sum of squares is about 1.6e13
 @pytest.mark.parametrize("vw4", [True, False])
 def test_one_block_sums_beyond_32_bits(L, vw4):
-    c = _ctx(L, CFG["pq11_luv8"])
+    c = ctx(L, CFG["pq11_luv8"])
     rng = np.random.default_rng(4)
     w, h, profile = 64, 64, 2
-    fr = Frames(_frames(rng, 1, w, h), pad=4 if vw4 else 2)   # (a frame stride of 2 mod 4 floats: two pixels per thread, 32 lanes per block)
-    enc, ebufs = _encode(c, L, fr, 1.0, profile)
+    fr = Frames(float_frames(rng, 1, w, h), pad=4 if vw4 else 2)   # (a frame stride of 2 mod 4 floats: two pixels per thread, 32 lanes per block)
+    enc, ebufs = encode(c, L, fr, 1.0, profile)
     ones = Planes(L, w, h, profile, 1, fill=[np.full(enc.pfs[p], 0xFF, dtype=np.uint8) for p in range(3)])
-    exp = _expect_map(enc, ebufs, ones, w, h, profile, 64)
+    exp = expect_map(enc, ebufs, ones, ones.fill, 64)
     assert exp.shape == (1, 1, 1, 3, 4) and exp[0, 0, 0, 0, 0] > np.uint64(10) ** np.uint64(13)
     assert np.all(exp[..., 0] > np.uint64(1) << np.uint64(32))
-    got = _map(c, fr, 1.0, ones, 64)
+    got = dist_map(c, fr, 1.0, ones, 64)
     assert np.array_equal(got, exp), (got, exp)
 
 
@@ -214,7 +136,7 @@ def test_launch_shapes_give_identical_maps(L, name, profile):
     nf = 3
     shapes = {}
     for shape in ("default", "two_workgroups_of_64", "1024_threads"):
-        c = _ctx(L, cfg)
+        c = ctx(L, cfg)
         if shape == "two_workgroups_of_64":      # the persistent loop, the frame change, the most sub-tiles per map tile
             c.tune("block", 64)
             c.tune("grid_enc", 2)
@@ -222,13 +144,13 @@ def test_launch_shapes_give_identical_maps(L, name, profile):
             c.tune("block", 1024)
         shapes[shape] = c
     for (w, h) in ((264, 70), (34, 18)):
-        fr = Frames(_frames(rng, nf, w, h))
-        enc, ebufs = _encode(shapes["default"], L, fr, sc, profile)
+        fr = Frames(float_frames(rng, nf, w, h))
+        enc, ebufs = encode(shapes["default"], L, fr, sc, profile)
         for block in BLOCKS:
-            given = _from_frames(L, _perturbed(rng, enc, ebufs, w, h, profile, block), w, h, profile)
-            exp = _expect_map(enc, ebufs, given, w, h, profile, block)
+            given = from_frames(L, map_perturbed(rng, enc, ebufs, w, h, profile, block), w, h, profile, padding="sentinel")
+            exp = expect_map(enc, ebufs, given, given.fill, block)
             for shape, c in shapes.items():
-                got = _map(c, fr, sc, given, block)
+                got = dist_map(c, fr, sc, given, block)
                 assert np.array_equal(got, exp), (name, w, h, block, shape, got, exp)
 
 
@@ -238,18 +160,18 @@ def test_one_720p_frame_twice_and_in_an_unordered_section(L, name):
     import torch
     cfg = CFG[name]
     sc = 20.0 if cfg[2] == 2 else 1.0
-    c = _ctx(L, cfg)
+    c = ctx(L, cfg)
     rng = np.random.default_rng(721)
     w, h, profile, block = 1280, 720, 2, 64
-    fr = Frames(_frames(rng, 1, w, h))
-    enc, ebufs = _encode(c, L, fr, sc, profile)
-    given = _from_frames(L, _perturbed(rng, enc, ebufs, w, h, profile, block)[:1], w, h, profile)
-    exp = _expect_map(enc, ebufs, given, w, h, profile, block)
-    a = _map(c, fr, sc, given, block)
-    b = _map(c, fr, sc, given, block)
+    fr = Frames(float_frames(rng, 1, w, h))
+    enc, ebufs = encode(c, L, fr, sc, profile)
+    given = from_frames(L, map_perturbed(rng, enc, ebufs, w, h, profile, block)[:1], w, h, profile, padding="sentinel")
+    exp = expect_map(enc, ebufs, given, given.fill, block)
+    a = dist_map(c, fr, sc, given, block)
+    b = dist_map(c, fr, sc, given, block)
     assert np.array_equal(a, exp), (a, exp)
     assert np.array_equal(a, b)
-    bufs = [_map_buf(_nwords(1, w, h, block)) for _ in range(2)]
+    bufs = [map_buf(nwords(1, w, h, block)) for _ in range(2)]
     torch.cuda.synchronize()
     c.begin_unordered(2)
     for buf in bufs:
@@ -258,7 +180,7 @@ def test_one_720p_frame_twice_and_in_an_unordered_section(L, name):
     c.sync()
     torch.cuda.synchronize()
     for buf in bufs:
-        assert np.array_equal(_map_words(buf, 1, w, h, block), a)
+        assert np.array_equal(map_words(buf, 1, w, h, block), a)
     assert fr.unchanged() and given.unchanged()
 
 
@@ -269,12 +191,12 @@ def test_host_form_equals_the_device_call(L):
                                          ("pq11_luv8", 0, (264, 70), 32)):
         cfg = CFG[name]
         sc = 20.0 if cfg[2] == 2 else 1.0
-        c = _ctx(L, cfg)
-        frames = _frames(rng, 1, w, h)
+        c = ctx(L, cfg)
+        frames = float_frames(rng, 1, w, h)
         fr = Frames(frames)
-        enc, ebufs = _encode(c, L, fr, sc, profile)
-        given = _from_frames(L, [_perturb(rng, enc.frame(ebufs, 0), w, h, profile, frac=0.5)], w, h, profile)
-        dev = _map(c, fr, sc, given, block)
+        enc, ebufs = encode(c, L, fr, sc, profile)
+        given = from_frames(L, [perturb(rng, enc.frame(ebufs, 0), w, h, profile, frac=0.5)], w, h, profile, padding="sentinel")
+        dev = dist_map(c, fr, sc, given, block)
         host = c.distortion_map_frame(frames[0], given.frame(given.fill, 0), given.st, sc, profile, block)
         assert host.dtype == np.uint64 and host.shape == dev[0].shape and np.array_equal(host, dev[0]), (name, host, dev)
         assert dev.any()
@@ -285,12 +207,12 @@ def test_errors_launch_nothing(L):
     import torch
     rng = np.random.default_rng(9)
     w, h, nf, profile = 34, 18, 1, 2
-    frames = _frames(rng, nf, w, h)
+    frames = float_frames(rng, nf, w, h)
     fr = Frames(frames)
     given = Planes(L, w, h, profile, nf)
 
     def refused(c, code, w=w, block=16, map_ptr="own"):
-        buf = _map_buf(_nwords(nf, 34, 18, 16))
+        buf = map_buf(nwords(nf, 34, 18, 16))
         ptr = buf.data_ptr() if map_ptr == "own" else map_ptr(buf)
         with pytest.raises(L.LumaHipError) as ei:
             c.distortion_map_frames_device(fr.ptr, fr.fs, nf, w, h, 1.0, profile, given.ptrs, given.st, given.pfs, block, ptr)
@@ -298,10 +220,10 @@ def test_errors_launch_nothing(L):
         torch.cuda.synchronize()
         assert np.all(buf.cpu().numpy() == OUT_FILL)
 
-    good = _ctx(L, CFG["pq11_luv8"])
+    good = ctx(L, CFG["pq11_luv8"])
     for block in (8, 48, 0, 128):
         refused(good, ERR_ARG, block=block)                                         # bad block
-    refused(_ctx(L, CFG["pq11_luv8"], quantizer=False), ERR_STATE)                  # no quantizer
+    refused(ctx(L, CFG["pq11_luv8"], quantizer=False), ERR_STATE)                  # no quantizer
     refused(good, ERR_ARG, w=33)                                                    # odd size
     refused(good, ERR_ARG, map_ptr=lambda o: o.data_ptr() + 4)                      # misaligned map_dev
     refused(good, ERR_ARG, map_ptr=lambda o: None)                                  # null map_dev
@@ -310,11 +232,11 @@ def test_errors_launch_nothing(L):
     refused(good, ERR_ARG, map_ptr=lambda o: given.ptrs[1] - 200)
     refused(good, ERR_ARG, map_ptr=lambda o: fr.ptr + 8 * (w * h // 2))             # map_dev inside the frame
     refused(good, ERR_ARG, map_ptr=lambda o: fr.ptr - 200)                          # ... reaching into it
-    refused(_ctx(L, CFG["pq11_luv8"], literal=True), ERR_UNSUPPORTED)               # force_literal
-    refused(_ctx(L, CFG["pq14_luv8"]), ERR_UNSUPPORTED)                             # a 14-bit table: records in global memory
+    refused(ctx(L, CFG["pq11_luv8"], literal=True), ERR_UNSUPPORTED)               # force_literal
+    refused(ctx(L, CFG["pq14_luv8"]), ERR_UNSUPPORTED)                             # a 14-bit table: records in global memory
     # the host form: map_words one short, and a bad block
     planes = given.frame(given.fill, 0)
-    need = _nwords(1, w, h, 16)
+    need = nwords(1, w, h, 16)
     for block, words in ((16, need - 1), (8, need)):
         m = np.full(need + GUARD, OUT_FILL, dtype=np.int64)
         rc = good.L.lumahip_distortion_map_frame_host(good.h, frames[0].ctypes.data, w, h, 1.0, profile,
@@ -323,5 +245,5 @@ def test_errors_launch_nothing(L):
         assert rc == ERR_ARG and np.all(m == OUT_FILL), (block, words, rc)
     assert fr.unchanged() and given.unchanged()
     # ... and the same arguments are accepted by a context that can
-    assert _map(good, fr, 1.0, given, 16).shape == (1, 2, 3, 3, 4)
+    assert dist_map(good, fr, 1.0, given, 16).shape == (1, 2, 3, 3, 4)
     assert good.distortion_map_frame(frames[0], planes, given.st, 1.0, profile, 16).shape == (2, 3, 3, 4)

@@ -16,36 +16,15 @@ import numpy as np
 import pytest
 
 from tests.golden.make_golden import CONFIGS
-from tests.test_f16_frames_host import float_to_half_np
+from tests.support.device import L, ctx, dev  # noqa: F401  (L is the module fixture)
+from tests.support.host import float_to_half_np
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    return lumahdrv_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def _ctx(L, cfg, literal=False):
-    """a context on torch's current stream, so that its launches are ordered with the tensors' fills and copies"""
-    import torch
-    c = L.Context(0)
-    c.set_stream(torch.cuda.current_stream().cuda_stream)
-    if literal:
-        c.tune("force_literal", 1)
-    c.set_quantizer(*cfg, L.build_lut(cfg[0], cfg[1], cfg[4], cfg[5]))
-    return c
-
-
 def _tensor_u8(arrs):
     import torch
-    return [torch.from_numpy(np.ascontiguousarray(a).ravel()).to(_dev()) for a in arrs]
+    return [torch.from_numpy(np.ascontiguousarray(a).ravel()).to(dev()) for a in arrs]
 
 
 def _sc_for(cfg):
@@ -65,14 +44,14 @@ def test_decode_f16_equals_reference_lumadec_halves(L, golden_dir):
         w, h = (int(x) for x in size.split("x"))
         profile = int(prof[1])
         sc = _sc_for(cfg)
-        c = _ctx(L, cfg)
+        c = ctx(L, cfg)
         dst = tuple(int(x) for x in gp[key + "_dec_stride"])
         dpl = [gp[key + "_dec_plane%d" % p] for p in range(3)]
         exp = float_to_half_np(gp[key + "_decoded"])
         got = c.decode_frame_f16(dpl, dst, w, h, sc, profile)
         assert got.dtype == np.float16 and np.array_equal(got.view(np.uint16), exp), key
         tp = _tensor_u8(dpl)
-        out = torch.empty(3 * h * w, dtype=torch.float16, device=_dev())
+        out = torch.empty(3 * h * w, dtype=torch.float16, device=dev())
         c.decode_frames_device_f16([t.data_ptr() for t in tp], dst, [t.numel() for t in tp], 1, w, h, profile, sc,
                                    out.data_ptr(), 3 * h * w)
         c.sync()
@@ -80,7 +59,7 @@ def test_decode_f16_equals_reference_lumadec_halves(L, golden_dir):
 
 
 # ---- 2. f16 decode vs the narrowed float decode
-def _random_planes(rng, w, h, profile, nframes):
+def _random_buffers(rng, w, h, profile, nframes):
     _, hs, st, bps = L_geometry(w, h, profile)
     return [rng.integers(0, 256, size=nframes * hs[p] * st[p], dtype=np.uint8) for p in range(3)], st, \
         [hs[p] * st[p] for p in range(3)]
@@ -102,24 +81,24 @@ def test_decode_f16_equals_narrowed_float_decode(L, name):
     cfg = DEC_CONFIGS[name]
     rng = np.random.default_rng(len(name))
     seen = dict(inf=0, nan=0, den=0)
-    c = _ctx(L, cfg)
+    c = ctx(L, cfg)
     for profile in range(4):
         for (w, h) in DEC_SIZES:
             # sc 0.01 / 3e5 / 0 / NaN: results beyond 65504 (inf), in the binary16 denormal range, x / 0 and NaN
             for sc in (_sc_for(cfg), 0.01, 3e5, 0.0, float("nan")):
                 nf = 3
-                pl, st, pfs = _random_planes(rng, w, h, profile, nf)
+                pl, st, pfs = _random_buffers(rng, w, h, profile, nf)
                 tp = _tensor_u8(pl)
                 ptrs = [t.data_ptr() for t in tp]
                 n = w * h
-                ref = torch.empty(nf * 3 * n, dtype=torch.float32, device=_dev())
+                ref = torch.empty(nf * 3 * n, dtype=torch.float32, device=dev())
                 c.decode_frames_device(ptrs, st, pfs, nf, w, h, profile, sc, ref.data_ptr(), 3 * n)
                 # packed frames of halves with a frame stride of 3*n + 2 (two pixels per access; the gap must stay untouched)
                 fs = 3 * n + 2
-                o16 = torch.full((nf * fs,), 7, dtype=torch.int16, device=_dev())
+                o16 = torch.full((nf * fs,), 7, dtype=torch.int16, device=dev())
                 c.decode_frames_device_f16(ptrs, st, pfs, nf, w, h, profile, sc, o16.data_ptr(), fs)
                 # planar: three separate buffers
-                pp = [torch.empty(nf * n, dtype=torch.float16, device=_dev()) for _ in range(3)]
+                pp = [torch.empty(nf * n, dtype=torch.float16, device=dev()) for _ in range(3)]
                 c.decode_frames_device_planar_f16(ptrs, st, pfs, nf, w, h, profile, sc, [t.data_ptr() for t in pp], n)
                 c.sync()
                 r = ref.cpu().numpy()
@@ -197,12 +176,12 @@ def _encode_pair(c, frames16, w, h, profile, sc, stats, planar=False):
     n = w * h
     _, hs, st, _ = L_geometry(w, h, profile)
     sizes = [hs[p] * st[p] for p in range(3)]
-    x16 = torch.from_numpy(frames16.reshape(-1).view(np.int16).copy()).to(_dev())
-    x32 = torch.from_numpy(_widen(frames16).reshape(-1)).to(_dev())
+    x16 = torch.from_numpy(frames16.reshape(-1).view(np.int16).copy()).to(dev())
+    x32 = torch.from_numpy(_widen(frames16).reshape(-1)).to(dev())
     outs = []
     for half in (False, True):
-        pl = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=_dev()) for p in range(3)]
-        sd = torch.zeros(3 * nf, dtype=torch.float32, device=_dev()) if stats else None
+        pl = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=dev()) for p in range(3)]
+        sd = torch.zeros(3 * nf, dtype=torch.float32, device=dev()) if stats else None
         sp = sd.data_ptr() if stats else None
         pp = [t.data_ptr() for t in pl]
         if not half:
@@ -221,7 +200,7 @@ def _encode_pair(c, frames16, w, h, profile, sc, stats, planar=False):
 def test_encode_f16_equals_float_encode_and_oracle(L, oracle_mod, case):
     cfg, literal, mode = ENC_CASES[case]
     o = oracle_mod
-    c = _ctx(L, cfg, literal)
+    c = ctx(L, cfg, literal=literal)
     if mode is not None:
         assert c.quantizer_info()["mode"] == mode
     orc = o.Oracle(*cfg)
@@ -265,7 +244,7 @@ def test_ycbcr_f16_takes_the_half_table_by_type(L):
     for sc in (1.0, 20.0, 0.0):
         for stats in (False, True):
             fr = _half_frames(rng, 2, 258, 10)
-            c = _ctx(L, cfg)
+            c = ctx(L, cfg)
             (f32, f16), st, sizes, _ = _encode_pair(c, fr, 258, 10, 2, sc, stats)
             for p in range(3):
                 assert np.array_equal(f16[0][p], f32[0][p]), (sc, stats, p)
@@ -273,10 +252,10 @@ def test_ycbcr_f16_takes_the_half_table_by_type(L):
                 assert _same_stats(f16[1], f32[1]), (sc, f16[1], f32[1])
             # the f16 call alone on a fresh context: the table kernel on its first launch exactly when it exists and no
             # statistics are asked for
-            c = _ctx(L, cfg)
-            x16 = torch.from_numpy(fr.reshape(-1).view(np.int16).copy()).to(_dev())
-            pl = [torch.zeros(2 * sizes[p], dtype=torch.uint8, device=_dev()) for p in range(3)]
-            sd = torch.zeros(6, dtype=torch.float32, device=_dev())
+            c = ctx(L, cfg)
+            x16 = torch.from_numpy(fr.reshape(-1).view(np.int16).copy()).to(dev())
+            pl = [torch.zeros(2 * sizes[p], dtype=torch.uint8, device=dev()) for p in range(3)]
+            sd = torch.zeros(6, dtype=torch.float32, device=dev())
             c.encode_frames_device_f16(x16.data_ptr(), 3 * 258 * 10, 2, 258, 10, sc, 2, [t.data_ptr() for t in pl], st, sizes,
                                        sd.data_ptr() if stats else None)
             c.sync()
@@ -293,17 +272,17 @@ def test_full_size_4k(L):
     n = w * h
     for name, nf, sc in (("pq11_luv8", 8, 1.0), ("pq10_ycbcr10", 1, 20.0)):
         cfg = CONFIGS[name]
-        c = _ctx(L, cfg)
-        g = torch.Generator(device=_dev())
+        c = ctx(L, cfg)
+        g = torch.Generator(device=dev())
         g.manual_seed(3)
-        x32 = torch.exp(torch.empty(nf * 3 * n, device=_dev()).uniform_(np.log(1e-3), np.log(2e4), generator=g))
+        x32 = torch.exp(torch.empty(nf * 3 * n, device=dev()).uniform_(np.log(1e-3), np.log(2e4), generator=g))
         x16 = x32.to(torch.float16)
         x32 = x16.to(torch.float32)
         _, hs, st, _ = L_geometry(w, h, 2)
         sizes = [hs[p] * st[p] for p in range(3)]
         res = []
         for half in (False, True):
-            pl = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=_dev()) for p in range(3)]
+            pl = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=dev()) for p in range(3)]
             pp = [t.data_ptr() for t in pl]
             if half:
                 c.encode_frames_device_f16(x16.data_ptr(), 3 * n, nf, w, h, sc, 2, pp, st, sizes)
@@ -314,8 +293,8 @@ def test_full_size_4k(L):
         for p in range(3):
             assert torch.equal(res[0][p], res[1][p]), (name, p)
         pp = [t.data_ptr() for t in res[0]]
-        d32 = torch.empty(nf * 3 * n, dtype=torch.float32, device=_dev())
-        d16 = torch.empty(nf * 3 * n, dtype=torch.float16, device=_dev())
+        d32 = torch.empty(nf * 3 * n, dtype=torch.float32, device=dev())
+        d16 = torch.empty(nf * 3 * n, dtype=torch.float16, device=dev())
         c.decode_frames_device(pp, st, sizes, nf, w, h, 2, sc, d32.data_ptr(), 3 * n)
         c.decode_frames_device_f16(pp, st, sizes, nf, w, h, 2, sc, d16.data_ptr(), 3 * n)
         c.sync()
@@ -357,8 +336,8 @@ def test_device_narrowing_equals_float_to_half_for_every_float(L):
     s = torch.cuda.current_stream().cuda_stream
     c.set_stream(s)
     n = 1 << 26
-    out = torch.empty(n, dtype=torch.int16, device=_dev())
-    base = torch.arange(n, dtype=torch.int64, device=_dev())
+    out = torch.empty(n, dtype=torch.int16, device=dev())
+    base = torch.arange(n, dtype=torch.int64, device=dev())
     bad = 0
     for chunk in range(64):
         first = chunk * n
@@ -370,7 +349,7 @@ def test_device_narrowing_equals_float_to_half_for_every_float(L):
     assert bad == 0
     # and the torch port against the numpy restatement on a sample
     x = np.arange(0, 1 << 32, 65521, dtype=np.uint64).astype(np.uint32)
-    t = float_to_half_torch(torch.from_numpy(x.view(np.int32)).to(_dev())).cpu().numpy().view(np.uint16)
+    t = float_to_half_torch(torch.from_numpy(x.view(np.int32)).to(dev())).cpu().numpy().view(np.uint16)
     assert np.array_equal(t, float_to_half_np(x.view(np.float32)))
 
 
@@ -378,18 +357,18 @@ def test_device_narrowing_equals_float_to_half_for_every_float(L):
 def test_torch_float16_buffers_both_ways(L):
     import torch
     cfg = CONFIGS["pq11_luv8"]
-    c = _ctx(L, cfg)
+    c = ctx(L, cfg)
     w, h, nf = 256, 64, 2
-    x = (torch.rand(nf, 3, h, w, device=_dev()) * 1000 + 0.01).to(torch.float16)
+    x = (torch.rand(nf, 3, h, w, device=dev()) * 1000 + 0.01).to(torch.float16)
     _, hs, st, _ = L_geometry(w, h, 2)
     sizes = [hs[p] * st[p] for p in range(3)]
-    a = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=_dev()) for p in range(3)]
-    b = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=_dev()) for p in range(3)]
+    a = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=dev()) for p in range(3)]
+    b = [torch.zeros(nf * sizes[p], dtype=torch.uint8, device=dev()) for p in range(3)]
     c.encode_frames_device_f16(x.data_ptr(), 3 * w * h, nf, w, h, 1.0, 2, [t.data_ptr() for t in a], st, sizes)
     xf = x.float().contiguous()
     c.encode_frames_device(xf.data_ptr(), 3 * w * h, nf, w, h, 1.0, 2, [t.data_ptr() for t in b], st, sizes)
-    y16 = torch.empty(nf, 3, h, w, dtype=torch.float16, device=_dev())
-    y32 = torch.empty(nf, 3, h, w, dtype=torch.float32, device=_dev())
+    y16 = torch.empty(nf, 3, h, w, dtype=torch.float16, device=dev())
+    y32 = torch.empty(nf, 3, h, w, dtype=torch.float32, device=dev())
     c.decode_frames_device_f16([t.data_ptr() for t in a], st, sizes, nf, w, h, 2, 1.0, y16.data_ptr(), 3 * w * h)
     c.decode_frames_device([t.data_ptr() for t in a], st, sizes, nf, w, h, 2, 1.0, y32.data_ptr(), 3 * w * h)
     c.sync()
@@ -413,13 +392,13 @@ def test_torch_float16_buffers_both_ways(L):
 def test_f16_argument_errors(L):
     import torch
     from lumahdrv_amd import capi
-    c = _ctx(L, CONFIGS["pq11_luv8"])
+    c = ctx(L, CONFIGS["pq11_luv8"])
     w, h = 64, 16
     _, hs, st, _ = L_geometry(w, h, 2)
     sizes = [hs[p] * st[p] for p in range(3)]
-    pl = [torch.zeros(sizes[p], dtype=torch.uint8, device=_dev()) for p in range(3)]
+    pl = [torch.zeros(sizes[p], dtype=torch.uint8, device=dev()) for p in range(3)]
     pp = [t.data_ptr() for t in pl]
-    buf = torch.zeros(3 * w * h + 8, dtype=torch.float16, device=_dev())
+    buf = torch.zeros(3 * w * h + 8, dtype=torch.float16, device=dev())
     base = buf.data_ptr()
     for call in (lambda: c.encode_frames_device_f16(base + 2, 3 * w * h, 1, w, h, 1.0, 2, pp, st, sizes),
                  lambda: c.decode_frames_device_f16(pp, st, sizes, 1, w, h, 2, 1.0, base + 2, 3 * w * h),

@@ -6,16 +6,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.support.tools import build_facade_test
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_facade_test(tmp):
-    exe = os.path.join(tmp, "facade_roundtrip")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "facade_roundtrip.cpp"), "-o", exe,
-                    "-L" + os.path.join(ROOT, "lumahdrv_amd", "lib"), "-lluma_hip", "-llumahip",
-                    "-Wl,-rpath," + os.path.join(ROOT, "lumahdrv_amd", "lib")], check=True)
-    return exe
 
 
 @pytest.mark.gpu
@@ -78,7 +71,7 @@ def test_simple_enc_dec_tools_end_to_end(oracle_mod, tmp_path):
     y = np.frombuffer(body[:1280 * 720 * 2], dtype=np.uint8)
     assert o.survey_digest(y) == "e0ff09731298e8f6"
     assert np.array_equal(y.reshape(720, 2560), o.packed_rows(planes[0], 2560))
-    from tests.test_exr import read_exr_py
+    from tests.support.exr import read_exr_py
     ch, _ = read_exr_py(str(tmp_path / "dec_001.exr"))
     dec = orc.decode(planes, st, 1280, 720, 1.0, 2)
     with np.errstate(over="ignore"):
@@ -191,7 +184,7 @@ def test_lumaenc_lumadec_drivers_end_to_end(oracle_mod, tmp_path):
     for a, b in zip(_split_planes(body, w, h, prof, 0), planes):
         assert np.array_equal(a, b[:, :a.shape[1]])
     # (3)
-    from tests.test_exr import read_exr_py, write_exr_py
+    from tests.support.exr import read_exr_py, write_exr_py
     frames = {}
     for idx in (3, 5):
         f = o.synth_frame(1920, 1080, frame=idx)

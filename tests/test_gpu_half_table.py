@@ -4,6 +4,8 @@ for any mix of the two inside one wave."""
 import numpy as np
 import pytest
 
+from tests.support.host import _half_policy_model
+
 pytestmark = pytest.mark.gpu
 
 
@@ -153,38 +155,6 @@ def test_pairs_without_a_table_and_the_table_cache(oracle_mod):
         exp, _, _ = orc12.encode(f.copy(), 1.0, 3)
     for p in range(3):
         assert np.array_equal(got[p], exp[p]), p
-
-
-def _half_policy_model(kinds, lag=4, longest=1024):
-    """lumahip_core.hip lag_policy_next (LagPolicy, lumahip_internal.hpp) restated: kinds[i] = True when eligible launch i holds full-precision floats (a table launch on
-    it reports).  Returns, per launch, (table launches so far, back-off launches so far) AFTER it was issued."""
-    ON, BACKOFF, PROBE_WAIT = 0, 1, 2
-    state, left, length, pending, table, backoff, out = ON, 0, 0, [], 0, 0, []
-    for e, is_float in enumerate(kinds):
-        while pending and pending[0][0] + lag <= e:
-            _, reported, probe = pending.pop(0)
-            if state == ON and reported:
-                state, length = BACKOFF, 16
-                left = length
-            elif state == PROBE_WAIT and probe:
-                if reported:
-                    length = min(2 * max(length, 8), longest)
-                    state, left = BACKOFF, length
-                else:
-                    state, length = ON, 0
-        probe = False
-        if state == BACKOFF and left > 0:
-            left -= 1
-            backoff += 1
-        elif state == PROBE_WAIT:
-            backoff += 1
-        else:
-            if state == BACKOFF:
-                state, probe = PROBE_WAIT, True
-            pending.append((e, is_float, probe))
-            table += 1
-        out.append((table, backoff))
-    return out
 
 
 def test_float_streams_back_off_to_the_per_pixel_kernels(oracle_mod):

@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support.tools import ROOT, bench
 
 
 def _free_port():
@@ -73,17 +73,10 @@ def test_sharded_stream_drives_real_contexts_over_rccl(tmp_path, oracle_mod):
         assert np.load(tmp_path / ("rank%d.npy" % r)).tolist() == expect     # every rank holds the in-order digests
 
 
-def _bench(*flags, env=None):
-    e = dict(os.environ)
-    e.update(env or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(flags), capture_output=True, text=True, env=e, timeout=900)
-    return p
-
-
 @pytest.mark.gpu
 def test_bench_contract_single_gpu():
-    p = _bench("--full", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-other-workloads",
-               "--no-facade-hostfed")
+    p = bench("--full", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-other-workloads",
+              "--no-facade-hostfed")
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -137,7 +130,7 @@ def test_bench_plain_run_times_exactly_k_steps_and_dumps_what_they_computed(tmp_
     o = oracle_mod
     d = tmp_path / "out"
     _wait_for_hbm()
-    p = _bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
+    p = bench("--steps", "3", "--warmup", "1", "--dump-outputs", str(d))
     if p.returncode == 3:
         pytest.skip("the 500-frame resident stream does not fit this GPU's free HBM right now (bench.py exit code 3, by design): "
                     + p.stderr[-300:])
@@ -195,15 +188,15 @@ def test_bench_rccl_path_and_stream_mode():
     """the RCCL code path with the devices this box has (forced with one rank), in the 2000-frame-stream mode scaled down"""
     import torch
     n = 2 if torch.cuda.device_count() >= 2 else 1
-    p = _bench("--gpus", str(n), "--stream-frames", "37", "--frames-per-step", "8", "--width", "1280", "--height", "720",
-               "--min-seconds", "0.05", env={"LUMAHIP_BENCH_FORCE_DIST": "1"})
+    p = bench("--gpus", str(n), "--stream-frames", "37", "--frames-per-step", "8", "--width", "1280", "--height", "720",
+              "--min-seconds", "0.05", env={"LUMAHIP_BENCH_FORCE_DIST": "1"})
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     assert r["n_gpus"] == n and r["scaling"] == "strong"
     assert r["digests"]["gathered_in_stream_order"] == 37 and r["digests"]["spot_checked_by_rank0"] == 2 * n
     # the stream digest does not depend on how many ranks produced it
-    q = _bench("--gpus", "1", "--stream-frames", "37", "--frames-per-step", "5", "--width", "1280", "--height", "720",
-               "--min-seconds", "0.05")
+    q = bench("--gpus", "1", "--stream-frames", "37", "--frames-per-step", "5", "--width", "1280", "--height", "720",
+              "--min-seconds", "0.05")
     assert q.returncode == 0, q.stderr[-2000:]
     assert json.loads(q.stdout.splitlines()[-1])["digests"]["stream_digest"] == r["digests"]["stream_digest"]
 
@@ -236,11 +229,11 @@ def test_bench_under_the_launcher_at_n1_is_the_plain_run():
     torch.cuda.empty_cache()
     flags = ["--gpus", "1", "--steps", "10", "--warmup", "2", "--min-seconds", "0.3", "--no-cpu-baseline", "--no-other-workloads",
              "--no-facade-hostfed", "--no-placement-off"]
-    planned = _bench(*(flags + ["--plan-only", "--hbm-free-gb", "280"]))
+    planned = bench(*(flags + ["--plan-only", "--hbm-free-gb", "280"]))
     assert planned.returncode == 0, planned.stderr[-2000:]
     plan = json.loads(planned.stdout.strip().splitlines()[-1])
     _wait_for_hbm()
-    plain = _bench(*flags)
+    plain = bench(*flags)
     if plain.returncode == 3:
         pytest.skip("the 500-frame resident stream does not fit this GPU's free HBM right now (bench.py exit code 3, by design): "
                     + plain.stderr[-300:])
@@ -281,9 +274,9 @@ def test_bench_fails_loudly_when_the_stream_does_not_fit(tmp_path):
     try:
         flags = ["--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-other-workloads",
                  "--no-facade-hostfed", "--no-placement-off"]
-        p = _bench(*flags)
+        p = bench(*flags)
         assert p.returncode == 3 and "does not fit" in p.stderr and not [l for l in p.stdout.splitlines() if l.startswith("{")], p.stderr[-1500:]
-        q = _bench(*(flags + ["--allow-short-stream"]))
+        q = bench(*(flags + ["--allow-short-stream"]))
         assert q.returncode == 0, q.stderr[-2000:]
         r = json.loads([l for l in q.stdout.splitlines() if l.startswith("{")][-1])
         assert r["config_degraded"] is True and 20 <= r["config"]["resident_frames"] < 500 and r["config"]["resident_frames"] % 20 == 0
@@ -297,18 +290,18 @@ def test_bench_fails_loudly_when_the_stream_does_not_fit(tmp_path):
 def test_bench_refuses_more_gpus_than_visible():
     import torch
     n = torch.cuda.device_count() + 1
-    p = _bench("--gpus", str(n), "--steps", "1")
+    p = bench("--gpus", str(n), "--steps", "1")
     assert p.returncode != 0 and "visible" in (p.stderr + p.stdout)
 
 
 def test_bench_never_mislabels_world_size():
     """CPU-checkable halves of the contract: --gpus 2 with WORLD_SIZE=1 in the environment must fail (round 1 silently ran
     one rank and printed n_gpus: 1), and --gpus 2 without devices must fail instead of reporting fewer GPUs."""
-    p = _bench("--gpus", "2", "--steps", "1", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
+    p = bench("--gpus", "2", "--steps", "1", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE" in (p.stderr + p.stdout)
     import torch
     if not torch.cuda.is_available():
-        q = _bench("--gpus", "2", "--steps", "1")
+        q = bench("--gpus", "2", "--steps", "1")
         assert q.returncode != 0 and "visible" in (q.stderr + q.stdout)
 
 
@@ -316,8 +309,8 @@ def test_bench_never_mislabels_world_size():
 def test_bench_config3_encode_is_hbm_bound():
     """BASELINE configs[2] (HDR10 recipe, 4K): the synthetic stream holds binary16 values, as every EXR frame of the reference
     does, so the encode launches run on the half-input table and the line prices them against HBM; decode stays VALU-bound."""
-    p = _bench("--full", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-other-workloads",
-               "--no-facade-hostfed", "--no-placement-off", "--workload", "pq10_ycbcr")
+    p = bench("--full", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05", "--no-cpu-baseline", "--no-other-workloads",
+              "--no-facade-hostfed", "--no-placement-off", "--workload", "pq10_ycbcr")
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     rf = r["roofline"]
@@ -329,7 +322,7 @@ def test_bench_config3_encode_is_hbm_bound():
     # the other input class of this configuration: the same stream with full-precision mantissas (what the reference's PFS pipe
     # delivers, src/pfs_interface.cpp:57-113) through the DEFAULT policy -- VALU-bound, and the launches of each kind are exactly
     # what the policy's model says for a stream of that many float launches (a function of the data, not of timing)
-    from tests.test_gpu_half_table import _half_policy_model
+    from tests.support.host import _half_policy_model
     fi = r["float_inputs"]
     assert fi["value"] > 0 and fi["roofline"]["bound"] == "valu" and 0 < fi["hbm_frac"] < 1
     n = fi["table_launches"] + fi["backoff_launches"]

@@ -11,12 +11,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from tests.golden.make_golden import CONFIGS, extreme_frame, special_frame  # noqa: E402
-
-
-def same_bits(a, b):
-    a = np.asarray(a, dtype=np.float32)
-    b = np.asarray(b, dtype=np.float32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
+from tests.support.device import L, pair  # noqa: E402,F401  (L is the module fixture)
+from tests.support.host import same_bits  # noqa: E402
 
 
 def ulp_diff(a, b):
@@ -25,29 +21,6 @@ def ulp_diff(a, b):
     a = np.where(a < 0, -(a & 0x7fffffff), a)
     b = np.where(b < 0, -(b & 0x7fffffff), b)
     return np.abs(a - b)
-
-
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    return lumahdrv_amd
-
-
-def table_for(o, cfg):
-    if cfg[0] in (o.PTF_PSI, o.PTF_JND_HDRVDP):
-        d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lumahdrv_amd", "data")
-        nm = "psi" if cfg[0] == o.PTF_PSI else "jnd_hdrvdp"
-        return np.fromfile(os.path.join(d, "ptf_%s_%d.f32" % (nm, cfg[1])), dtype="<f4")
-    return None
-
-
-def pair(L, o, cfg):
-    """(HIP quantizer, oracle) for a configuration tuple (ptf, bits, cs, bitsC, maxLum, minLum)"""
-    q = L.LumaQuantizer()
-    q.setQuantizer(*cfg)
-    orc = o.Oracle(*cfg, table=table_for(o, cfg))
-    assert same_bits(q.getMapping(), orc.mapping)
-    return q, orc
 
 
 def frames(o, w, h):

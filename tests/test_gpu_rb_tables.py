@@ -5,7 +5,7 @@ and the choice of kernel per launch is a function of the stream's data alone (lu
 import numpy as np
 import pytest
 
-from tests.test_gpu_half_table import _half_policy_model
+from tests.support.host import _half_policy_model
 
 pytestmark = pytest.mark.gpu
 

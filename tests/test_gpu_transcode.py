@@ -15,109 +15,11 @@ import os
 import numpy as np
 import pytest
 
-from tests.golden.make_golden import CONFIGS
 from tests.golden import make_transcode_golden as mg
-from tests.test_gpu_parity import table_for
+from tests.support.device import L, Planes, ctx, dev, from_frames, fused, table_for, two_calls  # noqa: F401  (L is the module fixture)
+from tests.support.host import CFG, PAIRS, SENTINEL, SIZES, same_rows
 
 pytestmark = pytest.mark.gpu
-
-CFG = dict(CONFIGS, linear12_luv8=(4, 12, 0, 8, 1e4, 0.005), pq10_ycbcr10_4000=mg.CONFIGS["pq10_ycbcr10_4000"])
-SENTINEL = 0xC3
-GAP = 48   # bytes between one frame's plane and the next frame's
-
-
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    return lumahdrv_amd
-
-
-def _dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def _ctx(L, dst_cfg, src_cfg=None):
-    """a context on torch's current stream: quantizer = dst_cfg, source quantizer = src_cfg"""
-    import torch
-    c = L.Context(0)
-    c.set_stream(torch.cuda.current_stream().cuda_stream)
-    c.set_quantizer(*dst_cfg, L.build_lut(dst_cfg[0], dst_cfg[1], dst_cfg[4], dst_cfg[5]))
-    if src_cfg is not None:
-        c.set_source_quantizer(*src_cfg, L.build_lut(src_cfg[0], src_cfg[1], src_cfg[4], src_cfg[5]))
-    return c
-
-
-def _rows(w, h, profile, p):
-    """(rows, row bytes) of plane p"""
-    sub, bps = profile in (0, 2), 2 if profile > 1 else 1
-    return ((h + 1) // 2 if (p and sub) else h), ((w + 1) // 2 if (p and sub) else w) * bps
-
-
-class Planes:
-    """nf frames of code planes in device buffers: plane p of frame f at buf[p] + f * pfs[p], rows st[p] bytes apart"""
-
-    def __init__(self, L, w, h, profile, nf, fill=None, strides=None, gap=GAP):
-        import torch
-        self.w, self.h, self.profile, self.nf = w, h, profile, nf
-        _, hs, st, _ = L.plane_geometry(w, h, profile)
-        self.st = tuple(strides) if strides is not None else st
-        self.hs = hs
-        self.size = [hs[p] * self.st[p] for p in range(3)]
-        self.pfs = [self.size[p] + gap for p in range(3)]
-        if fill is None:
-            fill = [np.full(nf * self.pfs[p], SENTINEL, dtype=np.uint8) for p in range(3)]
-        self.t = [torch.from_numpy(np.ascontiguousarray(fill[p])).to(_dev()) for p in range(3)]
-
-    @property
-    def ptrs(self):
-        return [t.data_ptr() for t in self.t]
-
-    def host(self):
-        return [t.cpu().numpy() for t in self.t]
-
-    def frame(self, bufs, f):
-        """frame f as three (rows, stride) arrays"""
-        return [bufs[p][f * self.pfs[p]: f * self.pfs[p] + self.size[p]].reshape(self.hs[p], self.st[p]) for p in range(3)]
-
-    def gaps_intact(self, bufs):
-        ok = True
-        for p in range(3):
-            b = bufs[p].reshape(self.nf, self.pfs[p])
-            ok = ok and bool(np.all(b[:, self.size[p]:] == SENTINEL))
-            rows, rb = _rows(self.w, self.h, self.profile, p)
-            ok = ok and bool(np.all(b[:, :self.size[p]].reshape(self.nf, rows, self.st[p])[:, :, rb:] == SENTINEL))
-        return ok
-
-
-def _from_frames(L, frames, w, h, profile, strides=None):
-    """Planes holding the given frames (lists of three (rows, stride) arrays), sentinel in the gaps"""
-    pl = Planes(L, w, h, profile, len(frames), strides=strides)
-    fill = [np.full(len(frames) * pl.pfs[p], SENTINEL, dtype=np.uint8) for p in range(3)]
-    for f, fr in enumerate(frames):
-        for p in range(3):
-            fill[p][f * pl.pfs[p]: f * pl.pfs[p] + pl.size[p]] = np.ascontiguousarray(fr[p]).ravel()
-    return Planes(L, w, h, profile, len(frames), fill=fill, strides=strides)
-
-
-def _fused(c, src, src_sc, dst, dst_sc, stats=None):
-    c.transcode_frames_device(src.ptrs, src.st, src.pfs, src.profile, src_sc, src.nf, src.w, src.h,
-                              dst.ptrs, dst.st, dst.pfs, dst.profile, dst_sc, stats.data_ptr() if stats is not None else None)
-
-
-def _two_calls(cd, ce, src, src_sc, dst, dst_sc, stats=None):
-    """decode under cd's quantizer into a float buffer, encode it under ce's"""
-    import torch
-    n3 = 3 * src.w * src.h
-    buf = torch.empty(src.nf * n3, dtype=torch.float32, device=_dev())
-    cd.decode_frames_device(src.ptrs, src.st, src.pfs, src.nf, src.w, src.h, src.profile, src_sc, buf.data_ptr(), n3)
-    ce.encode_frames_device(buf.data_ptr(), n3, src.nf, src.w, src.h, dst_sc, dst.profile, dst.ptrs, dst.st, dst.pfs,
-                            stats.data_ptr() if stats is not None else None)
-    return buf
-
-
-def _same_rows(a, b, w, h, profile):
-    return all(np.array_equal(a[p][:, :_rows(w, h, profile, p)[1]], b[p][:, :_rows(w, h, profile, p)[1]]) for p in range(3))
 
 
 # ---- 1. the reference's own decode -> encode
@@ -127,31 +29,27 @@ def test_fused_equals_the_reference_fixture(L, golden_dir):
     gt = np.load(os.path.join(golden_dir, "ref_transcode.npz"))
     n = 0
     for case, (sname, src_sc, dname, dst_sc) in sorted(mg.CASES.items()):
-        c = _ctx(L, mg.CONFIGS[dname], mg.CONFIGS[sname])
+        c = ctx(L, mg.CONFIGS[dname], mg.CONFIGS[sname])
         for (w, h) in mg.SIZES:
             for sp in mg.SRC_PROFILES:
                 k = mg.key_of(case, w, h, sp)
                 planes, st = mg.source_planes(gp, sname, w, h, sp)
                 exp = [gt[k + "_plane%d" % p] for p in range(3)]
                 est = tuple(int(s) for s in gt[k + "_stride"])
-                src = _from_frames(L, [planes], w, h, sp, strides=st)
+                src = from_frames(L, [planes], w, h, sp, strides=st, padding="source")
                 dst = Planes(L, w, h, mg.DST_PROFILE, 1, strides=est)
-                _fused(c, src, src_sc, dst, dst_sc)
+                fused(c, src, src_sc, dst, dst_sc)
                 torch.cuda.synchronize()
                 bufs = dst.host()
-                assert _same_rows(dst.frame(bufs, 0), exp, w, h, mg.DST_PROFILE), (k, "device")
+                assert same_rows(dst.frame(bufs, 0), exp, w, h, mg.DST_PROFILE), (k, "device")
                 assert dst.gaps_intact(bufs), k
                 hp, hst, _ = c.transcode_frame(planes, st, w, h, src_sc, sp, dst_sc, mg.DST_PROFILE, dst_strides=est)
-                assert _same_rows(hp, exp, w, h, mg.DST_PROFILE), (k, "host")
+                assert same_rows(hp, exp, w, h, mg.DST_PROFILE), (k, "host")
                 n += 1
     assert n == 16
 
 
 # ---- 2. oracle and two-call pair
-PAIRS = [("pq11_luv8", "pq10_ycbcr10"), ("pq11_luv8", "log12_luv8"), ("psi11_luv8", "linear12_luv8"), ("hdrvdp12_luv10", "pq11_luv8"),
-         ("pq10_ycbcr10", "pq11_luv8"), ("pq10_ycbcr10", "pq10_ycbcr10_4000"), ("pq10_ycbcr10", "linear12_luv8"),
-         ("log12_luv8", "psi11_luv8"), ("hdrvdp12_luv10", "pq10_ycbcr10")]
-SIZES = [(34, 18), (258, 6), (64, 32), (6, 4)]
 SCS = (1.0, 20.0, 0.01, 3e5)
 
 
@@ -165,7 +63,7 @@ def test_fused_equals_oracle_and_the_two_call_pair(L, oracle_mod, sname, dname):
     import torch
     o = oracle_mod
     scfg, dcfg = CFG[sname], CFG[dname]
-    ct, cd = _ctx(L, dcfg, scfg), _ctx(L, scfg)
+    ct, cd = ctx(L, dcfg, scfg), ctx(L, scfg)
     if dname == "linear12_luv8":
         assert ct.quantizer_info()["mode"] == 7, "the value-keyed records are what this pair is here for"
     odec, oenc = o.Oracle(*scfg, table=table_for(o, scfg)), o.Oracle(*dcfg, table=table_for(o, dcfg))
@@ -181,17 +79,17 @@ def test_fused_equals_oracle_and_the_two_call_pair(L, oracle_mod, sname, dname):
                 if it % 7 == 0:   # x / 0 and NaN inputs to the target side: against the two-call pair only
                     src_sc = special = (0.0, float("nan"))[(it // 7) % 2]
                 if real:
-                    src = _from_frames(L, _real_planes(o, scfg, w, h, sp, nf, src_sc if special is None else 1.0), w, h, sp)
+                    src = from_frames(L, _real_planes(o, scfg, w, h, sp, nf, src_sc if special is None else 1.0), w, h, sp, padding="source")
                 else:
                     src = Planes(L, w, h, sp, nf)
                     fill = [rng.integers(0, 256, size=nf * src.pfs[p], dtype=np.uint8) for p in range(3)]   # out-of-range codes included
                     src = Planes(L, w, h, sp, nf, fill=fill)
                 dst, ref = Planes(L, w, h, dp, nf), Planes(L, w, h, dp, nf)
                 with_stats = it % 2 == 0
-                s1 = torch.zeros(3 * nf, dtype=torch.float32, device=_dev()) if with_stats else None
-                s2 = torch.zeros(3 * nf, dtype=torch.float32, device=_dev()) if with_stats else None
-                _fused(ct, src, src_sc, dst, dst_sc, s1)
-                buf = _two_calls(cd, ct, src, src_sc, ref, dst_sc, s2)
+                s1 = torch.zeros(3 * nf, dtype=torch.float32, device=dev()) if with_stats else None
+                s2 = torch.zeros(3 * nf, dtype=torch.float32, device=dev()) if with_stats else None
+                fused(ct, src, src_sc, dst, dst_sc, s1)
+                buf = two_calls(cd, ct, src, src_sc, ref, dst_sc, s2)
                 torch.cuda.synchronize()
                 tag = (sname, dname, sp, dp, w, h, src_sc, dst_sc, real)
                 got, exp = dst.host(), ref.host()
@@ -208,10 +106,10 @@ def test_fused_equals_oracle_and_the_two_call_pair(L, oracle_mod, sname, dname):
                         dec = odec.decode(src.frame(sh, f), src.st, w, h, src_sc, sp)
                         ep, est, _ = oenc.encode(dec, dst_sc, dp)
                         assert tuple(est) == tuple(dst.st)
-                        assert _same_rows(dst.frame(got, f), ep, w, h, dp), tag + ("oracle, frame %d" % f,)
+                        assert same_rows(dst.frame(got, f), ep, w, h, dp), tag + ("oracle, frame %d" % f,)
                 # the host call on frame 0: planes, and the mean luminance lumahip_encode_frame_host reports for the decoded frame
                 hp, _, mean = ct.transcode_frame(src.frame(sh, 0), src.st, w, h, src_sc, sp, dst_sc, dp)
-                assert _same_rows(hp, dst.frame(got, 0), w, h, dp), tag + ("host call",)
+                assert same_rows(hp, dst.frame(got, 0), w, h, dp), tag + ("host call",)
                 dec0 = buf[:3 * w * h].cpu().numpy().reshape(3, h, w)
                 _, _, emean = ct.encode_frame(dec0, dst_sc, dp)
                 assert (np.isnan(mean) and np.isnan(emean)) or mean == pytest.approx(emean, rel=1e-4), tag + ("mean luminance", mean, emean)
@@ -222,7 +120,7 @@ def test_host_mean_takes_the_reference_sum_where_the_encode_call_does(L, oracle_
     """a frame whose mean luminance lies in [0.25, 4]: both calls answer with the reference's sequential sum, which is exact"""
     o = oracle_mod
     scfg, dcfg = CFG["pq10_ycbcr10"], CFG["pq11_luv8"]
-    ct, cd = _ctx(L, dcfg, scfg), _ctx(L, scfg)
+    ct, cd = ctx(L, dcfg, scfg), ctx(L, scfg)
     w, h = 64, 32
     planes, st, _ = o.Oracle(*scfg).encode(o.synth_frame(w, h, frame=9), 20.0, 2)
     dec = cd.decode_frame(planes, st, w, h, 20.0, 2)
@@ -239,16 +137,16 @@ def test_host_mean_takes_the_reference_sum_where_the_encode_call_does(L, oracle_
 def test_persistent_loop_and_prefetch_tail(L, w, h):
     import torch
     scfg, dcfg = CFG["pq11_luv8"], CFG["pq10_ycbcr10"]
-    ct = _ctx(L, dcfg, scfg)
+    ct = ctx(L, dcfg, scfg)
     rng = np.random.default_rng(w)
     for sp, dp in ((2, 2), (3, 0), (1, 3)):
         src = Planes(L, w, h, sp, 3)
         src = Planes(L, w, h, sp, 3, fill=[rng.integers(0, 256, size=3 * src.pfs[p], dtype=np.uint8) for p in range(3)])
         a, b = Planes(L, w, h, dp, 3), Planes(L, w, h, dp, 3)
-        _fused(ct, src, 1.0, a, 20.0)
+        fused(ct, src, 1.0, a, 20.0)
         ct.tune("grid_enc", 2)
         ct.tune("block", 64)
-        _fused(ct, src, 1.0, b, 20.0)
+        fused(ct, src, 1.0, b, 20.0)
         ct.tune("grid_enc", 0)
         ct.tune("block", 0)
         torch.cuda.synchronize()
@@ -260,7 +158,7 @@ def test_persistent_loop_and_prefetch_tail(L, w, h):
 def test_unordered_section_gives_the_ordered_planes(L):
     import torch
     scfg, dcfg = CFG["pq10_ycbcr10"], CFG["log12_luv8"]
-    ct = _ctx(L, dcfg, scfg)
+    ct = ctx(L, dcfg, scfg)
     rng = np.random.default_rng(4)
     w, h, nf = 64, 32, 3
     srcs, ordered, lanes = [], [], []
@@ -269,10 +167,10 @@ def test_unordered_section_gives_the_ordered_planes(L):
         srcs.append(Planes(L, w, h, 2, nf, fill=[rng.integers(0, 256, size=nf * s.pfs[p], dtype=np.uint8) for p in range(3)]))
         ordered.append(Planes(L, w, h, 2, nf))
         lanes.append(Planes(L, w, h, 2, nf))
-        _fused(ct, srcs[i], 20.0, ordered[i], 1.0)
+        fused(ct, srcs[i], 20.0, ordered[i], 1.0)
     ct.begin_unordered(2)
     for i in range(4):
-        _fused(ct, srcs[i], 20.0, lanes[i], 1.0)
+        fused(ct, srcs[i], 20.0, lanes[i], 1.0)
     ct.end_unordered()
     ct.sync()
     torch.cuda.synchronize()
@@ -290,13 +188,13 @@ def test_720p_frame_against_the_oracle(L, oracle_mod):
     planes, st, _ = o.Oracle(*scfg).encode(o.test_frame(w, h), 1.0, 2)
     dec = o.Oracle(*scfg).decode(planes, st, w, h, 1.0, 2)
     exp, est, _ = o.Oracle(*dcfg).encode(dec, 20.0, 2)
-    ct = _ctx(L, dcfg, scfg)
-    src = _from_frames(L, [planes], w, h, 2, strides=st)
+    ct = ctx(L, dcfg, scfg)
+    src = from_frames(L, [planes], w, h, 2, strides=st, padding="source")
     dst = Planes(L, w, h, 2, 1, strides=est)
-    _fused(ct, src, 1.0, dst, 20.0)
+    fused(ct, src, 1.0, dst, 20.0)
     torch.cuda.synchronize()
     bufs = dst.host()
-    assert _same_rows(dst.frame(bufs, 0), exp, w, h, 2)
+    assert same_rows(dst.frame(bufs, 0), exp, w, h, 2)
     assert dst.gaps_intact(bufs)
 
 
@@ -322,11 +220,11 @@ def test_errors_launch_nothing_and_leave_the_context_usable(L):
 
     def works(c):
         src, dst = Planes(L, w, h, 2, 1), Planes(L, w, h, 2, 1)
-        _fused(c, src, 1.0, dst, 1.0)
+        fused(c, src, 1.0, dst, 1.0)
         torch.cuda.synchronize()
         assert not np.all(dst.host()[0] == SENTINEL)
 
-    c = _ctx(L, luv)
+    c = ctx(L, luv)
     attempt(c, ERR_STATE)                                    # no source quantizer
     c.set_source_quantizer(*luv, lut(luv))
     works(c)
@@ -342,7 +240,7 @@ def test_errors_launch_nothing_and_leave_the_context_usable(L):
         attempt(c, ERR_UNSUPPORTED)
         c.set_source_quantizer(*luv, lut(luv))
         works(c)
-        c2 = _ctx(L, bad, luv)
+        c2 = ctx(L, bad, luv)
         attempt(c2, ERR_UNSUPPORTED)
     deep = (1, 14, 0, 8, 1e4, 0.005)                         # source bit depth 14
     c.set_source_quantizer(*deep, lut(deep))
@@ -354,12 +252,12 @@ def test_errors_launch_nothing_and_leave_the_context_usable(L):
     c.tune("force_literal", 0)
     works(c)
     big, y12 = (1, 13, 0, 8, 1e4, 0.005), (1, 12, 2, 12, 1000.0, 0.01)   # 136 KiB of records + a 12-bit YCbCr source: beyond 160 KiB
-    c3 = _ctx(L, big, y12)
+    c3 = ctx(L, big, y12)
     attempt(c3, ERR_UNSUPPORTED)
     c3.set_source_quantizer(*luv, lut(luv))                  # ... while PQ-11 Lu'v' beside the 13-bit target fits
     works(c3)
     with pytest.raises(LumaHipError) as e:                   # the host call refuses the same way
-        _ctx(L, luv).transcode_frame([np.zeros((32, 128), np.uint8), np.zeros((16, 64), np.uint8), np.zeros((16, 64), np.uint8)], (128, 64, 64), w, h)
+        ctx(L, luv).transcode_frame([np.zeros((32, 128), np.uint8), np.zeros((16, 64), np.uint8), np.zeros((16, 64), np.uint8)], (128, 64, 64), w, h)
     assert e.value.code == ERR_STATE
 
 
@@ -367,7 +265,7 @@ def test_errors_launch_nothing_and_leave_the_context_usable(L):
 def test_set_source_quantizer_leaves_encode_and_decode_alone(L, oracle_mod):
     o = oracle_mod
     cfg = CFG["pq11_luv8"]
-    c = _ctx(L, cfg)
+    c = ctx(L, cfg)
     f = o.synth_frame(64, 32, frame=2)
 
     def digests():
@@ -383,8 +281,8 @@ def test_set_source_quantizer_leaves_encode_and_decode_alone(L, oracle_mod):
     # ... and the other way round: a new quantizer keeps the source quantizer
     import torch
     src, a, b = Planes(L, 64, 32, 2, 1), Planes(L, 64, 32, 2, 1), Planes(L, 64, 32, 2, 1)
-    _fused(c, src, 1.0, a, 1.0)
+    fused(c, src, 1.0, a, 1.0)
     c.set_quantizer(*cfg, L.build_lut(cfg[0], cfg[1], cfg[4], cfg[5]))
-    _fused(c, src, 1.0, b, 1.0)
+    fused(c, src, 1.0, b, 1.0)
     torch.cuda.synchronize()
     assert all(np.array_equal(x, y) for x, y in zip(a.host(), b.host()))

@@ -1,7 +1,7 @@
 """Transcode distortion map (include/lumahip.h lumahip_transcode_distortion_map_frames_device / _frame_host):
 lumahip_transcode_distortion_frames_device's four words per plane for every block of 16, 32 or 64 luma pixels squared of the target,
 from code planes alone, written by one launch.  Every expectation is exact equality of integers
-(tests/test_distortion_map_host.py expected_distortion_map); before every call the map buffer holds the 0xC3 pattern with 16 guard
+(tests/support/host.py expected_distortion_map); before every call the map buffer holds the 0xC3 pattern with 16 guard
 words behind it, which must survive; both plane sets and the sentinel bytes in their paddings and gaps must be as they were.
 
 1. The reference's own decode -> encode (tests/golden/ref_transcode.npz): zeros written over the fill against the fixture, numpy's
@@ -21,125 +21,15 @@ import numpy as np
 import pytest
 
 from tests.golden import make_transcode_golden as mg
-from tests.test_distortion_map_host import BLOCKS, expected_distortion_map, fold_map
-from tests.test_gpu_distortion import CFG as DIST_CFG, OUT_FILL, _out, _perturb, _row_bytes, _words
-from tests.test_gpu_transcode import CFG, PAIRS, SENTINEL, Planes, _ctx, _dev, _from_frames, _fused
-from tests.test_transcode_distortion_host import fixture_cases, perturbed
+from tests.support.device import (L, Planes, ctx, dev, from_frames, inputs_as_before, map_buf, measure, random_planes, tmap,  # noqa: F401  (L is the module fixture)
+                                  transcoded)
+from tests.support.host import (BLOCKS, CFG, GUARD, MAP_SIZES, OUT_FILL, PAIRS, SENTINEL, expect_map, expected_distortion_map, fixture_cases,
+                                fold_map, map_perturbed, map_words, neither_path_is_vacuous, nwords, perturb, perturbed)
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 16
-SIZES = [(34, 18), (260, 6), (258, 6), (264, 70), (64, 32), (6, 4)]
 ALL_BLOCKS_AT = ((264, 70), (34, 18))
 SCS = (1.0, 20.0, 0.01)
-
-
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    return lumahdrv_amd
-
-
-def _nwords(nf, w, h, block):
-    return nf * (-(-w // block)) * (-(-h // block)) * 12
-
-
-def _map_buf(nwords):
-    import torch
-    return torch.full((nwords + GUARD,), OUT_FILL, dtype=torch.int64, device=_dev())
-
-
-def _map_words(buf, nf, w, h, block):
-    """the map of a call as (nf, nby, nbx, 3, 4) uint64, after checking the guard words behind it"""
-    a = buf.cpu().numpy()
-    assert np.all(a[-GUARD:] == OUT_FILL), "guard words behind the map"
-    return a[:-GUARD].view(np.uint64).reshape(nf, -(-h // block), -(-w // block), 3, 4)
-
-
-def _tmap(c, src, src_sc, given, dst_sc, block, src_ptrs=None):
-    import torch
-    buf = _map_buf(_nwords(src.nf, src.w, src.h, block))
-    c.transcode_distortion_map_frames_device(src.ptrs if src_ptrs is None else src_ptrs, src.st, src.pfs, src.profile, src_sc, src.nf, src.w,
-                                             src.h, given.ptrs, given.st, given.pfs, given.profile, dst_sc, block, buf.data_ptr())
-    torch.cuda.synchronize()
-    return _map_words(buf, src.nf, src.w, src.h, block)
-
-
-def _measure(c, src, src_sc, given, dst_sc):
-    """the twelve words per frame of lumahip_transcode_distortion_frames_device"""
-    import torch
-    out = _out(src.nf)
-    c.transcode_distortion_frames_device(src.ptrs, src.st, src.pfs, src.profile, src_sc, src.nf, src.w, src.h,
-                                         given.ptrs, given.st, given.pfs, given.profile, dst_sc, out.data_ptr())
-    torch.cuda.synchronize()
-    return _words(out, src.nf)
-
-
-def _transcoded(c, L, src, src_sc, dp, dst_sc):
-    """what lumahip_transcode_frames_device writes for src: its Planes and their host buffers"""
-    import torch
-    dst = Planes(L, src.w, src.h, dp, src.nf)
-    _fused(c, src, src_sc, dst, dst_sc)
-    torch.cuda.synchronize()
-    return dst, dst.host()
-
-
-def _random_planes(L, rng, w, h, profile, nf):
-    """random bytes in the samples (out-of-range codes included), the sentinel in every row padding and gap"""
-    pl = Planes(L, w, h, profile, nf)
-    frames = []
-    for _ in range(nf):
-        fr = []
-        for p in range(3):
-            a = np.full((pl.hs[p], pl.st[p]), SENTINEL, dtype=np.uint8)
-            rb = _row_bytes(w, h, profile, p)
-            a[:, :rb] = rng.integers(0, 256, size=(pl.hs[p], rb), dtype=np.uint8)
-            fr.append(a)
-        frames.append(fr)
-    return _from_frames(L, frames, w, h, profile)
-
-
-def _perturbed(rng, enc, ebufs, w, h, profile, block):
-    """the transcode call's planes, every frame perturbed densely (about half the samples, so that blocks of a few samples differ
-    too); frame 1 keeps its rightmost block column and its bottom block row as transcoded"""
-    frames = []
-    bps = 2 if profile > 1 else 1
-    nbx, nby = -(-w // block), -(-h // block)
-    for f in range(enc.nf):
-        orig = enc.frame(ebufs, f)
-        g = _perturb(rng, orig, w, h, profile, frac=0.5)
-        if f == 1:
-            for p in range(3):
-                b = block // 2 if (p and profile in (0, 2)) else block
-                rb = _row_bytes(w, h, profile, p)
-                x0, y0 = (nbx - 1) * b * bps, (nby - 1) * b
-                g[p][:, x0:rb] = orig[p][:, x0:rb]
-                g[p][y0:, :rb] = orig[p][y0:, :rb]
-        frames.append(g)
-    return frames
-
-
-def _expect_map(enc, ebufs, given, gbufs, block):
-    return np.stack([expected_distortion_map(enc.frame(ebufs, f), given.frame(gbufs, f), enc.w, enc.h, enc.profile, block)
-                     for f in range(enc.nf)])
-
-
-def _neither_path_is_vacuous(exp, tag):
-    """asserted on the numpy expectation: with more than one block column and row, every plane has a block without a difference and at
-    least half of its blocks differ"""
-    nd = exp[:, :, :, :, 3]                       # (nf, nby, nbx, 3)
-    if nd.shape[1] > 1 and nd.shape[2] > 1:
-        for p in range(3):
-            assert (nd[..., p] == 0).any(), tag + (p, "no block without a difference")
-            assert 2 * np.count_nonzero(nd[..., p]) >= nd[..., p].size, tag + (p, "fewer than half the blocks differ")
-
-
-def _inputs_as_before(src, sbefore, given, gbefore, tag, sentinels=True):
-    """both plane sets byte for byte what they were, and (planes built here, not the fixture's rows) the sentinel in every padding and gap"""
-    for a, b in zip(sbefore + gbefore, src.host() + given.host()):
-        assert np.array_equal(a, b), tag + ("an input plane changed",)
-    if sentinels:
-        assert src.gaps_intact(sbefore) and given.gaps_intact(gbefore), tag
 
 
 # ---- 1. the reference's own decode -> encode
@@ -149,22 +39,22 @@ def test_reference_fixture_and_its_perturbed_copy(L, golden_dir):
     ctxs, n = {}, 0
     for k, case, w, h, sp in fixture_cases(gt):
         sname, src_sc, dname, dst_sc = mg.CASES[case]
-        c = ctxs.setdefault(case, _ctx(L, mg.CONFIGS[dname], mg.CONFIGS[sname]))
+        c = ctxs.setdefault(case, ctx(L, mg.CONFIGS[dname], mg.CONFIGS[sname]))
         planes, st = mg.source_planes(gp, sname, w, h, sp)
         fix = [gt[k + "_plane%d" % p] for p in range(3)]
         est = tuple(int(s) for s in gt[k + "_stride"])
         bad = perturbed(fix, w, h, mg.DST_PROFILE)
-        src = _from_frames(L, [planes], w, h, sp, strides=st)
+        src = from_frames(L, [planes], w, h, sp, strides=st, padding="source")
         sbefore = src.host()
         for block in BLOCKS:
             exp = expected_distortion_map(fix, bad, w, h, mg.DST_PROFILE, block)
             assert exp.any(), (k, block)
             for given, want in ((fix, np.zeros_like(exp)), (bad, exp)):
-                gv = _from_frames(L, [given], w, h, mg.DST_PROFILE, strides=est)
+                gv = from_frames(L, [given], w, h, mg.DST_PROFILE, strides=est, padding="source")
                 gbefore = gv.host()
-                got = _tmap(c, src, src_sc, gv, dst_sc, block)
+                got = tmap(c, src, src_sc, gv, dst_sc, block)
                 assert np.array_equal(got[0], want), (k, block, "device", got, want)
-                _inputs_as_before(src, sbefore, gv, gbefore, (k, block), sentinels=False)
+                inputs_as_before(src, sbefore, gv, gbefore, (k, block), sentinels=False)
                 hw = c.transcode_distortion_map_frame(planes, st, w, h, given, est, src_sc, sp, dst_sc, mg.DST_PROFILE, block)
                 assert hw.dtype == np.uint64 and hw.shape == want.shape
                 assert np.array_equal(hw, want), (k, block, "host", hw, want)
@@ -176,31 +66,31 @@ def test_reference_fixture_and_its_perturbed_copy(L, golden_dir):
 @pytest.mark.parametrize("sname,dname", PAIRS)
 def test_equals_numpy_on_the_transcode_calls_planes(L, sname, dname):
     scfg, dcfg = CFG[sname], CFG[dname]
-    c = _ctx(L, dcfg, scfg)
+    c = ctx(L, dcfg, scfg)
     if dname == "linear12_luv8":
         assert c.quantizer_info()["mode"] == 7, "the value-keyed records are what this pair is here for"
     rng = np.random.default_rng(len(sname) * 41 + len(dname))
     nf, it = 3, 0
     for sp in range(4):
         for dp in range(4):
-            for (w, h) in SIZES:
+            for (w, h) in MAP_SIZES:
                 it += 1
                 src_sc, dst_sc = (float(x) for x in rng.choice(SCS, 2))
-                src = _random_planes(L, rng, w, h, sp, nf)
+                src = random_planes(L, rng, w, h, sp, nf)
                 sbefore = src.host()
-                enc, ebufs = _transcoded(c, L, src, src_sc, dp, dst_sc)
+                enc, ebufs = transcoded(c, L, src, src_sc, dp, dst_sc)
                 for block in (BLOCKS if (w, h) in ALL_BLOCKS_AT else (BLOCKS[it % 3],)):
                     tag = (sname, dname, sp, dp, w, h, src_sc, dst_sc, block)
-                    given = _from_frames(L, _perturbed(rng, enc, ebufs, w, h, dp, block), w, h, dp)
+                    given = from_frames(L, map_perturbed(rng, enc, ebufs, w, h, dp, block), w, h, dp, padding="source")
                     gbefore = given.host()
-                    exp = _expect_map(enc, ebufs, given, gbefore, block)
-                    _neither_path_is_vacuous(exp, tag)
+                    exp = expect_map(enc, ebufs, given, gbefore, block)
+                    neither_path_is_vacuous(exp, tag)
                     assert exp[..., 3].any(), tag
-                    got = _tmap(c, src, src_sc, given, dst_sc, block)
+                    got = tmap(c, src, src_sc, given, dst_sc, block)
                     assert np.array_equal(got, exp), tag + (got, exp)
-                    frame_words = _measure(c, src, src_sc, given, dst_sc)
+                    frame_words = measure(c, src, src_sc, given, dst_sc)
                     assert np.array_equal(np.stack([fold_map(m) for m in got]), frame_words), tag + ("fold",)
-                    _inputs_as_before(src, sbefore, given, gbefore, tag)
+                    inputs_as_before(src, sbefore, given, gbefore, tag)
     assert it == 96
 
 
@@ -208,33 +98,33 @@ def test_equals_numpy_on_the_transcode_calls_planes(L, sname, dname):
 @pytest.mark.parametrize("sname,dname", [("pq11_luv8", "pq10_ycbcr10"), ("pq10_ycbcr10", "log12_luv8")])
 def test_odd_given_strides_and_misaligned_source_planes(L, sname, dname):
     import torch
-    c = _ctx(L, CFG[dname], CFG[sname])
+    c = ctx(L, CFG[dname], CFG[sname])
     rng = np.random.default_rng(34)
     nf = 3
     src_sc, dst_sc = (20.0, 1.0) if CFG[sname][2] == 2 else (1.0, 20.0)
     for (w, h) in ((64, 32), (34, 18)):
         for sp, dp in ((2, 2), (3, 1), (0, 3)):
-            src = _random_planes(L, rng, w, h, sp, nf)
+            src = random_planes(L, rng, w, h, sp, nf)
             sbefore = src.host()
-            enc, ebufs = _transcoded(c, L, src, src_sc, dp, dst_sc)
-            shifted = [torch.cat([torch.full((2,), SENTINEL, dtype=torch.uint8, device=_dev()), t]) for t in src.t]
+            enc, ebufs = transcoded(c, L, src, src_sc, dp, dst_sc)
+            shifted = [torch.cat([torch.full((2,), SENTINEL, dtype=torch.uint8, device=dev()), t]) for t in src.t]
             for block in BLOCKS:
                 tag = (sname, dname, w, h, sp, dp, block)
-                frames = _perturbed(rng, enc, ebufs, w, h, dp, block)
-                given = _from_frames(L, frames, w, h, dp)
+                frames = map_perturbed(rng, enc, ebufs, w, h, dp, block)
+                given = from_frames(L, frames, w, h, dp, padding="source")
                 # the same samples in rows three bytes longer
                 longer = [[np.concatenate([a, np.full((a.shape[0], 3), SENTINEL, np.uint8)], axis=1) for a in fr] for fr in frames]
-                odd = _from_frames(L, longer, w, h, dp, strides=tuple(s + 3 for s in enc.st))
+                odd = from_frames(L, longer, w, h, dp, strides=tuple(s + 3 for s in enc.st), padding="source")
                 gbefore, obefore = given.host(), odd.host()
-                exp = _expect_map(enc, ebufs, given, gbefore, block)
-                assert exp[..., 3].any() and np.array_equal(exp, _expect_map(enc, ebufs, odd, obefore, block)), tag
-                assert np.array_equal(_tmap(c, src, src_sc, odd, dst_sc, block), exp), tag + ("odd strides",)
-                _inputs_as_before(src, sbefore, odd, obefore, tag)
-                got = _tmap(c, src, src_sc, given, dst_sc, block, src_ptrs=[t.data_ptr() + 2 for t in shifted])
+                exp = expect_map(enc, ebufs, given, gbefore, block)
+                assert exp[..., 3].any() and np.array_equal(exp, expect_map(enc, ebufs, odd, obefore, block)), tag
+                assert np.array_equal(tmap(c, src, src_sc, odd, dst_sc, block), exp), tag + ("odd strides",)
+                inputs_as_before(src, sbefore, odd, obefore, tag)
+                got = tmap(c, src, src_sc, given, dst_sc, block, src_ptrs=[t.data_ptr() + 2 for t in shifted])
                 assert np.array_equal(got, exp), tag + ("misaligned source", got, exp)
-                both = _tmap(c, src, src_sc, odd, dst_sc, block, src_ptrs=[t.data_ptr() + 2 for t in shifted])
+                both = tmap(c, src, src_sc, odd, dst_sc, block, src_ptrs=[t.data_ptr() + 2 for t in shifted])
                 assert np.array_equal(both, exp), tag + ("both",)
-                _inputs_as_before(src, sbefore, given, gbefore, tag)
+                inputs_as_before(src, sbefore, given, gbefore, tag)
             for t, s in zip(shifted, src.t):
                 assert bool((t[:2] == SENTINEL).all()) and torch.equal(t[2:], s)
 
@@ -243,20 +133,20 @@ def test_odd_given_strides_and_misaligned_source_planes(L, sname, dname):
 @pytest.mark.parametrize("vw4", [True, False])
 def test_one_block_sums_beyond_32_bits(L, vw4):
     import torch
-    c = _ctx(L, CFG["log12_luv8"], CFG["pq11_luv8"])
+    c = ctx(L, CFG["log12_luv8"], CFG["pq11_luv8"])
     rng = np.random.default_rng(4)
     w, h, profile = 64, 64, 2
-    src = _random_planes(L, rng, w, h, profile, 1)
-    enc, ebufs = _transcoded(c, L, src, 1.0, profile, 1.0)
+    src = random_planes(L, rng, w, h, profile, 1)
+    enc, ebufs = transcoded(c, L, src, 1.0, profile, 1.0)
     ones = Planes(L, w, h, profile, 1, fill=[np.full(enc.pfs[p], 0xFF, dtype=np.uint8) for p in range(3)])
-    exp = _expect_map(enc, ebufs, ones, ones.host(), 64)
+    exp = expect_map(enc, ebufs, ones, ones.host(), 64)
     assert exp.shape == (1, 1, 1, 3, 4) and exp[0, 0, 0, 0, 0] > np.uint64(10) ** np.uint64(13)
     assert np.all(exp[..., 0] > np.uint64(1) << np.uint64(32))
     ptrs = None
     if not vw4:   # a source plane two bytes into its buffer: two pixels per thread, 32 lanes per block
-        shifted = [torch.cat([torch.full((2,), SENTINEL, dtype=torch.uint8, device=_dev()), t]) for t in src.t]
+        shifted = [torch.cat([torch.full((2,), SENTINEL, dtype=torch.uint8, device=dev()), t]) for t in src.t]
         ptrs = [t.data_ptr() + 2 for t in shifted]
-    got = _tmap(c, src, 1.0, ones, 1.0, 64, src_ptrs=ptrs)
+    got = tmap(c, src, 1.0, ones, 1.0, 64, src_ptrs=ptrs)
     assert np.array_equal(got, exp), (got, exp)
 
 
@@ -269,7 +159,7 @@ def test_launch_shapes_give_identical_maps(L, sname, dname, sp, dp):
     nf = 3
     shapes = {}
     for shape in ("default", "two_workgroups_of_64", "1024_threads"):
-        c = _ctx(L, CFG[dname], CFG[sname])
+        c = ctx(L, CFG[dname], CFG[sname])
         if shape == "two_workgroups_of_64":      # the persistent loop across frames, the most sub-tiles per map tile
             c.tune("block", 64)
             c.tune("grid_enc", 2)
@@ -277,14 +167,14 @@ def test_launch_shapes_give_identical_maps(L, sname, dname, sp, dp):
             c.tune("block", 1024)
         shapes[shape] = c
     for (w, h) in ((264, 70), (34, 18)):
-        src = _random_planes(L, rng, w, h, sp, nf)
-        enc, ebufs = _transcoded(shapes["default"], L, src, src_sc, dp, dst_sc)
+        src = random_planes(L, rng, w, h, sp, nf)
+        enc, ebufs = transcoded(shapes["default"], L, src, src_sc, dp, dst_sc)
         for block in BLOCKS:
-            given = _from_frames(L, _perturbed(rng, enc, ebufs, w, h, dp, block), w, h, dp)
-            exp = _expect_map(enc, ebufs, given, given.host(), block)
+            given = from_frames(L, map_perturbed(rng, enc, ebufs, w, h, dp, block), w, h, dp, padding="source")
+            exp = expect_map(enc, ebufs, given, given.host(), block)
             assert exp[..., 3].any()
             for shape, c in shapes.items():
-                got = _tmap(c, src, src_sc, given, dst_sc, block)
+                got = tmap(c, src, src_sc, given, dst_sc, block)
                 assert np.array_equal(got, exp), (sname, dname, w, h, block, shape, got, exp)
 
 
@@ -292,20 +182,20 @@ def test_launch_shapes_give_identical_maps(L, sname, dname, sp, dp):
 @pytest.mark.parametrize("sname,dname", [("pq11_luv8", "pq10_ycbcr10"), ("pq10_ycbcr10", "log12_luv8")])
 def test_one_720p_frame_twice_and_in_an_unordered_section(L, sname, dname):
     import torch
-    c = _ctx(L, CFG[dname], CFG[sname])
+    c = ctx(L, CFG[dname], CFG[sname])
     src_sc, dst_sc = (20.0 if CFG[sname][2] == 2 else 1.0), (20.0 if CFG[dname][2] == 2 else 1.0)
     rng = np.random.default_rng(722)
     w, h, profile, block = 1280, 720, 2, 64
-    src = _random_planes(L, rng, w, h, profile, 1)
-    enc, ebufs = _transcoded(c, L, src, src_sc, profile, dst_sc)
-    given = _from_frames(L, [_perturb(rng, enc.frame(ebufs, 0), w, h, profile, frac=0.5)], w, h, profile)
+    src = random_planes(L, rng, w, h, profile, 1)
+    enc, ebufs = transcoded(c, L, src, src_sc, profile, dst_sc)
+    given = from_frames(L, [perturb(rng, enc.frame(ebufs, 0), w, h, profile, frac=0.5)], w, h, profile, padding="source")
     sbefore, gbefore = src.host(), given.host()
-    exp = _expect_map(enc, ebufs, given, gbefore, block)
-    a = _tmap(c, src, src_sc, given, dst_sc, block)
-    b = _tmap(c, src, src_sc, given, dst_sc, block)
+    exp = expect_map(enc, ebufs, given, gbefore, block)
+    a = tmap(c, src, src_sc, given, dst_sc, block)
+    b = tmap(c, src, src_sc, given, dst_sc, block)
     assert np.array_equal(a, exp), (a, exp)
     assert np.array_equal(b, exp)
-    bufs = [_map_buf(_nwords(1, w, h, block)) for _ in range(2)]
+    bufs = [map_buf(nwords(1, w, h, block)) for _ in range(2)]
     torch.cuda.synchronize()
     c.begin_unordered(2)
     for buf in bufs:
@@ -315,8 +205,8 @@ def test_one_720p_frame_twice_and_in_an_unordered_section(L, sname, dname):
     c.sync()
     torch.cuda.synchronize()
     for buf in bufs:
-        assert np.array_equal(_map_words(buf, 1, w, h, block), exp)
-    _inputs_as_before(src, sbefore, given, gbefore, (sname, dname))
+        assert np.array_equal(map_words(buf, 1, w, h, block), exp)
+    inputs_as_before(src, sbefore, given, gbefore, (sname, dname))
 
 
 # ---- 8. errors: nothing is launched, the map is left as it was
@@ -324,12 +214,12 @@ def test_errors_launch_nothing(L):
     import torch
     from lumahdrv_amd.capi import ERR_ARG, ERR_STATE, ERR_UNSUPPORTED, LumaHipError
     w, h, profile, nf = 64, 32, 2, 1
-    luv, rgb, deep = CFG["pq11_luv8"], (1, 11, 1, 8, 1e4, 0.005), DIST_CFG["pq14_luv8"]
+    luv, rgb, deep = CFG["pq11_luv8"], (1, 11, 1, 8, 1e4, 0.005), CFG["pq14_luv8"]
     src, given = Planes(L, w, h, profile, nf), Planes(L, w, h, profile, nf)
-    assert _nwords(nf, w, h, 16) * 8 > 200
+    assert nwords(nf, w, h, 16) * 8 > 200
 
     def refused(c, code, w=w, block=16, map_ptr="own"):
-        buf = _map_buf(_nwords(nf, 64, 32, 16))
+        buf = map_buf(nwords(nf, 64, 32, 16))
         ptr = buf.data_ptr() if map_ptr == "own" else map_ptr(buf)
         with pytest.raises(LumaHipError) as ei:
             c.transcode_distortion_map_frames_device(src.ptrs, src.st, src.pfs, profile, 1.0, nf, w, h, given.ptrs, given.st, given.pfs,
@@ -340,10 +230,10 @@ def test_errors_launch_nothing(L):
         assert np.all(buf.cpu().numpy() == OUT_FILL), "an error return wrote to map_dev"
         assert all(np.all(b == SENTINEL) for b in src.host() + given.host())
 
-    good = _ctx(L, luv, luv)
+    good = ctx(L, luv, luv)
     for block in (8, 48, 0, 128):
         refused(good, ERR_ARG, block=block)                                         # bad block
-    refused(_ctx(L, luv), ERR_STATE)                                                # no source quantizer
+    refused(ctx(L, luv), ERR_STATE)                                                # no source quantizer
     refused(good, ERR_ARG, w=63)                                                    # odd width
     refused(good, ERR_ARG, map_ptr=lambda o: None)                                  # null map_dev
     refused(good, ERR_ARG, map_ptr=lambda o: o.data_ptr() + 4)                      # misaligned map_dev
@@ -352,14 +242,14 @@ def test_errors_launch_nothing(L):
     # ... and one whose first 200 bytes lie in front of the plane: the map's own byte count decides (8 blocks: 768 bytes)
     refused(good, ERR_ARG, map_ptr=lambda o: given.ptrs[1] - 200)
     refused(good, ERR_ARG, map_ptr=lambda o: src.ptrs[1] - 200)
-    refused(_ctx(L, luv, rgb), ERR_UNSUPPORTED)                                     # an RGB source quantizer
-    refused(_ctx(L, deep, luv), ERR_UNSUPPORTED)                                    # a 14-bit target: records in global memory
-    lit = _ctx(L, luv, luv)
+    refused(ctx(L, luv, rgb), ERR_UNSUPPORTED)                                     # an RGB source quantizer
+    refused(ctx(L, deep, luv), ERR_UNSUPPORTED)                                    # a 14-bit target: records in global memory
+    lit = ctx(L, luv, luv)
     lit.tune("force_literal", 1)
     refused(lit, ERR_UNSUPPORTED)                                                   # force_literal
     # the host form: map_words one short
     sp, gp = src.frame(src.host(), 0), given.frame(given.host(), 0)
-    need = _nwords(1, w, h, 16)
+    need = nwords(1, w, h, 16)
     m = np.full(need + GUARD, OUT_FILL, dtype=np.int64)
 
     def host_form(words):
@@ -369,31 +259,31 @@ def test_errors_launch_nothing(L):
 
     assert host_form(need - 1) == ERR_ARG and np.all(m == OUT_FILL)
     # ... and the same arguments are accepted by a context that can
-    got = _tmap(good, src, 1.0, given, 1.0, 16)
+    got = tmap(good, src, 1.0, given, 1.0, 16)
     assert got.shape == (1, 2, 4, 3, 4)
     assert host_form(need) == 0 and np.all(m[need:] == OUT_FILL)
     assert np.array_equal(m[:need].view(np.uint64).reshape(2, 4, 3, 4), got[0])
     lit.tune("force_literal", 0)
-    assert np.array_equal(_tmap(lit, src, 1.0, given, 1.0, 16), got)
+    assert np.array_equal(tmap(lit, src, 1.0, given, 1.0, 16), got)
     assert good.transcode_distortion_map_frame(sp, src.st, w, h, gp, given.st, block=16).shape == (2, 4, 3, 4)
 
 
 # ---- 9. both quantizers are what they were
 def test_the_quantizers_are_untouched(L):
-    c = _ctx(L, CFG["pq10_ycbcr10"], CFG["pq11_luv8"])
+    c = ctx(L, CFG["pq10_ycbcr10"], CFG["pq11_luv8"])
     rng = np.random.default_rng(9)
     w, h, nf = 64, 32, 3
-    src = _random_planes(L, rng, w, h, 2, nf)
+    src = random_planes(L, rng, w, h, 2, nf)
     info = c.quantizer_info()
-    _, before = _transcoded(c, L, src, 1.0, 2, 20.0)
-    given = _random_planes(L, rng, w, h, 2, nf)
-    first = _tmap(c, src, 1.0, given, 20.0, 16)
+    _, before = transcoded(c, L, src, 1.0, 2, 20.0)
+    given = random_planes(L, rng, w, h, 2, nf)
+    first = tmap(c, src, 1.0, given, 20.0, 16)
     c.tune("grid_enc", 2)
     c.tune("block", 64)
-    assert np.array_equal(_tmap(c, src, 1.0, given, 20.0, 16), first)
+    assert np.array_equal(tmap(c, src, 1.0, given, 20.0, 16), first)
     c.tune("grid_enc", 0)
     c.tune("block", 0)
-    _tmap(c, src, 1.0, given, 20.0, 64)
-    _, after = _transcoded(c, L, src, 1.0, 2, 20.0)
+    tmap(c, src, 1.0, given, 20.0, 64)
+    _, after = transcoded(c, L, src, 1.0, 2, 20.0)
     assert all(np.array_equal(a, b) for a, b in zip(before, after))
     assert c.quantizer_info() == info

@@ -13,11 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def L():
-    import lumahdrv_amd
-    lumahdrv_amd.build_library()
-    return lumahdrv_amd
+from tests.support.device import L  # noqa: E402,F401  (the module fixture)
 
 
 def test_every_declared_symbol_is_exported(L):
@@ -53,7 +49,7 @@ def test_no_gpu_means_loud_failure(L):
 
 
 def test_facade_compiles_and_links(L, tmp_path):
-    from tests.test_gpu_facade import build_facade_test
+    from tests.support.tools import build_facade_test
     exe = build_facade_test(str(tmp_path))
     out = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "lumahdrv_amd", "lib", "libluma_hip.so")],
                          capture_output=True, text=True, check=True).stdout

@@ -9,20 +9,14 @@ import numpy as np
 import pytest
 
 from tests.golden.make_golden import CONFIGS
+from tests.support.device import table_for
+from tests.support.host import plane_rows
 
 
 def same(a, b):
     a = np.asarray(a, dtype=np.float32)
     b = np.asarray(b, dtype=np.float32)
     return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-
-
-def table_for(o, cfg):
-    if cfg[0] in (o.PTF_PSI, o.PTF_JND_HDRVDP):
-        d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lumahdrv_amd", "data")
-        nm = "psi" if cfg[0] == o.PTF_PSI else "jnd_hdrvdp"
-        return np.fromfile(os.path.join(d, "ptf_%s_%d.f32" % (nm, cfg[1])), dtype="<f4")
-    return None
 
 
 # ---- the live-reference checks: the reference's results on their (seeded) inputs are recorded in
@@ -300,13 +294,6 @@ def _plane_keys(gp):
     return sorted(k[:-3] for k in gp.files if k.endswith("_in"))
 
 
-def _row_bytes(w, h, profile):
-    sub = profile in (0, 2)
-    bps = 2 if profile > 1 else 1
-    cw = (w + 1) // 2 if sub else w
-    return (w * bps, cw * bps, cw * bps)
-
-
 def test_plane_loops_match_reference_fixtures(oracle_mod, golden_dir):
     """lo_pack_plane / lo_unpack_plane (and the whole-frame drivers built on them) against what the reference's own
     setChannels / getVpxChannels produced: four configurations x the profiles their bit depth allows x two frame sizes,
@@ -324,7 +311,7 @@ def test_plane_loops_match_reference_fixtures(oracle_mod, golden_dir):
         qq = o.Oracle(*cfg, table=table_for(o, cfg))
         planes, st, mean = qq.encode(gp[key + "_in"].copy(), sc, profile)
         assert tuple(st) == tuple(gp[key + "_stride"])
-        rb = _row_bytes(w, h, profile)
+        rb = [plane_rows(w, h, profile, p)[1] for p in range(3)]
         for p in range(3):
             ref = gp[key + "_plane%d" % p]
             assert np.array_equal(planes[p][:, :rb[p]], ref[:, :rb[p]]), (key, p)
@@ -372,7 +359,7 @@ def check_plane_loops(o, tape):
                 st = tuple(s + 2 * p + 1 for p, s in enumerate(st0))             # odd, different per plane
                 a, _, _ = qq.encode(f.copy(), sc, profile)
                 b, _, _ = rp.encode(f.copy(), sc, profile, strides=st)
-                rb = _row_bytes(w, h, profile)
+                rb = [plane_rows(w, h, profile, p)[1] for p in range(3)]
                 for p in range(3):
                     assert np.array_equal(a[p][:, :rb[p]], b[p][:, :rb[p]]), (name, w, h, profile, p)
                     assert np.all(b[p][:, rb[p]:] == 0xA5)

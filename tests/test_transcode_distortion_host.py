@@ -7,42 +7,9 @@ import os
 import numpy as np
 
 from tests.golden import make_transcode_golden as mg
-from tests.test_distortion_host import expected_distortion
+from tests.support.host import expected_distortion, fixture_cases, perturbed
 
 SYMBOLS = ["lumahip_transcode_distortion_frames_device", "lumahip_transcode_distortion_frame_host"]
-
-
-def perturbed(planes, w, h, profile):
-    """a copy of three (rows, stride) uint8 planes with +-1..7 on about a tenth of the samples and a few samples of all zeros / all
-    ones; the same for the same arguments; bytes beyond the sample columns are left alone"""
-    rng = np.random.default_rng(w * 1000 + h * 10 + profile)
-    sub, bps = profile in (0, 2), 2 if profile > 1 else 1
-    out = []
-    for p, pl in enumerate(planes):
-        rows, cols = (h // 2, w // 2) if (p and sub) else (h, w)
-        q = np.array(pl, dtype=np.uint8, copy=True)
-        s = np.ascontiguousarray(q[:rows, :cols * bps])
-        v = (s.view("<u2") if bps == 2 else s).astype(np.int64)
-        hit = rng.random(v.shape) < 0.1
-        hit[0, 0] = True
-        v = np.clip(v + hit * rng.integers(1, 8, size=v.shape) * rng.choice((-1, 1), size=v.shape), 0, 0xFFFF if bps == 2 else 0xFF)
-        v[rows - 1, cols - 1] = 0xFFFF if bps == 2 else 0xFF
-        v[rows - 1, 0] = 0
-        q[:rows, :cols * bps] = v.astype("<u2").view(np.uint8) if bps == 2 else v.astype(np.uint8)
-        out.append(q)
-    return out
-
-
-def fixture_cases(gt):
-    """(key, case, w, h, source profile) for every entry of ref_transcode.npz"""
-    out = []
-    for case in sorted(mg.CASES):
-        for (w, h) in mg.SIZES:
-            for sp in mg.SRC_PROFILES:
-                k = mg.key_of(case, w, h, sp)
-                assert k + "_plane0" in gt.files, k
-                out.append((k, case, w, h, sp))
-    return out
 
 
 def test_library_exports_the_transcode_distortion_symbols():

@@ -8,9 +8,7 @@ import re
 import numpy as np
 
 from tests.golden import make_transcode_golden as mg
-from tests.test_distortion_host import expected_distortion
-from tests.test_distortion_map_host import BLOCKS, expected_distortion_map, fold_map
-from tests.test_transcode_distortion_host import fixture_cases, perturbed
+from tests.support.host import BLOCKS, expected_distortion, expected_distortion_map, fixture_cases, fold_map, perturbed
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["lumahip_transcode_distortion_map_frames_device", "lumahip_transcode_distortion_map_frame_host"]
