@@ -45,7 +45,8 @@ extern "C" {
  *     distortion calls lumahip_transcode_distortion_frames_device and lumahip_transcode_distortion_frame_host; the distortion
  *     map calls lumahip_distortion_map_dims, lumahip_distortion_map_frames_device / _planar / _f16 / _planar_f16 and
  *     lumahip_distortion_map_frame_host; the transcode distortion map calls lumahip_transcode_distortion_map_frames_device and
- *     lumahip_transcode_distortion_map_frame_host.
+ *     lumahip_transcode_distortion_map_frame_host; the moments map calls lumahip_moments_map_dims,
+ *     lumahip_moments_map_frames_device / _planar / _f16 / _planar_f16 and lumahip_moments_map_frame_host.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:
@@ -456,6 +457,44 @@ int lumahip_distortion_map_frames_device_planar_f16(lumahip_ctx *ctx, const uint
 int lumahip_distortion_map_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                       const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *map,
                                       size_t map_words);
+
+/* Moments map: what a structural-similarity index in the code domain (PU-SSIM) needs and the difference statistics above cannot
+ * give -- per plane and block of `block` x `block` luma pixels (block = 8, 16, 32 or 64) the first and second moments of both
+ * signals and their cross moment, as five exact integers.  One launch, no scratch planes; e, g, the blocks and their samples
+ * (co-sited 4:2:0 chroma samples, the cut at the frame's edges) are exactly the distortion map's.  With nbx = ceil(w / block),
+ * nby = ceil(h / block) (lumahip_moments_map_dims; host-only) the words of frame f, block (bx, by), plane p are
+ *     mom_dev[(((f*nby + by)*nbx + bx)*3 + p)*5 + 0..4] = sum e, sum g, sum e*e, sum g*g, sum e*g
+ * over the block's samples: 120 bytes per block.  The launch writes every one of the nframes*nby*nbx*15 words exactly once:
+ * mom_dev needs no initialisation and none is queued.  All arithmetic is integer: the map is the same from run to run whatever
+ * the launch shape; sum e*e - 2 sum e*g + sum g*g is the distortion map's sse of the same block, and adding the words of 2 x 2
+ * neighbouring blocks gives the map of twice the block size -- which is also how a caller forms overlapping windows (16 x 16
+ * windows at stride 8 from 8-blocks); the calls themselves deliver disjoint blocks only, and a frame's moments are plain sums
+ * over its blocks.
+ * Arguments, supported set, kernel choice from the arguments alone, stream, unordered sections and the honoured lumahip_tune keys
+ * are those of the matching lumahip_distortion_map_frames_device form, with mom_dev (required, 8-byte aligned, its
+ * nframes*nby*nbx*15 words sharing no byte with the frames or the given planes) in the place of map_dev.  Errors, all before
+ * anything is launched (mom_dev is then untouched): those of that call, and LUMAHIP_ERR_ARG for a block other than 8, 16, 32 or 64
+ * and, in the host form, for mom_words < nbx*nby*15.
+ * The host form takes one float frame (LumaFrame layout) and the given planes in host memory, uploads them, runs one launch,
+ * downloads the nbx*nby*15 words into `mom` and returns synchronously. */
+int lumahip_moments_map_dims(unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby);
+int lumahip_moments_map_frames_device(lumahip_ctx *ctx, const float *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                      unsigned h, float sc, int profile, const unsigned char *const planes_dev[3], const int stride[3],
+                                      const size_t plane_frame_stride[3], unsigned block, uint64_t *mom_dev);
+int lumahip_moments_map_frames_device_planar(lumahip_ctx *ctx, const float *const rgb_planes_dev[3], size_t frame_stride,
+                                             unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                             const unsigned char *const planes_dev[3], const int stride[3],
+                                             const size_t plane_frame_stride[3], unsigned block, uint64_t *mom_dev);
+int lumahip_moments_map_frames_device_f16(lumahip_ctx *ctx, const uint16_t *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                          unsigned h, float sc, int profile, const unsigned char *const planes_dev[3],
+                                          const int stride[3], const size_t plane_frame_stride[3], unsigned block, uint64_t *mom_dev);
+int lumahip_moments_map_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t *const rgb_planes_dev[3], size_t frame_stride,
+                                                 unsigned nframes, unsigned w, unsigned h, float sc, int profile,
+                                                 const unsigned char *const planes_dev[3], const int stride[3],
+                                                 const size_t plane_frame_stride[3], unsigned block, uint64_t *mom_dev);
+int lumahip_moments_map_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                   const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *mom,
+                                   size_t mom_words);
 
 /* Transcode distortion: how far GIVEN code planes in the target's format -- what came back from the VP9 decoder on the delivery
  * side -- are from the planes the SOURCE stream's planes transcode to, in the launch that would have transcoded them; no float

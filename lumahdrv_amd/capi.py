@@ -44,6 +44,8 @@ SYMBOLS = [
     "lumahip_distortion_map_dims", "lumahip_distortion_map_frames_device", "lumahip_distortion_map_frames_device_planar",
     "lumahip_distortion_map_frames_device_f16", "lumahip_distortion_map_frames_device_planar_f16", "lumahip_distortion_map_frame_host",
     "lumahip_transcode_distortion_map_frames_device", "lumahip_transcode_distortion_map_frame_host",
+    "lumahip_moments_map_dims", "lumahip_moments_map_frames_device", "lumahip_moments_map_frames_device_planar",
+    "lumahip_moments_map_frames_device_f16", "lumahip_moments_map_frames_device_planar_f16", "lumahip_moments_map_frame_host",
     "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
 ]
 
@@ -82,7 +84,7 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
-                  "lumahip_transcode_distortion_map.hip")
+                  "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip")
 
 
 def kernel_source_sha() -> str:
@@ -188,6 +190,12 @@ def lib():
     L.lumahip_distortion_map_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
     L.lumahip_distortion_map_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
     L.lumahip_distortion_map_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, u, vp, sz]
+    L.lumahip_moments_map_dims.argtypes = [u, u, u, C.POINTER(u), C.POINTER(u)]
+    L.lumahip_moments_map_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_moments_map_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_moments_map_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_moments_map_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
+    L.lumahip_moments_map_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, u, vp, sz]
     L.lumahip_transcode_distortion_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, vp]
     L.lumahip_transcode_distortion_map_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, u, vp]
     L.lumahip_transcode_distortion_map_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, u, vp, sz]
@@ -438,7 +446,10 @@ def block_sample_counts(w: int, h: int, profile: int, block: int) -> np.ndarray:
     """(nby, nbx, 3) int64: how many samples of each plane a block of a distortion map covers -- block x block luma pixels cut at
     the frame's edges, and on the 4:2:0 chroma planes (profiles 0 and 2) the samples co-sited with them.  code_psnr(map[by, bx, p, 0],
     counts[by, bx, p], peak) is the block's PSNR"""
-    nbx, nby = distortion_map_dims(w, h, block)
+    return _block_sample_counts(w, h, profile, block, *distortion_map_dims(w, h, block))
+
+
+def _block_sample_counts(w, h, profile, block, nbx, nby) -> np.ndarray:
     out = np.empty((nby, nbx, 3), dtype=np.int64)
     for p in range(3):
         sub = p > 0 and profile in (0, 2)
@@ -447,6 +458,48 @@ def block_sample_counts(w: int, h: int, profile: int, block: int) -> np.ndarray:
         ny = np.minimum(ph, (np.arange(nby) + 1) * b) - np.arange(nby) * b
         out[:, :, p] = ny[:, None] * nx[None, :]
     return out
+
+
+def moments_map_dims(w: int, h: int, block: int):
+    """(nbx, nby): blocks per frame of a moments map, ceil(w / block) x ceil(h / block); block is 8, 16, 32 or 64"""
+    nbx, nby = C.c_uint(0), C.c_uint(0)
+    rc = lib().lumahip_moments_map_dims(w, h, block, C.byref(nbx), C.byref(nby))
+    if rc != 0:
+        raise LumaHipError(rc, "moments map: block must be 8, 16, 32 or 64 (got %r)" % (block,))
+    return int(nbx.value), int(nby.value)
+
+
+def moments_sample_counts(w: int, h: int, profile: int, block: int) -> np.ndarray:
+    """(nby, nbx, 3) int64: the samples N behind each entry of a moments map -- block_sample_counts with blocks of 8 allowed"""
+    return _block_sample_counts(w, h, profile, block, *moments_map_dims(w, h, block))
+
+
+def code_ssim(moments, counts, peak, k1=0.01, k2=0.03) -> np.ndarray:
+    """Structural similarity in the code domain from the five sums of a moments map (Context.moments_map_*): moments (..., 5) =
+    {Se, Sg, See, Sgg, Seg}, counts (...) = the samples N behind them, `peak` the largest code of the plane.  The usual SSIM with
+    population variances and C1 = (k1 peak)^2, C2 = (k2 peak)^2, multiplied through by N^4:
+        (2 Se Sg + N^2 C1) (2 (N Seg - Se Sg) + N^2 C2) / ((Se^2 + Sg^2 + N^2 C1) ((N See - Se^2) + (N Sgg - Sg^2) + N^2 C2))
+    The four integer parts are formed exactly in int64 (N <= 2^12, sums <= 2^28, second moments <= 2^44: every product is below
+    2^57), so the cancellation in N See - Se^2 never happens in floating point and identical planes give exactly 1.0.  Returns a
+    float64 array (...)."""
+    m = np.asarray(moments)
+    if m.shape[-1:] != (5,):
+        raise ValueError("code_ssim needs moments of shape (..., 5)")
+    m = m.astype(np.int64)
+    n = np.asarray(counts).astype(np.int64)
+    if n.shape != m.shape[:-1]:
+        raise ValueError("code_ssim needs counts of the moments' shape without its last axis")
+    if peak <= 0 or np.any(n <= 0) or np.any(n > 4096):
+        raise ValueError("code_ssim needs peak > 0 and 0 < counts <= 4096")
+    se, sg, see, sgg, seg = (m[..., k] for k in range(5))
+    mean_num = 2 * se * sg
+    mean_den = se * se + sg * sg
+    cov_num = 2 * (n * seg - se * sg)
+    var_den = (n * see - se * se) + (n * sgg - sg * sg)
+    n2 = (n * n).astype(np.float64)
+    c1 = n2 * (float(k1) * float(peak)) ** 2
+    c2 = n2 * (float(k2) * float(peak)) ** 2
+    return ((mean_num + c1) * (cov_num + c2)) / ((mean_den + c1) * (var_den + c2))
 
 
 def _arr3(ctype, vals):
@@ -595,6 +648,20 @@ class Context:
         self._chk(self.L.lumahip_distortion_map_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
                                                            _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
                                                            block, out.ctypes.data, out.size))
+        return out
+
+    def moments_map_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2, block=8) -> np.ndarray:
+        """per block of block x block luma pixels (8, 16, 32 or 64) and plane the five sums {Se, Sg, See, Sgg, Seg} of the frame's
+        codes e and the given samples g: a (nby, nbx, 3, 5) uint64 array, in one launch; moments_sample_counts gives the samples
+        behind each entry and code_ssim the structural similarity"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        _, h, w = rgb.shape
+        planes = [np.ascontiguousarray(p) for p in planes]
+        nbx, nby = moments_map_dims(w, h, block)
+        out = np.zeros((nby, nbx, 3, 5), dtype=np.uint64)
+        self._chk(self.L.lumahip_moments_map_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
+                                                        _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
+                                                        block, out.ctypes.data, out.size))
         return out
 
     def transcode_distortion_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
@@ -777,6 +844,33 @@ class Context:
                                                                          w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
                                                                          _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
                                                                          block, map_ptr))
+
+    # the moments of both signals per block x block luma pixels (8, 16, 32 or 64): mom_ptr receives nframes x nby x nbx x 3 planes x
+    # {Se, Sg, See, Sgg, Seg} as uint64, every word written by the launch (moments_map_dims, moments_sample_counts, code_ssim)
+    def moments_map_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides,
+                                  block, mom_ptr):
+        self._chk(self.L.lumahip_moments_map_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                           _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                           _arr3(C.c_size_t, plane_frame_strides), block, mom_ptr))
+
+    def moments_map_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                         plane_frame_strides, block, mom_ptr):
+        self._chk(self.L.lumahip_moments_map_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w,
+                                                                  h, sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                                  _arr3(C.c_size_t, plane_frame_strides), block, mom_ptr))
+
+    def moments_map_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                      plane_frame_strides, block, mom_ptr):
+        self._chk(self.L.lumahip_moments_map_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
+                                                               _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                                                               _arr3(C.c_size_t, plane_frame_strides), block, mom_ptr))
+
+    def moments_map_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                                             plane_frame_strides, block, mom_ptr):
+        self._chk(self.L.lumahip_moments_map_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
+                                                                      w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
+                                                                      _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
+                                                                      block, mom_ptr))
 
     # distortion of given planes against the source planes' own transcode: the arguments are transcode_frames_device's, the
     # target-side planes are read, out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ} as uint64 (zeroed by the call)

@@ -25,3 +25,6 @@ FLAGS_lumahip_distortion_f16 := $(FLAGS_lumahip_encode)
 #   lumahip_distortion_map / _f16: the same -- k_distortion_map is k_distortion with the accumulation in space.
 FLAGS_lumahip_distortion_map := $(FLAGS_lumahip_encode)
 FLAGS_lumahip_distortion_map_f16 := $(FLAGS_lumahip_encode)
+#   lumahip_moments_map / _f16: the same -- k_moments_map is k_distortion_map with another consumer.
+FLAGS_lumahip_moments_map := $(FLAGS_lumahip_encode)
+FLAGS_lumahip_moments_map_f16 := $(FLAGS_lumahip_encode)

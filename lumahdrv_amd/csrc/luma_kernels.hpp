@@ -639,11 +639,12 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
 }
 
 // ---- THE KERNELS THAT END IN enc_codes ----------------------------------------------------------------
-// Two front ends produce a transformed unit (c0, c1, c2), two consumers take the codes enc_codes makes of it, and the measuring one
-// sums per frame (DistAcc, dist_flush) or per block (DistBlockAcc, dist_map_flush):
-//                                                        store (EncStoreUnit)   measure (DistMeasureUnit)   ... per block
-//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion                k_distortion_map
-//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion      k_transcode_distortion_map
+// Two front ends produce a transformed unit (c0, c1, c2), three consumers take the codes enc_codes makes of it; the one that measures
+// differences sums per frame (DistAcc, dist_flush) or per block (DistBlockAcc, dist_map_flush), the one that measures moments per
+// block only (MomentBlockAcc, the same dist_map_flush):
+//                                                        store (EncStoreUnit)   measure (DistMeasureUnit)   ... per block                 moments per block (MomentMeasureUnit)
+//   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion                k_distortion_map              k_moments_map
+//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion      k_transcode_distortion_map    (not built yet)
 //                   enc_transform
 // A kernel is its front end, its consumer and the persistent loop that orders their loads against each other; the loops differ on
 // purpose (stores before the next loads / the given words travelling along, one flush site) and stay written out.  Also written
@@ -1760,8 +1761,12 @@ struct DistMapArgs {
     MapGeom m;
 };
 
+// What a map kernel's helpers (dist_map_words, map_lanes_meet, dist_map_flush) ask of a lane's per-block record: WORDS per block
+// in LDS and in the map, MIN_B the smallest block its calls accept (a map tile holds up to 256 / MIN_B blocks: map_lds_words), and
+// the overloads map_lanes_step / map_wave_has / map_lanes_add below.
 // a lane's share of ONE block: at most 64 rows x 4 columns, so only the squares need 64 bits -- and so do their sums over a block
 struct DistBlockAcc {
+    static constexpr int WORDS = 12, MIN_B = 16;
     uint64_t sse[3];
     uint32_t sad[3], mx[3], nd[3];
     LH_DEVS DistBlockAcc() { reset(); }
@@ -1775,13 +1780,35 @@ struct DistBlockAcc {
     }
 };
 
-constexpr int DIST_MAP_LDS_WORDS = 16 * 12;   // 64 VW / B <= 16 blocks per map tile
+// The moments of both signals (k_moments_map): sum e, sum g, sum e^2, sum g^2, sum e g of a lane's share of ONE block.  256 samples
+// of at most 65535: the first moments fit 32 bits (< 2^24), a product of two samples fills 32 and their sums need 64.
+struct MomentBlockAcc {
+    static constexpr int WORDS = 15, MIN_B = 8;
+    uint32_t se[3], sg[3];
+    uint64_t see[3], sgg[3], seg[3];
+    LH_DEVS MomentBlockAcc() { reset(); }
+    LH_DEVS void reset()
+    {
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            se[p] = sg[p] = 0;
+            see[p] = sgg[p] = seg[p] = 0;
+        }
+    }
+};
+
+// LDS words the blocks of a map tile meet in: 64 VW / B <= 256 / MIN_B blocks per map tile
+template <typename Acc>
+constexpr int map_lds_words() { return 256 / Acc::MIN_B * Acc::WORDS; }
+constexpr int DIST_MAP_LDS_WORDS = map_lds_words<DistBlockAcc>();       // 16 x 12: 1536 B
+constexpr int MOMENTS_MAP_LDS_WORDS = map_lds_words<MomentBlockAcc>();  // 32 x 15: 3840 B
 
 // the map's LDS words, zeroed (as dist_words: before stage_tables, which synchronises; force-inlined, the array is the kernel's)
+template <typename Acc = DistBlockAcc>
 LH_DEV unsigned long long *dist_map_words()
 {
-    __shared__ unsigned long long s_map[DIST_MAP_LDS_WORDS];
-    for (int i = threadIdx.x; i < DIST_MAP_LDS_WORDS; i += blockDim.x)
+    __shared__ unsigned long long s_map[map_lds_words<Acc>()];
+    for (int i = threadIdx.x; i < map_lds_words<Acc>(); i += blockDim.x)
         s_map[i] = 0;
     return s_map;
 }
@@ -1820,13 +1847,29 @@ LH_DEV void map_lanes_step(DistBlockAcc &acc, Xch xch)
     }
 }
 
-// The `lanes` (4, 8, 16 or 32; uniform) adjacent lanes of a block, aligned to that count: afterwards every one of them holds the
-// block's sums over this wave's rows.  Pairs, then quads (quad_perm), the other quad of eight (row_half_mirror: its lanes hold the
-// same sums by then), the other eight of a row (row_mirror), the other row of 32
-LH_DEV void map_lanes_meet(DistBlockAcc &acc, int lanes)
+template <typename Xch>
+LH_DEV void map_lanes_step(MomentBlockAcc &acc, Xch xch)
+{
+    const auto x64 = [&](uint64_t v) { return ((uint64_t)xch((uint32_t)(v >> 32)) << 32) | xch((uint32_t)v); };
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        acc.se[p] += xch(acc.se[p]);
+        acc.sg[p] += xch(acc.sg[p]);
+        acc.see[p] += x64(acc.see[p]);
+        acc.sgg[p] += x64(acc.sgg[p]);
+        acc.seg[p] += x64(acc.seg[p]);
+    }
+}
+
+// The `lanes` (2 -- blocks of 8 at VW 4, MomentBlockAcc only --, 4, 8, 16 or 32; uniform) adjacent lanes of a block, aligned to that
+// count: afterwards every one of them holds the block's sums over this wave's rows.  Pairs, then quads (quad_perm), the other quad of
+// eight (row_half_mirror: its lanes hold the same sums by then), the other eight of a row (row_mirror), the other row of 32
+template <typename Acc>
+LH_DEV void map_lanes_meet(Acc &acc, int lanes)
 {
     map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0xb1>(v); });   // quad_perm [1, 0, 3, 2]
-    map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x4e>(v); });   // quad_perm [2, 3, 0, 1]
+    if (Acc::MIN_B >= 16 || lanes >= 4)   // (a record whose smallest block is 16 never meets in pairs only)
+        map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x4e>(v); });   // quad_perm [2, 3, 0, 1]
     if (lanes >= 8)
         map_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x141>(v); });   // row_half_mirror
     if (lanes >= 16)
@@ -1835,34 +1878,54 @@ LH_DEV void map_lanes_meet(DistBlockAcc &acc, int lanes)
         map_lanes_step(acc, [](uint32_t v) { return swz16_lane(v); });
 }
 
-// The end of map tile m, called by every thread of the workgroup at the same point (m is workgroup-uniform): lanes, waves, stores.
-template <int VW>
-LH_DEV void dist_map_flush(DistBlockAcc &acc, unsigned long long *s_map, const MapGeom &a, const FrameGeom &g, uint64_t *map, int m, int tx)
+// whether this wave has anything to add to the LDS words (uniform).  Differences: a wave that saw none anywhere has not -- the words
+// are zero already.  Moments: always -- they are non-zero for identical planes
+LH_DEV bool map_wave_has(const DistBlockAcc &acc) { return __builtin_amdgcn_ballot_w64((acc.nd[0] | acc.nd[1] | acc.nd[2]) != 0) != 0; }
+LH_DEV bool map_wave_has(const MomentBlockAcc &) { return true; }
+
+// the first lane of a block's group adds the group's sums into the block's words w
+LH_DEV void map_lanes_add(const DistBlockAcc &acc, unsigned long long *w)
 {
-    const int lanes = a.B / VW;                    // of a wave per block: 4 ... 32, a power of two
-    const int lanes_log2 = __builtin_ctz(lanes);   // (uniform)
-    // (a wave that saw no difference anywhere has nothing to add: the words are zero already)
-    if (__builtin_amdgcn_ballot_w64((acc.nd[0] | acc.nd[1] | acc.nd[2]) != 0) != 0) {
-        map_lanes_meet(acc, lanes);
-        if ((tx & (lanes - 1)) == 0) {   // (every lane adding into LDS itself measured no better: profiles/map_lanes_ab.txt)
-            unsigned long long *w = s_map + (tx >> lanes_log2) * 12;
 #pragma unroll
-            for (int p = 0; p < 3; p++)
-                if (acc.nd[p] != 0) {
-                    atomicAdd(&w[4 * p + 0], (unsigned long long)acc.sse[p]);
-                    atomicAdd(&w[4 * p + 1], (unsigned long long)acc.sad[p]);
-                    atomicMax(&w[4 * p + 2], (unsigned long long)acc.mx[p]);
-                    atomicAdd(&w[4 * p + 3], (unsigned long long)acc.nd[p]);
-                }
+    for (int p = 0; p < 3; p++)
+        if (acc.nd[p] != 0) {
+            atomicAdd(&w[4 * p + 0], (unsigned long long)acc.sse[p]);
+            atomicAdd(&w[4 * p + 1], (unsigned long long)acc.sad[p]);
+            atomicMax(&w[4 * p + 2], (unsigned long long)acc.mx[p]);
+            atomicAdd(&w[4 * p + 3], (unsigned long long)acc.nd[p]);
         }
+}
+LH_DEV void map_lanes_add(const MomentBlockAcc &acc, unsigned long long *w)
+{
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        atomicAdd(&w[5 * p + 0], (unsigned long long)acc.se[p]);
+        atomicAdd(&w[5 * p + 1], (unsigned long long)acc.sg[p]);
+        atomicAdd(&w[5 * p + 2], (unsigned long long)acc.see[p]);
+        atomicAdd(&w[5 * p + 3], (unsigned long long)acc.sgg[p]);
+        atomicAdd(&w[5 * p + 4], (unsigned long long)acc.seg[p]);
+    }
+}
+
+// The end of map tile m, called by every thread of the workgroup at the same point (m is workgroup-uniform): lanes, waves, stores.
+template <int VW, typename Acc>
+LH_DEV void dist_map_flush(Acc &acc, unsigned long long *s_map, const MapGeom &a, const FrameGeom &g, uint64_t *map, int m, int tx)
+{
+    constexpr int W = Acc::WORDS;
+    const int lanes = a.B / VW;                    // of a wave per block: (2,) 4 ... 32, a power of two
+    const int lanes_log2 = __builtin_ctz(lanes);   // (uniform)
+    if (map_wave_has(acc)) {
+        map_lanes_meet(acc, lanes);
+        if ((tx & (lanes - 1)) == 0)   // (every lane adding into LDS itself measured no better: profiles/map_lanes_ab.txt)
+            map_lanes_add(acc, s_map + (tx >> lanes_log2) * W);
     }
     __syncthreads();
     const int f = m / a.mapTilesPerFrame, r = m - f * a.mapTilesPerFrame;
     const int by = r / g.tilesX, bx = r - by * g.tilesX;
     const int b0 = bx * (64 >> lanes_log2);          // the tile's first block: inside the map, as the tile is
     const int nb = min(64 >> lanes_log2, a.nbx - b0);   // (blocks past nbx hold no pixel: their words stayed zero)
-    unsigned long long *dst = reinterpret_cast<unsigned long long *>(map) + (((size_t)f * a.nby + by) * a.nbx + b0) * 12;
-    for (int i = threadIdx.x; i < nb * 12; i += blockDim.x) {
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(map) + (((size_t)f * a.nby + by) * a.nbx + b0) * W;
+    for (int i = threadIdx.x; i < nb * W; i += blockDim.x) {
         dst[i] = s_map[i];
         s_map[i] = 0;
     }
@@ -1901,6 +1964,119 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
             float c0[2 * VW], c1[2 * VW], c2[2 * VW];
             enc_transform<CS, VW, LM == 5 || LM == 6, LM == 6, false>(u, a.e, fr.k, c0, c1, c2, st, fr.s_half);
             const DistMeasureUnit<SUB, VW, DistBlockAcc> out{given, a.g, acc, mask};
+            enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), fr.s_rec, out);   // (record searches: no table pointer)
+        }
+        const bool last = s + 1 == a.m.S;
+        const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
+        const int t = map_subtile(a.m, a.e.g, mn, sn);
+        enc_load<VW, IN16>(u, a.e, t, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
+        if (last) {
+            dist_map_flush<VW>(acc, s_map, a.m, a.e.g, a.map, m, tx);
+            acc.reset();
+        }
+        m = mn;
+        s = sn;
+    }
+}
+
+// ---- MOMENTS MAP ------------------------------------------------------------------------------------
+// What a structural-similarity index in the code domain needs of every B x B block of luma pixels (B = 8, 16, 32 or 64; block
+// membership is the distortion map's): per plane the five sums {sum e, sum g, sum e^2, sum g^2, sum e g} over the block's samples, e and
+// g exactly k_distortion_map's -- map[(((f * nby + by) * nbx + bx) * 3 + p) * 5 + k].  sum e^2 - 2 sum e g + sum g^2 is that map's sse.
+// k_distortion_map's front end, loop, prefetch order, flush site and owner per word with another consumer (MomentMeasureUnit) and
+// another record (MomentBlockAcc): 15 words per block, LDS adds only, no shortcut for waves without a difference.  B = 8 makes a
+// block 2 lanes at VW 4 (map_lanes_meet's pair step alone) and a map tile 32 blocks.
+// Reads 12 + 3 B per pixel (6 + 3 from binary16 frames), writes 120 B per block; no scratch planes, no global atomic, no memset.
+struct MomentsMapArgs {
+    EncArgs e;         // as DistArgs::e
+    DecArgs g;         // as DistArgs::g
+    uint64_t *map;     // [nframes][nby][nbx][3 planes][se, sg, see, sgg, seg]; needs no zeroing
+    MapGeom m;
+};
+
+// Row r of plane pl of the given unit exactly as DistMeasureUnit::row fetches it.  That one keeps its own copy of these lines: with
+// the fetch behind a function -- free, member of a base, by reference or by value -- the compiler allocates the registers of every
+// k_distortion, k_distortion_map and k_transcode_distortion(_map) kernel differently (same instructions, other registers and order;
+// profiles/moments_map_codegen.txt), and those kernels are measured as they are.
+template <bool SUB, int VW, int N>
+LH_DEV void given_row(const DecRaw<SUB, VW> &g, const DecArgs &d, int pl, int r, int (&given)[N])
+{
+    if (d.aligned) {
+        unpack_raw<N>(pl == 0 ? g.y[r] : pl == 1 ? g.c1[r] : g.c2[r], given, d.bps);
+    } else {
+        const int y0 = (SUB && pl) ? g.uy : 2 * g.uy;   // first plane row of the unit
+        load_samples<N>(d.src[pl] + (size_t)g.f * d.src_frame_stride[pl] + (size_t)(y0 + r) * d.stride[pl] + (size_t)g.ux * N * d.bps, given,
+                        d.bps, 0);
+    }
+}
+
+// the consumer of enc_codes that accumulates the moments of both signals, row by row
+template <bool SUB, int VW>
+struct MomentMeasureUnit {
+    const DecRaw<SUB, VW> &g;
+    const DecArgs &d;
+    MomentBlockAcc &acc;
+    int mask;   // 0xffff / 0xff: what store_samples keeps of a code
+    template <int N>
+    LH_DEVS void row(int pl, int r, const int (&codes)[N]) const
+    {
+        int given[N];
+        given_row<SUB, VW, N>(g, d, pl, r, given);
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            const uint32_t e = (uint32_t)(codes[i] & mask), gv = (uint32_t)given[i];   // <= 65535: a product fits 32 bits
+            acc.se[pl] += e;
+            acc.sg[pl] += gv;
+            acc.see[pl] += (uint64_t)(e * e);
+            acc.sgg[pl] += (uint64_t)(gv * gv);
+            acc.seg[pl] += (uint64_t)(e * gv);
+        }
+    }
+};
+
+// Register budget (DESIGN.md 3.11 has the compiler's table): the record is 24 registers against DistBlockAcc's 15.  The variants
+// that fit 128 registers with it keep k_distortion_map's bound -- 1024 threads, four waves per SIMD; those that would spill there
+// (moments_wide) are allocated for three waves per SIMD (168 registers) in workgroups of at most 512 threads, which distortion_plan
+// clamps the launch to (moments_threads_bound).
+constexpr bool moments_wide(int cs, bool sub, int vw, int lm)
+{
+    // every VW 2 variant fits 128 registers, and so do the 4:2:0 RGB / XYZ ones at VW 4; whatever the search mode
+    (void)lm;
+    return vw == 4 && !((cs == CS_RGB || cs == CS_XYZ) && sub);
+}
+constexpr int moments_threads_bound(int cs, bool sub, int vw, int lm) { return moments_wide(cs, sub, vw, lm) ? 512 : 1024; }
+
+template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
+__global__ __launch_bounds__(moments_threads_bound(CS, SUB, VW, LM)) __attribute__((amdgpu_waves_per_eu(moments_wide(CS, SUB, VW, LM) ? 3 : 4)))
+void k_moments_map(const MomentsMapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    static_assert(LM == 3 || LM == 7 || LM == 5 || LM == 6, "search records in LDS");
+    unsigned long long *const s_map = dist_map_words<MomentBlockAcc>();
+    stage_tables<FrameFront<CS, LM>::WHAT>(smem, a.e.q, a.e.half);
+    const FrameFront<CS, LM> fr(smem, a.e);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    MomentBlockAcc acc;
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    EncUnit<VW> u;
+    DecRaw<SUB, VW> given;
+    int m = blockIdx.x, s = 0;
+    {
+        const int t = map_subtile(a.m, a.e.g, m, 0);
+        enc_load<VW, IN16>(u, a.e, t, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
+    }
+    while (m < a.m.totalMapTiles) {   // workgroup-uniform
+        if (u.valid) {
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CS, VW, LM == 5 || LM == 6, LM == 6, false>(u, a.e, fr.k, c0, c1, c2, st, fr.s_half);
+            const MomentMeasureUnit<SUB, VW> out{given, a.g, acc, mask};
             enc_codes<CS, SUB, VW, LM == 6 ? 5 : LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), fr.s_rec, out);   // (record searches: no table pointer)
         }
         const bool last = s + 1 == a.m.S;

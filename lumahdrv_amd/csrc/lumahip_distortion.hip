@@ -10,11 +10,15 @@ using namespace lhost;
 
 namespace lhost {
 
-int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, size_t out_bytes, unsigned map_block,
+int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, DistWhat kind, unsigned map_block,
                     hipStream_t stream, DistortionPlan &p)
 {
-    const char *const what = map_block ? "distortion map" : "distortion";
-    const char *const out_name = map_block ? "map_dev" : "out_dev";
+    const char *const what = kind == DistWhat::Moments ? "moments map" : kind == DistWhat::Map ? "distortion map" : "distortion";
+    const char *const out_name = kind == DistWhat::Moments ? "mom_dev" : kind == DistWhat::Map ? "map_dev" : "out_dev";
+    if (kind == DistWhat::Frame)
+        map_block = 0;
+    else if (!dist_block_ok(kind, map_block))
+        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", what, kind == DistWhat::Moments ? "8, " : "", map_block);
     const bool in16 = f.elem == Elem::F16;
     const unsigned nframes = f.nframes, w = f.w, h = f.h;
     const int profile = given.profile;
@@ -35,6 +39,8 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     } else if ((rc = check_out_words(c, out))) {
         return rc;
     }
+    const size_t out_bytes =
+        map_block ? (size_t)nframes * dist_map_words(w, h, map_block, dist_words_per_block(kind)) * sizeof(uint64_t) : out_words_bytes(nframes);
     const size_t esz = elem_size(f.elem);
     bool al4;
     if ((rc = check_frame_alignment(c, f, esz, &al4)))
@@ -59,7 +65,7 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     bool ycode = !in16 && ycbcr_composite_ready(c);
     const float *half = nullptr;
     // (+ the words the waves of a workgroup meet in: 12, or the blocks of a map tile)
-    const size_t meet = map_block ? DIST_MAP_LDS_WORDS * sizeof(uint64_t) : 128;
+    const size_t meet = (kind == DistWhat::Moments ? MOMENTS_MAP_LDS_WORDS : kind == DistWhat::Map ? DIST_MAP_LDS_WORDS : 16) * sizeof(uint64_t);
     if (in16 && ycbcr_composite_ready(c) && c->half_mode != 0 && lds_bytes(c, true, cs, true, true) + meet <= LUMAHIP_LDS_PER_WORKGROUP) {
         if ((rc = half_table_for(c, sc, &half)))
             return rc;
@@ -80,6 +86,10 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     // the map: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
     if (map_block && p.threads > 64 * (int)map_block / 2)
         p.threads = 64 * (int)map_block / 2;
+    p.kmode = half ? 6 : ycode ? 5 : mode;
+    // ... and the moments kernels that are register-allocated for fewer threads run with at most those
+    if (kind == DistWhat::Moments && p.threads > moments_threads_bound(cs, p.sub, p.vw, p.kmode))
+        p.threads = moments_threads_bound(cs, p.sub, p.vw, p.kmode);
     p.lds = lds;
     p.e = EncArgs{};
     p.g = DecArgs{};
@@ -95,7 +105,6 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     p.e.sc = sc;
     read_planes(p.g, given, p.vw);
     p.e.bps = p.g.bps;
-    p.kmode = half ? 6 : ycode ? 5 : mode;
     p.grid = grid_for(c, p.threads, p.e.g.totalTiles, 0, 0, half ? 2 : cs == CS_YCBCR ? 1 : 0);
     return LUMAHIP_OK;
 }
@@ -103,7 +112,7 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
 int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out, const DistortionLaunch &o)
 {
     DistortionPlan p;
-    if (int rc = distortion_plan(c, f, sc, given, out, out_words_bytes(f.nframes), 0, o.stream, p))
+    if (int rc = distortion_plan(c, f, sc, given, out, DistWhat::Frame, 0, o.stream, p))
         return rc;
     DistArgs a{};
     a.e = p.e;

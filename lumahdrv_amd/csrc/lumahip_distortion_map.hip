@@ -12,10 +12,8 @@ namespace lhost {
 
 int distortion_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *map, const DistortionLaunch &o)
 {
-    if (!dist_map_block_ok(block))
-        return fail(c, LUMAHIP_ERR_ARG, "distortion map: block must be 16, 32 or 64 (got %u)", block);
     DistortionPlan p;
-    if (int rc = distortion_plan(c, f, sc, given, map, (size_t)f.nframes * dist_map_words(f.w, f.h, block) * sizeof(uint64_t), block, o.stream, p))
+    if (int rc = distortion_plan(c, f, sc, given, map, DistWhat::Map, block, o.stream, p))
         return rc;
     DistMapArgs a{};
     a.e = p.e;

@@ -1154,6 +1154,32 @@ extern "C" int lumahip_distortion_map_frame_host(lumahip_ctx *c, const float *rg
     return words_down(c, map, words);
 }
 
+// ... -> the frame's moments map (lumahip_moments_map.hip): nbx * nby * 15 words, synchronously
+extern "C" int lumahip_moments_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                              const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *mom,
+                                              size_t mom_words)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!rgb || !planes || !stride || !mom)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (!dist_block_ok(DistWhat::Moments, block))
+        return fail(c, LUMAHIP_ERR_ARG, "moments map: block must be 8, 16, 32 or 64 (got %u)", block);
+    StagedPlanes given{"", planes, stride, profile};
+    const size_t nfl = (size_t)3 * w * h, words = dist_map_words(w, h, block, dist_words_per_block(DistWhat::Moments));
+    int rc = planes_staging(c, w, h, nullptr, given, words);
+    if (rc)
+        return rc;
+    if (mom_words < words)
+        return fail(c, LUMAHIP_ERR_ARG, "moments map: %zu words for a map of %zu", mom_words, words);
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
+        (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
+        (rc = moments_map_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), block,
+                               reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
+        return rc;
+    return words_down(c, mom, words);
+}
+
 // Source planes and given planes in host memory -> the 12 words of the transcode distortion (lumahip_transcode_distortion.hip),
 // synchronously; the context's plane staging holds both sets
 extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],

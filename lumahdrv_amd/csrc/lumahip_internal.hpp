@@ -21,6 +21,8 @@
 //                       planes against frames may be, for these units and the next --, the distortion dispatch and the _device entry points
 //   lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip  pick_dist<DistMapFamily, .> (every k_distortion_map), the map's dispatch
 //                       and its _device entry points
+//   lumahip_moments_map.hip / lumahip_moments_map_f16.hip  pick_dist<MomentsMapFamily, .> (every k_moments_map), the moments map's
+//                       dispatch and its _device entry points
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -557,11 +559,22 @@ struct DistortionPlan {
     lh::EncArgs e;   // DistArgs::e
     lh::DecArgs g;   // DistArgs::g
 };
-// out: the launch's words (non-null, 8-byte aligned, out_bytes of them sharing no byte with the frames or the given planes);
-// map_block: 0 = the 12 words per frame, else the block size of the distortion map -- 16, 32 or 64 -- whose kernels meet in
-// lh::DIST_MAP_LDS_WORDS of LDS and whose workgroup is clamped to a power of two of at most 64 * map_block / 2 threads (a map tile
-// is a whole number of standard tiles).  Every error is raised here, before anything of the launch is queued.
-int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, size_t out_bytes, unsigned map_block,
+// What the launch delivers.  Frame: the 12 words per frame (map_block ignored).  Map: the distortion map -- blocks of 16, 32 or 64,
+// 12 words each, lh::DIST_MAP_LDS_WORDS of LDS to meet in.  Moments: the moments map -- blocks of 8, 16, 32 or 64, 15 words each,
+// lh::MOMENTS_MAP_LDS_WORDS of LDS, the workgroup clamped to its kernels' launch bound (lh::moments_threads_bound).
+enum class DistWhat { Frame, Map, Moments };
+static inline int dist_words_per_block(DistWhat what) { return what == DistWhat::Moments ? 15 : 12; }
+static inline bool dist_map_block_ok(unsigned block) { return block == 16 || block == 32 || block == 64; }
+static inline bool dist_block_ok(DistWhat what, unsigned block) { return dist_map_block_ok(block) || (what == DistWhat::Moments && block == 8); }
+static inline size_t dist_map_words(unsigned w, unsigned h, unsigned block, int per_block = 12)
+{
+    return (size_t)((w + block - 1) / block) * ((h + block - 1) / block) * per_block;
+}
+// out: the launch's words (non-null, 8-byte aligned, sharing no byte with the frames or the given planes -- judged by the byte
+// count of what the launch writes); the workgroup of the two maps is clamped to a power of two of at most 64 * map_block / 2
+// threads (a map tile is a whole number of standard tiles).  Every error is raised here, the block size first, before anything of
+// the launch is queued.
+int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, DistWhat what, unsigned map_block,
                     hipStream_t stream, DistortionPlan &p);
 
 // ---- lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip: pick_dist<DistMapFamily, false / true> of lumahip_pick.hpp (every
@@ -570,8 +583,6 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
 int distortion_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *map_dev, const DistortionLaunch &o);
 typedef void (*dist_map_kernel_t)(const lh::DistMapArgs);
 dist_map_kernel_t pick_dist_map_f16(int cs, bool sub, int vw, int mode);
-static inline bool dist_map_block_ok(unsigned block) { return block == 16 || block == 32 || block == 64; }
-static inline size_t dist_map_words(unsigned w, unsigned h, unsigned block) { return (size_t)((w + block - 1) / block) * ((h + block - 1) / block) * 12; }
 // what the map kernels' helpers read beside g, the launch's frame-major geometry; threads = its workgroup, a power of two of at most 32 * block
 static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsigned h, unsigned block, int threads)
 {
@@ -584,6 +595,13 @@ static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsi
     m.totalMapTiles = m.mapTilesPerFrame * g.nframes;   // (<= the standard tiles, which make_geom has bounded)
     return m;
 }
+
+// ---- lumahip_moments_map.hip / lumahip_moments_map_f16.hip: pick_dist<MomentsMapFamily, false / true> of lumahip_pick.hpp (every
+// k_moments_map; the binary16-frame ones are exported as pick_moments_map_f16)
+// the five moment sums per plane and block x block luma pixels: nframes * nby * nbx * 15 words at mom_dev, every one written by the launch
+int moments_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *mom_dev, const DistortionLaunch &o);
+typedef void (*moments_map_kernel_t)(const lh::MomentsMapArgs);
+moments_map_kernel_t pick_moments_map_f16(int cs, bool sub, int vw, int mode);
 
 // ---- lumahip_transcode_distortion.hip: pick_planes<TransDistFamily, .> of lumahip_pick.hpp (every k_transcode_distortion)
 // the source planes' transcode (transcode_impl's planes, never written) against the given planes: 12 words per frame at out_dev

@@ -1,5 +1,5 @@
 // lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / k_decode / k_transcode / k_distortion /
-// k_distortion_map / k_transcode_distortion / k_transcode_distortion_map, luma_kernels.hpp) a launch takes.
+// k_distortion_map / k_moments_map / k_transcode_distortion / k_transcode_distortion_map, luma_kernels.hpp) a launch takes.
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
@@ -7,7 +7,8 @@
 // lumahip_transcode_distortion.hip takes pick_planes<TransDistFamily, 4 | 2>; lumahip_transcode_distortion_map.hip takes
 // pick_planes<TransDistMapFamily, 4 | 2>; lumahip_distortion.hip /
 // lumahip_distortion_f16.hip take pick_dist<DistFamily, false / true>; lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip
-// take pick_dist<DistMapFamily, false / true>.  Included by those eleven units only.
+// take pick_dist<DistMapFamily, false / true>; lumahip_moments_map.hip / lumahip_moments_map_f16.hip take
+// pick_dist<MomentsMapFamily, false / true>.  Included by those thirteen units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -151,8 +152,8 @@ static typename F::kernel_t pick_planes(int csd, bool subd, int cse, bool sube, 
 }
 
 // The frame-fed measuring kernels: lh::k_distortion (DistFamily, named by lumahip_distortion.hip / lumahip_distortion_f16.hip only) and
-// lh::k_distortion_map (DistMapFamily, named by lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip only), the same keys kernel
-// for kernel.
+// lh::k_distortion_map (DistMapFamily, named by lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip only) and lh::k_moments_map
+// (MomentsMapFamily, named by lumahip_moments_map.hip / lumahip_moments_map_f16.hip only), the same keys kernel for kernel.
 struct DistFamily {
     using kernel_t = dist_kernel_t;
     template <int CS, bool SUB, int VW, int LM, bool IN16>
@@ -162,6 +163,11 @@ struct DistMapFamily {
     using kernel_t = dist_map_kernel_t;
     template <int CS, bool SUB, int VW, int LM, bool IN16>
     static kernel_t kernel() { return lh::k_distortion_map<CS, SUB, VW, LM, IN16>; }
+};
+struct MomentsMapFamily {   // (launch bound: lh::moments_threads_bound, which distortion_plan clamps the launch to)
+    using kernel_t = moments_map_kernel_t;
+    template <int CS, bool SUB, int VW, int LM, bool IN16>
+    static kernel_t kernel() { return lh::k_moments_map<CS, SUB, VW, LM, IN16>; }
 };
 
 // Search records in LDS only.  mode: LUT_THRESH_LDS or LUT_LINKEY_LDS, or for YCbCr 5 = the composite records (float frames),
