@@ -8,6 +8,8 @@ host.py    numpy alone (no torch, no library): the plane geometry, the numpy mod
 device.py  the `L` fixture (test modules import it by name), dev, ctx, table_for, pair; Frames and Planes in device buffers, from_frames,
            random_planes, the out-word and map buffers; one wrapper per device call (encode, dist, dist_map, fused, two_calls,
            transcoded, measure, tmap).  torch is imported inside the functions.
+display.py numpy alone: the display transform in float64 kept before its floor (display_t), what an RGBA image must satisfy against
+           it (check_rgba, with the derivation of its EPS), the conditions on a reference image and frames that meet them.
 exr.py     an OpenEXR scan-line writer and reader in numpy + zlib.
 tools.py   ROOT, and what runs as a process of its own: bench.py, the facade's round-trip program.
 

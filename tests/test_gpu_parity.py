@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from tests.golden.make_golden import CONFIGS, extreme_frame, special_frame  # noqa: E402
 from tests.support.device import L, pair  # noqa: E402,F401  (L is the module fixture)
+from tests.support.display import check_rgba, display_bytes, display_t  # noqa: E402
 from tests.support.host import same_bits  # noqa: E402
 
 
@@ -231,6 +232,10 @@ def test_decode_display_transform(L, oracle_mod, do_tmo, ldr_sim, exposure, gamm
     assert np.all(exp[..., 3] == 255)
     assert np.max(np.abs(got[..., :3] - exp[..., :3])) <= 1
     assert np.mean(got[..., :3] == exp[..., :3]) > 0.98
+    # ... and a code differs only next to a rounding boundary, towards it (tests/support/display.py)
+    t = display_t(dec, exposure, gamma, do_tmo, ldr_sim)
+    assert np.array_equal(display_bytes(t), exp)
+    check_rgba(rgba.cpu().numpy().reshape(h, w, 4), t, (do_tmo, ldr_sim, exposure, gamma))
 
 
 def test_python_host_mirror_of_the_reference_interface(L, oracle_mod):
