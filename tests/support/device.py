@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.support.host import (GAP, GUARD, OUT_FILL, blank_planes, frames_buffer, gaps_intact, layout, map_words, nwords,
+from tests.support.host import (GAP, GUARD, OUT_FILL, SENTINEL, blank_planes, frames_buffer, gaps_intact, layout, map_words, nwords,
                                 planes_from_frames, random_frames, same_bits)
 from tests.support.tools import ROOT
 
@@ -54,22 +54,52 @@ def pair(L, o, cfg):
 
 
 class Frames:
-    """frames on the device, frame f at base + f * fs elements; the gap between frames holds sentinel bytes"""
+    """frames on the device, frame f at base + f * fs elements; the gap between frames holds sentinel bytes, and so do the `base`
+    elements in front of the first frame (base 2 puts float frames 8 bytes off a 16-byte boundary)"""
 
-    def __init__(self, frames, dtype=np.float32, pad=4):
+    def __init__(self, frames, dtype=np.float32, pad=4, base=0):
         import torch
         nf, _, h, w = frames.shape
         self.nf, self.w, self.h, self.n = nf, w, h, w * h
         self.fs = 3 * self.n + pad
         self.host = frames_buffer(frames, dtype, pad)
-        self.t = torch.from_numpy(self.host.view(np.uint8).ravel().copy()).to(dev())
+        self.front = base * np.dtype(dtype).itemsize
+        self.bytes = np.concatenate([np.full(self.front, SENTINEL, dtype=np.uint8), self.host.view(np.uint8).ravel()])
+        self.t = torch.from_numpy(self.bytes.copy()).to(dev())
 
     @property
     def ptr(self):
-        return self.t.data_ptr()
+        return self.t.data_ptr() + self.front
 
     def unchanged(self):
-        return np.array_equal(self.t.cpu().numpy(), self.host.view(np.uint8).ravel())
+        return np.array_equal(self.t.cpu().numpy(), self.bytes)
+
+
+class FloatOut:
+    """the buffer a decode call writes nf frames of floats (or halves) into: frame f at base + f * fs elements, fs = 3 w h + pad; the
+    sentinel everywhere before the call"""
+
+    def __init__(self, nf, w, h, dtype=np.float32, pad=4, base=0):
+        import torch
+        self.nf, self.w, self.h, self.n3, self.dtype = nf, w, h, 3 * w * h, np.dtype(dtype)
+        self.fs = self.n3 + pad
+        self.front = base * self.dtype.itemsize
+        self.t = torch.full((self.front + nf * self.fs * self.dtype.itemsize,), SENTINEL, dtype=torch.uint8, device=dev())
+
+    @property
+    def ptr(self):
+        return self.t.data_ptr() + self.front
+
+    def frames(self):
+        """(nf, 3, h, w) of dtype, after checking the bytes in front of the first frame and behind every frame"""
+        a = self.t.cpu().numpy()
+        assert np.all(a[:self.front] == SENTINEL), "bytes in front of the first frame"
+        fr = a[self.front:].reshape(self.nf, self.fs * self.dtype.itemsize)
+        assert np.all(fr[:, self.n3 * self.dtype.itemsize:] == SENTINEL), "bytes behind a frame"
+        return np.ascontiguousarray(fr[:, :self.n3 * self.dtype.itemsize]).view(self.dtype).reshape(self.nf, 3, self.h, self.w)
+
+    def untouched(self):
+        return bool((self.t == SENTINEL).all())
 
 
 def _strides(L, w, h, profile, strides):
@@ -78,35 +108,37 @@ def _strides(L, w, h, profile, strides):
 
 
 class Planes:
-    """nf frames of code planes on the device: plane p of frame f at buf[p] + f * pfs[p], rows st[p] bytes apart; `fill` is what the
-    buffers were given (the sentinel everywhere by default)"""
+    """nf frames of code planes on the device: plane p of frame f at buf[p] + base + f * pfs[p], rows st[p] bytes apart; `fill` is what
+    the buffers were given (the sentinel everywhere by default).  `base` bytes of sentinel lie in front of every plane (torch's
+    buffers are aligned far beyond 16 bytes, so base is the planes' misalignment); `gap`: one number or one per plane"""
 
-    def __init__(self, L, w, h, profile, nf, fill=None, strides=None, gap=GAP):
+    def __init__(self, L, w, h, profile, nf, fill=None, strides=None, gap=GAP, base=0):
         import torch
-        self.w, self.h, self.profile, self.nf, self.gap = w, h, profile, nf, gap
+        self.w, self.h, self.profile, self.nf, self.gap, self.base = w, h, profile, nf, gap, base
         self.st = _strides(L, w, h, profile, strides)
         self.hs, self.size, self.pfs = layout(w, h, profile, self.st, gap)
         if fill is None:
-            fill = blank_planes(w, h, profile, nf, self.st, gap)
+            fill = blank_planes(w, h, profile, nf, self.st, gap, base)
         self.fill = [np.ascontiguousarray(f) for f in fill]
         self.t = [torch.from_numpy(self.fill[p]).to(dev()) for p in range(3)]
 
     @property
     def ptrs(self):
-        return [t.data_ptr() for t in self.t]
+        return [t.data_ptr() + self.base for t in self.t]
 
     def host(self):
         return [t.cpu().numpy() for t in self.t]
 
     def frame(self, bufs, f):
         """frame f as three (rows, stride) arrays"""
-        return [bufs[p][f * self.pfs[p]: f * self.pfs[p] + self.size[p]].reshape(self.hs[p], self.st[p]) for p in range(3)]
+        return [bufs[p][self.base + f * self.pfs[p]: self.base + f * self.pfs[p] + self.size[p]].reshape(self.hs[p], self.st[p])
+                for p in range(3)]
 
     def unchanged(self):
         return all(np.array_equal(a, b) for a, b in zip(self.host(), self.fill))
 
     def gaps_intact(self, bufs):
-        return gaps_intact(bufs, self.w, self.h, self.profile, self.nf, self.st, self.gap)
+        return gaps_intact(bufs, self.w, self.h, self.profile, self.nf, self.st, self.gap, self.base)
 
 
 def from_frames(L, frames, w, h, profile, strides=None, *, padding):

@@ -32,6 +32,17 @@ def same_bits(a, b):
     return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
 
 
+def widen_halves(frames16):
+    """binary16 -> float32 as IEEE conversion (and the kernels' v_cvt_f32_f16) widens: a signalling NaN comes out quiet.
+    numpy's astype keeps it signalling, and a signalling NaN in the float kernels' min / max (v_min_f32 / v_max_f32 return
+    NaN for one) would drop the values the wave had seen before it -- the float call would then be fed other data than the
+    kernels of the f16 call read"""
+    w = np.asarray(frames16).astype(np.float32)
+    b = w.view(np.uint32)
+    b[np.isnan(w)] |= np.uint32(0x00400000)
+    return w
+
+
 def float_to_half_np(x) -> np.ndarray:
     """ExrInterface::floatToHalf (lumahdrv_amd/csrc/facade/exr_interface.cpp) over a float32 array -> uint16 bit patterns"""
     b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.int64)
@@ -100,11 +111,17 @@ def plane_rows(w, h, profile, p):
     return ((h + 1) // 2 if (p and sub) else h), ((w + 1) // 2 if (p and sub) else w) * bps
 
 
+def per_plane(v):
+    """a value per plane from one value or from three"""
+    return tuple(v) if isinstance(v, (tuple, list)) else (v,) * 3
+
+
 def layout(w, h, profile, st, gap=GAP):
-    """(rows, bytes, frame stride) per plane, for rows st[p] bytes apart and `gap` bytes behind every frame's plane"""
+    """(rows, bytes, frame stride) per plane, for rows st[p] bytes apart and `gap` bytes (one number, or one per plane) behind every
+    frame's plane"""
     hs = [plane_rows(w, h, profile, p)[0] for p in range(3)]
     size = [hs[p] * st[p] for p in range(3)]
-    return hs, size, [size[p] + gap for p in range(3)]
+    return hs, size, [size[p] + per_plane(gap)[p] for p in range(3)]
 
 
 def same_rows(a, b, w, h, profile):
@@ -283,7 +300,8 @@ def float_frames(rng, nf, w, h, halves=False):
 
 
 def frames_buffer(frames, dtype=np.float32, pad=4):
-    """(nf, 3 * w * h + pad) of dtype: frame f in row f, sentinel bytes in the pad behind it"""
+    """(nf, 3 * w * h + pad) of dtype: frame f in row f, sentinel bytes in the pad behind it (frames of another float type are
+    converted; frames of dtype are taken bit for bit)"""
     nf, _, h, w = frames.shape
     fs = 3 * w * h + pad
     buf = np.full(nf * fs * np.dtype(dtype).itemsize, SENTINEL, dtype=np.uint8).view(dtype).reshape(nf, fs)
@@ -291,24 +309,24 @@ def frames_buffer(frames, dtype=np.float32, pad=4):
     return buf
 
 
-def blank_planes(w, h, profile, nf, st, gap=GAP):
-    """three byte buffers of nf frames' planes, the sentinel everywhere"""
+def blank_planes(w, h, profile, nf, st, gap=GAP, base=0):
+    """three byte buffers of nf frames' planes behind `base` bytes, the sentinel everywhere"""
     pfs = layout(w, h, profile, st, gap)[2]
-    return [np.full(nf * pfs[p], SENTINEL, dtype=np.uint8) for p in range(3)]
+    return [np.full(base + nf * pfs[p], SENTINEL, dtype=np.uint8) for p in range(3)]
 
 
-def planes_from_frames(frames, w, h, profile, st, padding, gap=GAP):
+def planes_from_frames(frames, w, h, profile, st, padding, gap=GAP, base=0):
     """three byte buffers holding the given frames (lists of three (rows, >= row bytes) arrays) in rows st[p] bytes apart, the sentinel
-    in every gap.  Behind each row's samples: the sentinel (padding="sentinel"), or the source rows' own bytes up to st[p]
+    in every gap and in the `base` bytes in front of the first frame.  Behind each row's samples: the sentinel (padding="sentinel"), or the source rows' own bytes up to st[p]
     (padding="source"; the source rows are then at least st[p] bytes long)"""
     if padding not in ("sentinel", "source"):
         raise ValueError("padding: 'sentinel' or 'source', not %r" % (padding,))
     hs, size, pfs = layout(w, h, profile, st, gap)
-    fill = blank_planes(w, h, profile, len(frames), st, gap)
+    fill = blank_planes(w, h, profile, len(frames), st, gap, base)
     for f, fr in enumerate(frames):
         for p in range(3):
             n = plane_rows(w, h, profile, p)[1] if padding == "sentinel" else st[p]
-            dst = fill[p][f * pfs[p]: f * pfs[p] + size[p]].reshape(hs[p], st[p])
+            dst = fill[p][base + f * pfs[p]: base + f * pfs[p] + size[p]].reshape(hs[p], st[p])
             dst[:, :n] = np.asarray(fr[p])[:hs[p], :n]
     return fill
 
@@ -327,12 +345,14 @@ def random_frames(rng, w, h, profile, nf, st):
     return frames
 
 
-def gaps_intact(bufs, w, h, profile, nf, st, gap=GAP):
-    """the sentinel in every gap behind a frame's plane and behind every row's samples"""
+def gaps_intact(bufs, w, h, profile, nf, st, gap=GAP, base=0):
+    """the sentinel in every gap behind a frame's plane (the last frame's too), behind every row's samples and in the `base` bytes in
+    front of the first frame"""
     hs, size, pfs = layout(w, h, profile, st, gap)
     ok = True
     for p in range(3):
-        b = bufs[p].reshape(nf, pfs[p])
+        ok = ok and bool(np.all(bufs[p][:base] == SENTINEL))
+        b = bufs[p][base:].reshape(nf, pfs[p])
         ok = ok and bool(np.all(b[:, size[p]:] == SENTINEL))
         rb = plane_rows(w, h, profile, p)[1]
         ok = ok and bool(np.all(b[:, :size[p]].reshape(nf, hs[p], st[p])[:, :, rb:] == SENTINEL))

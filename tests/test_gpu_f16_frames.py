@@ -17,7 +17,7 @@ import pytest
 
 from tests.golden.make_golden import CONFIGS
 from tests.support.device import L, ctx, dev  # noqa: F401  (L is the module fixture)
-from tests.support.host import float_to_half_np
+from tests.support.host import float_to_half_np, widen_halves as _widen
 
 pytestmark = pytest.mark.gpu
 
@@ -134,17 +134,6 @@ def _half_frames(rng, nf, w, h):
     for c in range(3):
         flat[:, c, :k] = np.roll(sp, c)[:k]
     return f
-
-
-def _widen(frames16):
-    """binary16 -> float32 as IEEE conversion (and the kernels' v_cvt_f32_f16) widens: a signalling NaN comes out quiet.
-    numpy's astype keeps it signalling, and a signalling NaN in the float kernels' min / max (v_min_f32 / v_max_f32 return
-    NaN for one) would drop the values the wave had seen before it -- the float call would then be fed other data than the
-    kernels of the f16 call read"""
-    w = np.asarray(frames16).astype(np.float32)
-    b = w.view(np.uint32)
-    b[np.isnan(w)] |= np.uint32(0x00400000)
-    return w
 
 
 def _same_stats(a, b):
