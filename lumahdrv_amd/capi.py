@@ -18,39 +18,164 @@ CS_LUV, CS_RGB, CS_YCBCR, CS_XYZ = range(4)
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = range(5)
 
-SYMBOLS = [
-    "lumahip_abi_version", "lumahip_device_count", "lumahip_create", "lumahip_destroy", "lumahip_last_error",
-    "lumahip_set_stream", "lumahip_reset_stream", "lumahip_sync", "lumahip_tune", "lumahip_set_quantizer", "lumahip_build_lut", "lumahip_thresh_index_host", "lumahip_lin_index_host", "lumahip_ycbcr_luma_index_host", "lumahip_ycbcr_ytab_host", "lumahip_ycbcr_half_table_host", "lumahip_half_table_info", "lumahip_rb_table_info", "lumahip_quantize_value_host", "lumahip_dequantize_value_host", "lumahip_half_upload_info", "lumahip_numa_info", "lumahip_numa_pin_current_thread", "lumahip_numa_plan_host", "lumahip_quantizer_info",
-    "lumahip_encode_stream_push", "lumahip_encode_stream_pop", "lumahip_encode_stream_pending",
-    "lumahip_decode_stream_push", "lumahip_decode_stream_pop", "lumahip_decode_stream_pending",
-    "lumahip_encode_frame_host", "lumahip_decode_frame_host", "lumahip_encode_frames_host", "lumahip_decode_frames_host", "lumahip_pack_frame_host", "lumahip_unpack_frame_host", "lumahip_transform_color_space_host",
-    "lumahip_quantize_array_host", "lumahip_dequantize_array_host", "lumahip_quantize_array_device", "lumahip_dequantize_array_device",
-    "lumahip_encode_frames_device", "lumahip_mean_luminance_reference_device",
-    "lumahip_decode_frames_device", "lumahip_decode_frames_device_rotating", "lumahip_decode_display_frames_device", "lumahip_transform_color_space_device", "lumahip_synth_frames_device",
-    "lumahip_device", "lumahip_encode_frames_device_planar", "lumahip_decode_frames_device_planar", "lumahip_begin_unordered", "lumahip_end_unordered",
-    "lumahip_probe_decode_traffic_device",
-    "lumahip_decoded_ring_create", "lumahip_decoded_ring_destroy", "lumahip_decoded_ring_info", "lumahip_decoded_ring_frame", "lumahip_decode_frames_device_ring",
-    "lumahip_pool_create", "lumahip_pool_create_small", "lumahip_pool_destroy", "lumahip_pool_alloc", "lumahip_pool_release", "lumahip_pool_available", "lumahip_pool_group_of",
-    "lumahip_pool_stats_json", "lumahip_pool_find_groups",
-    "lumahip_multi_create", "lumahip_multi_destroy", "lumahip_multi_shards", "lumahip_multi_ctx", "lumahip_multi_last_error", "lumahip_multi_used_rccl", "lumahip_multi_set_transport", "lumahip_multi_transport_note",
-    "lumahip_shard_range", "lumahip_multi_set_quantizer", "lumahip_multi_encode_frames_host", "lumahip_multi_decode_frames_host",
-    "lumahip_multi_encode_frames_device", "lumahip_multi_decode_frames_device", "lumahip_multi_sync",
-    "lumahip_encode_frames_device_f16", "lumahip_encode_frames_device_planar_f16", "lumahip_decode_frames_device_f16",
-    "lumahip_decode_frames_device_planar_f16", "lumahip_encode_frame_host_f16", "lumahip_decode_frame_host_f16", "lumahip_f16_narrow_probe_device",
-    "lumahip_set_source_quantizer", "lumahip_transcode_frames_device", "lumahip_transcode_frame_host",
-    "lumahip_distortion_frames_device", "lumahip_distortion_frames_device_planar", "lumahip_distortion_frames_device_f16",
-    "lumahip_distortion_frames_device_planar_f16", "lumahip_distortion_frame_host",
-    "lumahip_transcode_distortion_frames_device", "lumahip_transcode_distortion_frame_host",
-    "lumahip_distortion_map_dims", "lumahip_distortion_map_frames_device", "lumahip_distortion_map_frames_device_planar",
-    "lumahip_distortion_map_frames_device_f16", "lumahip_distortion_map_frames_device_planar_f16", "lumahip_distortion_map_frame_host",
-    "lumahip_transcode_distortion_map_frames_device", "lumahip_transcode_distortion_map_frame_host",
-    "lumahip_moments_map_dims", "lumahip_moments_map_frames_device", "lumahip_moments_map_frames_device_planar",
-    "lumahip_moments_map_frames_device_f16", "lumahip_moments_map_frames_device_planar_f16", "lumahip_moments_map_frame_host",
-    "lumahip_time_launches", "lumahip_probe_encode_traffic_device", "lumahip_powf_probe_device", "lumahip_quantize_probe_device", "lumahip_ycbcr_luma_probe_device", "lumahip_host_register", "lumahip_host_unregister", "lumahip_malloc", "lumahip_free", "lumahip_memcpy_h2d", "lumahip_memcpy_d2h",
-]
-
-
 PROBE_FN = C.CFUNCTYPE(C.c_double, C.c_int, C.c_int, C.c_void_p)
+
+
+class PoolConfig(C.Structure):
+    """lumahip_pool_config (include/lumahip.h)"""
+    _fields_ = [("chunk_bytes", C.c_size_t), ("n_float", C.c_int), ("n_y", C.c_int), ("n_uv", C.c_int), ("n_striped", C.c_int),
+                ("keep_free_bytes", C.c_size_t), ("max_chunks", C.c_int), ("probe_iters", C.c_int)]
+
+
+_vp, _u, _i, _f, _sz, _str = C.c_void_p, C.c_uint, C.c_int, C.c_float, C.c_size_t, C.c_char_p
+_p3, _i3, _s3 = C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_size_t)       # T name[3] and other T * parameters
+_fp, _up, _dp, _lp = C.POINTER(C.c_float), C.POINTER(C.c_uint), C.POINTER(C.c_double), C.POINTER(C.c_long)
+# the parameter runs that many entry points share, ctx first
+_QUANTIZER = (_vp, _i, _u, _i, _u, _f, _f, _vp, _sz)                        # ptf, bitdepth, cs, bitdepthC, max_lum, min_lum, lut, n
+_FRAMES = (_vp, _vp, _sz, _u, _u, _u, _f, _i, _p3, _i3, _s3)                # frames, frame_stride, nframes, w, h, sc, profile, plane triplets
+_PLANAR = (_vp, _p3) + _FRAMES[2:]                                          # the same with three colour-plane pointers
+_PLANES = (_vp, _p3, _i3, _s3, _u, _u, _u, _i, _f)                          # plane triplets, nframes, w, h, profile, sc
+_TWO_SETS = (_vp, _p3, _i3, _s3, _i, _f, _u, _u, _u, _p3, _i3, _s3, _i, _f)  # source triplets, profile, sc, nframes, w, h, target ...
+_FRAME_HOST = (_vp, _vp, _u, _u, _f, _i, _p3, _i3)                          # rgb, w, h, sc, profile, planes, strides
+_PLANES_HOST = (_vp, _p3, _i3, _u, _u, _i, _f)                              # planes, strides, w, h, profile, sc
+_TWO_SETS_HOST = (_vp, _p3, _i3, _i, _f, _u, _u, _p3, _i3, _i, _f)
+_FRAMES_HOST = (_vp, _p3, _u, _u, _u, _f, _i, _p3, _i3, _fp)                # frames[n], n, w, h, sc, profile, planes[3n], strides, means
+_PLANES_FRAMES_HOST = (_vp, _p3, _i3, _u, _u, _u, _i, _f, _p3)
+_ARRAY = (_vp, _vp, _vp, _sz, _u)                                           # in, out, n, channel
+_MAP_DIMS = (_u, _u, _u, _up, _up)
+_PROBE = (_vp, _vp, C.c_uint32, _sz)                                        # out, first_bits, n
+
+# include/lumahip.h, one entry per declaration: name -> (restype, argtypes).  The only place a signature is written: lib() applies it,
+# SYMBOLS lists it, tests/test_capi_abi_host.py holds it against the header.
+_ABI = {
+    "lumahip_abi_version": (_i, ()),
+    "lumahip_device_count": (_i, (_i3,)),
+    "lumahip_create": (_i, (_p3, _i)),
+    "lumahip_destroy": (None, (_vp,)),
+    "lumahip_last_error": (_str, (_vp,)),
+    "lumahip_set_stream": (_i, (_vp, _vp)),
+    "lumahip_reset_stream": (_i, (_vp,)),
+    "lumahip_sync": (_i, (_vp,)),
+    "lumahip_tune": (_i, (_vp, _str, C.c_long)),
+    "lumahip_set_quantizer": (_i, _QUANTIZER),
+    "lumahip_build_lut": (_i, (_i, _u, _f, _f, _vp, _sz)),
+    "lumahip_thresh_index_host": (_i, (_vp, _sz, _i3, _vp, _sz)),
+    "lumahip_lin_index_host": (_i, (_vp, _sz, _i3, _vp, _sz)),
+    "lumahip_ycbcr_luma_index_host": (_i, (_vp, _sz, _f, _i3, _vp, _sz)),
+    "lumahip_ycbcr_ytab_host": (_i, (_vp, _sz, _f, _vp)),
+    "lumahip_ycbcr_half_table_host": (_i, (_f, _f, _vp, _sz)),
+    "lumahip_half_table_info": (_i, (_vp, _f, _i3)),
+    "lumahip_rb_table_info": (_i, (_vp, _f, _i3)),
+    "lumahip_quantize_value_host": (_i, (_vp, _sz, _i, _u, _f, _u, _fp)),
+    "lumahip_dequantize_value_host": (_i, (_vp, _sz, _i, _u, _f, _u, _fp)),
+    "lumahip_half_upload_info": (_i, (_vp, _lp)),
+    "lumahip_numa_info": (_i, (_vp, _i3)),
+    "lumahip_numa_pin_current_thread": (_i, (_vp,)),
+    "lumahip_numa_plan_host": (_i, (_str, _str, _str, _i3, _i3, _i, _i3)),
+    "lumahip_quantizer_info": (_i, (_vp, _i3)),
+    "lumahip_encode_stream_push": (_i, _FRAME_HOST),
+    "lumahip_encode_stream_pop": (_i, (_vp, _fp)),
+    "lumahip_encode_stream_pending": (_i, (_vp,)),
+    "lumahip_decode_stream_push": (_i, _PLANES_HOST + (_vp,)),
+    "lumahip_decode_stream_pop": (_i, (_vp,)),
+    "lumahip_decode_stream_pending": (_i, (_vp,)),
+    "lumahip_encode_frame_host": (_i, _FRAME_HOST + (_fp, _vp)),
+    "lumahip_decode_frame_host": (_i, _PLANES_HOST + (_vp,)),
+    "lumahip_encode_frames_host": (_i, _FRAMES_HOST),
+    "lumahip_decode_frames_host": (_i, _PLANES_FRAMES_HOST),
+    "lumahip_pack_frame_host": (_i, (_vp, _vp, _u, _u, _i, _p3, _i3, _fp)),
+    "lumahip_unpack_frame_host": (_i, (_vp, _p3, _i3, _u, _u, _i, _vp)),
+    "lumahip_transform_color_space_host": (_i, (_vp, _vp, _u, _u, _i, _f)),
+    "lumahip_quantize_array_host": (_i, _ARRAY),
+    "lumahip_dequantize_array_host": (_i, _ARRAY),
+    "lumahip_quantize_array_device": (_i, _ARRAY),
+    "lumahip_dequantize_array_device": (_i, _ARRAY),
+    "lumahip_encode_frames_device": (_i, _FRAMES + (_vp,)),
+    "lumahip_mean_luminance_reference_device": (_i, (_vp, _vp, _u, _u, _f, _fp)),
+    "lumahip_decode_frames_device": (_i, _PLANES + (_vp, _sz)),
+    "lumahip_decode_frames_device_rotating": (_i, _PLANES + (_p3, _sz)),
+    "lumahip_decode_display_frames_device": (_i, _PLANES + (_vp, _sz, _vp, _i, _sz, _f, _f, _i, _i)),
+    "lumahip_transform_color_space_device": (_i, (_vp, _vp, _sz, _u, _u, _u, _i, _f)),
+    "lumahip_synth_frames_device": (_i, (_vp, _vp, _sz, _u, _u, _u, C.c_uint64, C.c_uint64)),
+    "lumahip_device": (_i, (_vp,)),
+    "lumahip_encode_frames_device_planar": (_i, _PLANAR + (_vp,)),
+    "lumahip_decode_frames_device_planar": (_i, _PLANES + (_p3, _sz)),
+    "lumahip_begin_unordered": (_i, (_vp, _i)),
+    "lumahip_end_unordered": (_i, (_vp,)),
+    "lumahip_probe_decode_traffic_device": (_i, _PLANES[:7] + (_p3, _sz, _i, _fp)),
+    "lumahip_decoded_ring_create": (_i, (_vp, _u, _u, _u, _u, _p3)),
+    "lumahip_decoded_ring_destroy": (None, (_vp,)),
+    "lumahip_decoded_ring_info": (_i, (_vp, _i3, _s3)),
+    "lumahip_decoded_ring_frame": (_vp, (_vp, _u, _u)),
+    "lumahip_decode_frames_device_ring": (_i, (_vp, _p3, _i3, _s3, _u, _i, _f, _vp, _u)),
+    "lumahip_pool_create": (_i, (_vp, C.POINTER(PoolConfig), _p3)),
+    "lumahip_pool_create_small": (_i, (_vp, _i, _i, _i, _i, _p3)),
+    "lumahip_pool_destroy": (None, (_vp,)),
+    "lumahip_pool_alloc": (_i, (_vp, _i, _i, _p3)),
+    "lumahip_pool_release": (_i, (_vp, _vp)),
+    "lumahip_pool_available": (_i, (_vp, _i, _i)),
+    "lumahip_pool_group_of": (_i, (_vp, _vp)),
+    "lumahip_pool_stats_json": (_str, (_vp,)),
+    "lumahip_pool_find_groups": (_i, (_i, PROBE_FN, _vp, _vp, _i3, _dp, _i3)),
+    "lumahip_multi_create": (_i, (_p3, _i3, _i)),
+    "lumahip_multi_destroy": (None, (_vp,)),
+    "lumahip_multi_shards": (_i, (_vp,)),
+    "lumahip_multi_ctx": (_vp, (_vp, _i)),
+    "lumahip_multi_last_error": (_str, (_vp,)),
+    "lumahip_multi_used_rccl": (_i, (_vp,)),
+    "lumahip_multi_set_transport": (_i, (_vp, _i)),
+    "lumahip_multi_transport_note": (_str, (_vp,)),
+    "lumahip_shard_range": (_i, (_u, _i, _i, _up, _up)),
+    "lumahip_multi_set_quantizer": (_i, _QUANTIZER),
+    "lumahip_multi_encode_frames_host": (_i, _FRAMES_HOST),
+    "lumahip_multi_decode_frames_host": (_i, _PLANES_FRAMES_HOST),
+    "lumahip_multi_encode_frames_device": (_i, (_vp, _p3, _sz, _up, _u, _u, _f, _i, _p3, _i3, _s3)),
+    "lumahip_multi_decode_frames_device": (_i, (_vp, _p3, _i3, _s3, _up, _u, _u, _i, _f, _p3, _sz)),
+    "lumahip_multi_sync": (_i, (_vp,)),
+    "lumahip_encode_frames_device_f16": (_i, _FRAMES + (_vp,)),
+    "lumahip_encode_frames_device_planar_f16": (_i, _PLANAR + (_vp,)),
+    "lumahip_decode_frames_device_f16": (_i, _PLANES + (_vp, _sz)),
+    "lumahip_decode_frames_device_planar_f16": (_i, _PLANES + (_p3, _sz)),
+    "lumahip_encode_frame_host_f16": (_i, _FRAME_HOST + (_fp,)),
+    "lumahip_decode_frame_host_f16": (_i, _PLANES_HOST + (_vp,)),
+    "lumahip_f16_narrow_probe_device": (_i, _PROBE),
+    "lumahip_set_source_quantizer": (_i, _QUANTIZER),
+    "lumahip_transcode_frames_device": (_i, _TWO_SETS + (_vp,)),
+    "lumahip_transcode_frame_host": (_i, _TWO_SETS_HOST + (_fp,)),
+    "lumahip_distortion_frames_device": (_i, _FRAMES + (_vp,)),
+    "lumahip_distortion_frames_device_planar": (_i, _PLANAR + (_vp,)),
+    "lumahip_distortion_frames_device_f16": (_i, _FRAMES + (_vp,)),
+    "lumahip_distortion_frames_device_planar_f16": (_i, _PLANAR + (_vp,)),
+    "lumahip_distortion_frame_host": (_i, _FRAME_HOST + (_vp,)),
+    "lumahip_transcode_distortion_frames_device": (_i, _TWO_SETS + (_vp,)),
+    "lumahip_transcode_distortion_frame_host": (_i, _TWO_SETS_HOST + (_vp,)),
+    "lumahip_distortion_map_dims": (_i, _MAP_DIMS),
+    "lumahip_distortion_map_frames_device": (_i, _FRAMES + (_u, _vp)),
+    "lumahip_distortion_map_frames_device_planar": (_i, _PLANAR + (_u, _vp)),
+    "lumahip_distortion_map_frames_device_f16": (_i, _FRAMES + (_u, _vp)),
+    "lumahip_distortion_map_frames_device_planar_f16": (_i, _PLANAR + (_u, _vp)),
+    "lumahip_distortion_map_frame_host": (_i, _FRAME_HOST + (_u, _vp, _sz)),
+    "lumahip_transcode_distortion_map_frames_device": (_i, _TWO_SETS + (_u, _vp)),
+    "lumahip_transcode_distortion_map_frame_host": (_i, _TWO_SETS_HOST + (_u, _vp, _sz)),
+    "lumahip_moments_map_dims": (_i, _MAP_DIMS),
+    "lumahip_moments_map_frames_device": (_i, _FRAMES + (_u, _vp)),
+    "lumahip_moments_map_frames_device_planar": (_i, _PLANAR + (_u, _vp)),
+    "lumahip_moments_map_frames_device_f16": (_i, _FRAMES + (_u, _vp)),
+    "lumahip_moments_map_frames_device_planar_f16": (_i, _PLANAR + (_u, _vp)),
+    "lumahip_moments_map_frame_host": (_i, _FRAME_HOST + (_u, _vp, _sz)),
+    "lumahip_time_launches": (_i, (_vp, _i, _i) + _FRAMES[1:] + (_fp,)),
+    "lumahip_probe_encode_traffic_device": (_i, _FRAMES[:6] + (_p3, _i3, _s3, _i, _fp)),
+    "lumahip_powf_probe_device": (_i, _PROBE + (_f, _i)),
+    "lumahip_quantize_probe_device": (_i, _PROBE + (_i,)),
+    "lumahip_ycbcr_luma_probe_device": (_i, _PROBE + (_i,)),
+    "lumahip_host_register": (_i, (_vp, _vp, _sz)),
+    "lumahip_host_unregister": (_i, (_vp, _vp)),
+    "lumahip_malloc": (_i, (_vp, _p3, _sz)),
+    "lumahip_free": (_i, (_vp, _vp)),
+    "lumahip_memcpy_h2d": (_i, (_vp, _vp, _vp, _sz)),
+    "lumahip_memcpy_d2h": (_i, (_vp, _vp, _vp, _sz)),
+}
+SYMBOLS = tuple(_ABI)
 
 
 class LumaHipError(RuntimeError):
@@ -117,148 +242,11 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    vp, u, i, f, sz = C.c_void_p, C.c_uint, C.c_int, C.c_float, C.c_size_t
-    pp3 = C.POINTER(C.c_void_p)
-    ip3 = C.POINTER(C.c_int)
-    sp3 = C.POINTER(C.c_size_t)
-    L.lumahip_abi_version.restype = i
-    L.lumahip_device_count.argtypes = [C.POINTER(i)]
-    L.lumahip_create.argtypes = [C.POINTER(vp), i]
-    L.lumahip_destroy.argtypes = [vp]
-    L.lumahip_destroy.restype = None
-    L.lumahip_last_error.argtypes = [vp]
-    L.lumahip_last_error.restype = C.c_char_p
-    L.lumahip_set_stream.argtypes = [vp, vp]
-    L.lumahip_reset_stream.argtypes = [vp]
-    L.lumahip_sync.argtypes = [vp]
-    L.lumahip_tune.argtypes = [vp, C.c_char_p, C.c_long]
-    L.lumahip_set_quantizer.argtypes = [vp, i, u, i, u, f, f, vp, sz]
-    L.lumahip_build_lut.argtypes = [i, u, f, f, vp, sz]
-    L.lumahip_thresh_index_host.argtypes = [vp, sz, C.POINTER(i), vp, sz]
-    L.lumahip_lin_index_host.argtypes = [vp, sz, C.POINTER(i), vp, sz]
-    L.lumahip_quantizer_info.argtypes = [vp, C.POINTER(i)]
-    L.lumahip_ycbcr_luma_index_host.argtypes = [vp, sz, f, C.POINTER(i), vp, sz]
-    L.lumahip_ycbcr_ytab_host.argtypes = [vp, sz, f, vp]
-    L.lumahip_ycbcr_half_table_host.argtypes = [f, f, vp, sz]
-    L.lumahip_half_table_info.argtypes = [vp, f, C.POINTER(i)]
-    L.lumahip_rb_table_info.argtypes = [vp, f, C.POINTER(i)]
-    L.lumahip_half_upload_info.argtypes = [vp, C.POINTER(C.c_long)]
-    L.lumahip_numa_info.argtypes = [vp, C.POINTER(i)]
-    L.lumahip_numa_pin_current_thread.argtypes = [vp]
-    L.lumahip_numa_plan_host.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(i), C.POINTER(i), i, C.POINTER(i)]
-    L.lumahip_quantize_value_host.argtypes = [vp, sz, i, u, f, u, C.POINTER(f)]
-    L.lumahip_dequantize_value_host.argtypes = [vp, sz, i, u, f, u, C.POINTER(f)]
-    L.lumahip_encode_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, C.POINTER(f), vp]
-    L.lumahip_decode_frame_host.argtypes = [vp, pp3, ip3, u, u, i, f, vp]
-    L.lumahip_encode_frames_host.argtypes = [vp, pp3, u, u, u, f, i, pp3, ip3, C.POINTER(f)]
-    L.lumahip_decode_frames_host.argtypes = [vp, pp3, ip3, u, u, u, i, f, pp3]
-    L.lumahip_pack_frame_host.argtypes = [vp, vp, u, u, i, pp3, ip3, C.POINTER(f)]
-    L.lumahip_unpack_frame_host.argtypes = [vp, pp3, ip3, u, u, i, vp]
-    L.lumahip_transform_color_space_host.argtypes = [vp, vp, u, u, i, f]
-    L.lumahip_quantize_array_host.argtypes = [vp, vp, vp, sz, u]
-    L.lumahip_dequantize_array_host.argtypes = [vp, vp, vp, sz, u]
-    L.lumahip_quantize_array_device.argtypes = [vp, vp, vp, sz, u]
-    L.lumahip_dequantize_array_device.argtypes = [vp, vp, vp, sz, u]
-    L.lumahip_encode_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_mean_luminance_reference_device.argtypes = [vp, vp, u, u, f, C.POINTER(f)]
-    L.lumahip_decode_frames_device.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, vp, sz]
-    L.lumahip_decode_display_frames_device.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, vp, sz, vp, i, sz, f, f, i, i]
-    L.lumahip_transform_color_space_device.argtypes = [vp, vp, sz, u, u, u, i, f]
-    L.lumahip_synth_frames_device.argtypes = [vp, vp, sz, u, u, u, C.c_uint64, C.c_uint64]
-    L.lumahip_time_launches.argtypes = [vp, i, i, vp, sz, u, u, u, f, i, pp3, ip3, sp3, C.POINTER(f)]
-    L.lumahip_probe_encode_traffic_device.argtypes = [vp, vp, sz, u, u, u, pp3, ip3, sp3, i, C.POINTER(f)]
-    L.lumahip_powf_probe_device.argtypes = [vp, vp, C.c_uint32, sz, f, i]
-    L.lumahip_f16_narrow_probe_device.argtypes = [vp, vp, C.c_uint32, sz]
-    L.lumahip_encode_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_encode_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_decode_frames_device_f16.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, vp, sz]
-    L.lumahip_decode_frames_device_planar_f16.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, pp3, sz]
-    L.lumahip_encode_frame_host_f16.argtypes = [vp, vp, u, u, f, i, pp3, ip3, C.POINTER(f)]
-    L.lumahip_decode_frame_host_f16.argtypes = [vp, pp3, ip3, u, u, i, f, vp]
-    L.lumahip_set_source_quantizer.argtypes = [vp, i, u, i, u, f, f, vp, sz]
-    L.lumahip_transcode_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, vp]
-    L.lumahip_transcode_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, C.POINTER(f)]
-    L.lumahip_distortion_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_distortion_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_distortion_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_distortion_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_distortion_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, vp]
-    L.lumahip_transcode_distortion_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, vp]
-    L.lumahip_distortion_map_dims.argtypes = [u, u, u, C.POINTER(u), C.POINTER(u)]
-    L.lumahip_distortion_map_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_distortion_map_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_distortion_map_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_distortion_map_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_distortion_map_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, u, vp, sz]
-    L.lumahip_moments_map_dims.argtypes = [u, u, u, C.POINTER(u), C.POINTER(u)]
-    L.lumahip_moments_map_frames_device.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_moments_map_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_moments_map_frames_device_f16.argtypes = [vp, vp, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_moments_map_frames_device_planar_f16.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, u, vp]
-    L.lumahip_moments_map_frame_host.argtypes = [vp, vp, u, u, f, i, pp3, ip3, u, vp, sz]
-    L.lumahip_transcode_distortion_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, vp]
-    L.lumahip_transcode_distortion_map_frames_device.argtypes = [vp, pp3, ip3, sp3, i, f, u, u, u, pp3, ip3, sp3, i, f, u, vp]
-    L.lumahip_transcode_distortion_map_frame_host.argtypes = [vp, pp3, ip3, i, f, u, u, pp3, ip3, i, f, u, vp, sz]
-    L.lumahip_quantize_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
-    L.lumahip_ycbcr_luma_probe_device.argtypes = [vp, vp, C.c_uint32, sz, i]
-    L.lumahip_host_register.argtypes = [vp, vp, sz]
-    L.lumahip_host_unregister.argtypes = [vp, vp]
-    L.lumahip_malloc.argtypes = [vp, C.POINTER(vp), sz]
-    L.lumahip_free.argtypes = [vp, vp]
-    L.lumahip_memcpy_h2d.argtypes = [vp, vp, vp, sz]
-    L.lumahip_memcpy_d2h.argtypes = [vp, vp, vp, sz]
-    L.lumahip_device.argtypes = [vp]
-    L.lumahip_encode_frames_device_planar.argtypes = [vp, pp3, sz, u, u, u, f, i, pp3, ip3, sp3, vp]
-    L.lumahip_decode_frames_device_planar.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, pp3, sz]
-    L.lumahip_decode_frames_device_rotating.argtypes = [vp, pp3, ip3, sp3, u, u, u, i, f, pp3, sz]
-    L.lumahip_begin_unordered.argtypes = [vp, i]
-    L.lumahip_end_unordered.argtypes = [vp]
-    L.lumahip_probe_decode_traffic_device.argtypes = [vp, pp3, ip3, sp3, u, u, u, pp3, sz, i, C.POINTER(f)]
-    L.lumahip_pool_create.argtypes = [vp, C.POINTER(PoolConfig), C.POINTER(vp)]
-    L.lumahip_pool_create_small.argtypes = [vp, i, i, i, i, C.POINTER(vp)]
-    L.lumahip_decoded_ring_create.argtypes = [vp, u, u, u, u, C.POINTER(vp)]
-    L.lumahip_decoded_ring_destroy.argtypes = [vp]
-    L.lumahip_decoded_ring_destroy.restype = None
-    L.lumahip_decoded_ring_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
-    L.lumahip_decoded_ring_frame.argtypes = [vp, u, u]
-    L.lumahip_decoded_ring_frame.restype = vp
-    L.lumahip_decode_frames_device_ring.argtypes = [vp, pp3, ip3, sp3, u, i, f, vp, u]
-    L.lumahip_pool_destroy.argtypes = [vp]
-    L.lumahip_pool_destroy.restype = None
-    L.lumahip_pool_alloc.argtypes = [vp, i, i, C.POINTER(vp)]
-    L.lumahip_pool_release.argtypes = [vp, vp]
-    L.lumahip_pool_available.argtypes = [vp, i, i]
-    L.lumahip_pool_group_of.argtypes = [vp, vp]
-    L.lumahip_pool_stats_json.argtypes = [vp]
-    L.lumahip_pool_stats_json.restype = C.c_char_p
-    L.lumahip_pool_find_groups.argtypes = [i, PROBE_FN, vp, vp, C.POINTER(i), C.POINTER(C.c_double), C.POINTER(i)]
-    L.lumahip_multi_create.argtypes = [C.POINTER(vp), ip3, i]
-    L.lumahip_multi_destroy.argtypes = [vp]
-    L.lumahip_multi_destroy.restype = None
-    L.lumahip_multi_shards.argtypes = [vp]
-    L.lumahip_multi_ctx.argtypes = [vp, i]
-    L.lumahip_multi_ctx.restype = vp
-    L.lumahip_multi_last_error.argtypes = [vp]
-    L.lumahip_multi_last_error.restype = C.c_char_p
-    L.lumahip_multi_used_rccl.argtypes = [vp]
-    L.lumahip_multi_set_transport.argtypes = [vp, i]
-    L.lumahip_multi_transport_note.argtypes = [vp]
-    L.lumahip_multi_transport_note.restype = C.c_char_p
-    L.lumahip_shard_range.argtypes = [u, i, i, C.POINTER(u), C.POINTER(u)]
-    L.lumahip_multi_set_quantizer.argtypes = [vp, i, u, i, u, f, f, vp, sz]
-    L.lumahip_multi_encode_frames_host.argtypes = [vp, pp3, u, u, u, f, i, pp3, ip3, C.POINTER(f)]
-    L.lumahip_multi_decode_frames_host.argtypes = [vp, pp3, ip3, u, u, u, i, f, pp3]
-    L.lumahip_multi_encode_frames_device.argtypes = [vp, pp3, sz, C.POINTER(u), u, u, f, i, pp3, ip3, sp3]
-    L.lumahip_multi_decode_frames_device.argtypes = [vp, pp3, ip3, sp3, C.POINTER(u), u, u, i, f, pp3, sz]
-    L.lumahip_multi_sync.argtypes = [vp]
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
     return L
-
-
-class PoolConfig(C.Structure):
-    """lumahip_pool_config (include/lumahip.h)"""
-    _fields_ = [("chunk_bytes", C.c_size_t), ("n_float", C.c_int), ("n_y", C.c_int), ("n_uv", C.c_int), ("n_striped", C.c_int),
-                ("keep_free_bytes", C.c_size_t), ("max_chunks", C.c_int), ("probe_iters", C.c_int)]
 
 
 POOL_FLOAT, POOL_Y, POOL_UV, POOL_STRIPED, POOL_ROTATING = range(5)
@@ -307,39 +295,35 @@ def build_lut(ptf: int, bitdepth: int, max_lum: float = 1e4, min_lum: float = 0.
     return out
 
 
+def _index_records(name, lut, mid, ninfo, shape):
+    """the index calls' two passes: ask for the size (records NULL), then, when the table qualifies (info[0]), fetch the records
+    into an array of shape(info).  Returns (info, rec or None)"""
+    lut = np.ascontiguousarray(lut, dtype=np.float32)
+    fn, info, rec = getattr(lib(), name), (C.c_int * ninfo)(), None
+    while True:
+        rc = fn(lut.ctypes.data, lut.size, *mid, info, None if rec is None else rec.ctypes.data, 0 if rec is None else rec.size)
+        if rc != OK:
+            raise LumaHipError(rc, name + " failed")
+        if rec is not None or not info[0]:
+            return info, rec
+        rec = np.zeros(shape(info), dtype=np.uint32)
+
+
+def _thresh_records(name, lut, *mid):
+    info, rec = _index_records(name, lut, mid, 5, lambda info: info[4])
+    return dict(ok=bool(info[0]), mant_bits=info[1], shift=info[2], kmin=info[3], nbuckets=info[4], rec=rec)
+
+
 def thresh_index(lut: np.ndarray):
     """host-only: the threshold records of a table (include/lumahip.h lumahip_thresh_index_host); no GPU needed"""
-    lut = np.ascontiguousarray(lut, dtype=np.float32)
-    info = (C.c_int * 5)()
-    rc = lib().lumahip_thresh_index_host(lut.ctypes.data, lut.size, info, None, 0)
-    if rc != OK:
-        raise LumaHipError(rc, "lumahip_thresh_index_host failed")
-    d = dict(ok=bool(info[0]), mant_bits=info[1], shift=info[2], kmin=info[3], nbuckets=info[4], rec=None)
-    if d["ok"]:
-        rec = np.zeros(info[4], dtype=np.uint32)
-        rc = lib().lumahip_thresh_index_host(lut.ctypes.data, lut.size, info, rec.ctypes.data, rec.size)
-        if rc != OK:
-            raise LumaHipError(rc, "lumahip_thresh_index_host failed")
-        d["rec"] = rec
-    return d
+    return _thresh_records("lumahip_thresh_index_host", lut)
 
 
 def lin_index(lut: np.ndarray):
     """host-only: the value-keyed records of an evenly spaced table (include/lumahip.h lumahip_lin_index_host); no GPU needed.
     dict(ok, nbuckets, kscale (np.float32), rec (nbuckets x 2 uint32: bits(T) - 1, start) | None)"""
-    lut = np.ascontiguousarray(lut, dtype=np.float32)
-    info = (C.c_int * 3)()
-    rc = lib().lumahip_lin_index_host(lut.ctypes.data, lut.size, info, None, 0)
-    if rc != OK:
-        raise LumaHipError(rc, "lumahip_lin_index_host failed")
-    d = dict(ok=bool(info[0]), nbuckets=info[1], kscale=np.array([info[2]], dtype=np.int32).view(np.float32)[0], rec=None)
-    if d["ok"]:
-        rec = np.zeros((info[1], 2), dtype=np.uint32)
-        rc = lib().lumahip_lin_index_host(lut.ctypes.data, lut.size, info, rec.ctypes.data, rec.size)
-        if rc != OK:
-            raise LumaHipError(rc, "lumahip_lin_index_host failed")
-        d["rec"] = rec
-    return d
+    info, rec = _index_records("lumahip_lin_index_host", lut, (), 3, lambda info: (info[1], 2))
+    return dict(ok=bool(info[0]), nbuckets=info[1], kscale=np.array([info[2]], dtype=np.int32).view(np.float32)[0], rec=rec)
 
 
 def lin_lookup(ix, v: np.ndarray) -> np.ndarray:
@@ -354,19 +338,7 @@ def lin_lookup(ix, v: np.ndarray) -> np.ndarray:
 
 def ycbcr_luma_index(lut: np.ndarray, max_lum: float):
     """host-only: the composite luma -> luminance code records of the YCbCr encode kernels (same dict as thresh_index)"""
-    lut = np.ascontiguousarray(lut, dtype=np.float32)
-    info = (C.c_int * 5)()
-    rc = lib().lumahip_ycbcr_luma_index_host(lut.ctypes.data, lut.size, max_lum, info, None, 0)
-    if rc != OK:
-        raise LumaHipError(rc, "lumahip_ycbcr_luma_index_host failed")
-    d = dict(ok=bool(info[0]), mant_bits=info[1], shift=info[2], kmin=info[3], nbuckets=info[4], rec=None)
-    if d["ok"]:
-        rec = np.zeros(info[4], dtype=np.uint32)
-        rc = lib().lumahip_ycbcr_luma_index_host(lut.ctypes.data, lut.size, max_lum, info, rec.ctypes.data, rec.size)
-        if rc != OK:
-            raise LumaHipError(rc, "lumahip_ycbcr_luma_index_host failed")
-        d["rec"] = rec
-    return d
+    return _thresh_records("lumahip_ycbcr_luma_index_host", lut, max_lum)
 
 
 def ycbcr_ytab(lut: np.ndarray, max_lum: float) -> np.ndarray:
@@ -532,6 +504,52 @@ class Context:
         if rc != OK:
             raise LumaHipError(rc, self.L.lumahip_last_error(self.h).decode())
 
+    # ---- one body per argument shape; `tail` is whatever the C function takes after the shared run
+    def _frame_fed(self, fn, frames, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides, *tail):
+        """the frame-fed device calls; frames: a packed pointer, or _arr3 of three colour-plane pointers for the _planar forms"""
+        self._chk(fn(self.h, frames, frame_stride, nframes, w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
+                     _arr3(C.c_size_t, plane_frame_strides), *tail))
+
+    def _plane_fed(self, fn, plane_ptrs, strides, plane_frame_strides, *tail):
+        """the plane-fed device calls (the decode forms)"""
+        self._chk(fn(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides), *tail))
+
+    def _two_sets(self, fn, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h, dst_plane_ptrs,
+                  dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, *tail):
+        """the device calls over source planes and target planes (transcode and its measuring forms)"""
+        self._chk(fn(self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides), _arr3(C.c_size_t, src_plane_frame_strides),
+                     src_profile, src_sc, nframes, w, h, _arr3(C.c_void_p, dst_plane_ptrs), _arr3(C.c_int, dst_strides),
+                     _arr3(C.c_size_t, dst_plane_frame_strides), dst_profile, dst_sc, *tail))
+
+    def _measured(self, fn, args, w, h, words, dims, block):
+        """the measuring host forms: fn(ctx, *args, tail) into a (3, words) uint64 array of the frame, or with dims into a
+        (nby, nbx, 3, words) one per block"""
+        if dims is None:
+            out = np.zeros((3, words), dtype=np.uint64)
+            self._chk(fn(self.h, *args, out.ctypes.data))
+        else:
+            nbx, nby = dims(w, h, block)
+            out = np.zeros((nby, nbx, 3, words), dtype=np.uint64)
+            self._chk(fn(self.h, *args, block, out.ctypes.data, out.size))
+        return out
+
+    def _measure_frame(self, fn, rgb, planes, strides, sc, profile, words, dims=None, block=None):
+        """the frame-fed measuring host forms"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        _, h, w = rgb.shape
+        planes = [np.ascontiguousarray(p) for p in planes]
+        args = (rgb.ctypes.data, w, h, sc, profile, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides))
+        return self._measured(fn, args, w, h, words, dims, block)
+
+    def _measure_planes(self, fn, planes, strides, w, h, given_planes, given_strides, src_sc, src_profile, dst_sc, dst_profile, dims=None,
+                        block=None):
+        """the plane-fed measuring host forms"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        given_planes = [np.ascontiguousarray(p) for p in given_planes]
+        args = (_arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
+                _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc)
+        return self._measured(fn, args, w, h, 4, dims, block)
+
     # ---- configuration
     def set_stream(self, hip_stream: int | None):
         """hip_stream: a hipStream_t handle (0 = the default stream, as torch's default stream reports);
@@ -628,68 +646,34 @@ class Context:
     def distortion_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2) -> np.ndarray:
         """rgb: (3,h,w) float32; planes: the given code planes as three (rows, stride) uint8 arrays.  Returns a (3, 4) uint64 array:
         per plane {sse, sad, max_abs, n_differ} of the planes encode_frame would write against the given ones"""
-        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-        _, h, w = rgb.shape
-        planes = [np.ascontiguousarray(p) for p in planes]
-        out = np.zeros((3, 4), dtype=np.uint64)
-        self._chk(self.L.lumahip_distortion_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
-                                                       _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
-                                                       out.ctypes.data))
-        return out
+        return self._measure_frame(self.L.lumahip_distortion_frame_host, rgb, planes, strides, sc, profile, 4)
 
     def distortion_map_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2, block=16) -> np.ndarray:
         """distortion_frame's words per block of block x block luma pixels (16, 32 or 64): a (nby, nbx, 3, 4) uint64 array, in one
         launch; block_sample_counts gives the samples behind each entry"""
-        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-        _, h, w = rgb.shape
-        planes = [np.ascontiguousarray(p) for p in planes]
-        nbx, nby = distortion_map_dims(w, h, block)
-        out = np.zeros((nby, nbx, 3, 4), dtype=np.uint64)
-        self._chk(self.L.lumahip_distortion_map_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
-                                                           _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
-                                                           block, out.ctypes.data, out.size))
-        return out
+        return self._measure_frame(self.L.lumahip_distortion_map_frame_host, rgb, planes, strides, sc, profile, 4, distortion_map_dims,
+                                   block)
 
     def moments_map_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2, block=8) -> np.ndarray:
         """per block of block x block luma pixels (8, 16, 32 or 64) and plane the five sums {Se, Sg, See, Sgg, Seg} of the frame's
         codes e and the given samples g: a (nby, nbx, 3, 5) uint64 array, in one launch; moments_sample_counts gives the samples
         behind each entry and code_ssim the structural similarity"""
-        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-        _, h, w = rgb.shape
-        planes = [np.ascontiguousarray(p) for p in planes]
-        nbx, nby = moments_map_dims(w, h, block)
-        out = np.zeros((nby, nbx, 3, 5), dtype=np.uint64)
-        self._chk(self.L.lumahip_moments_map_frame_host(self.h, rgb.ctypes.data, w, h, sc, profile,
-                                                        _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
-                                                        block, out.ctypes.data, out.size))
-        return out
+        return self._measure_frame(self.L.lumahip_moments_map_frame_host, rgb, planes, strides, sc, profile, 5, moments_map_dims, block)
 
     def transcode_distortion_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
                                    dst_profile=2) -> np.ndarray:
         """planes: code planes under the source quantizer; given_planes: code planes in the target's format, three (rows, stride)
         uint8 arrays each.  Returns a (3, 4) uint64 array: per plane {sse, sad, max_abs, n_differ} of the planes transcode_frame
         would write against the given ones, in one fused launch"""
-        planes = [np.ascontiguousarray(p) for p in planes]
-        given_planes = [np.ascontiguousarray(p) for p in given_planes]
-        out = np.zeros((3, 4), dtype=np.uint64)
-        self._chk(self.L.lumahip_transcode_distortion_frame_host(
-            self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
-            _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc, out.ctypes.data))
-        return out
+        return self._measure_planes(self.L.lumahip_transcode_distortion_frame_host, planes, strides, w, h, given_planes, given_strides,
+                                    src_sc, src_profile, dst_sc, dst_profile)
 
     def transcode_distortion_map_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
                                        dst_profile=2, block=16) -> np.ndarray:
         """transcode_distortion_frame's words per block of block x block luma pixels (16, 32 or 64) of the target: a
         (nby, nbx, 3, 4) uint64 array, in one launch; block_sample_counts(w, h, dst_profile, block) gives the samples behind each entry"""
-        planes = [np.ascontiguousarray(p) for p in planes]
-        given_planes = [np.ascontiguousarray(p) for p in given_planes]
-        nbx, nby = distortion_map_dims(w, h, block)
-        out = np.zeros((nby, nbx, 3, 4), dtype=np.uint64)
-        self._chk(self.L.lumahip_transcode_distortion_map_frame_host(
-            self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
-            _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc, block,
-            out.ctypes.data, out.size))
-        return out
+        return self._measure_planes(self.L.lumahip_transcode_distortion_map_frame_host, planes, strides, w, h, given_planes, given_strides,
+                                    src_sc, src_profile, dst_sc, dst_profile, distortion_map_dims, block)
 
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
@@ -780,116 +764,95 @@ class Context:
     # ---- device entry points (raw device pointers, e.g. torch.Tensor.data_ptr())
     def encode_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                              plane_frame_strides, stats_ptr=None):
-        self._chk(self.L.lumahip_encode_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                      _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                      _arr3(C.c_size_t, plane_frame_strides), stats_ptr))
+        self._frame_fed(self.L.lumahip_encode_frames_device, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                        plane_frame_strides, stats_ptr)
 
     def transcode_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
                                 dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr=None):
-        self._chk(self.L.lumahip_transcode_frames_device(self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides),
-                                                         _arr3(C.c_size_t, src_plane_frame_strides), src_profile, src_sc, nframes, w, h,
-                                                         _arr3(C.c_void_p, dst_plane_ptrs), _arr3(C.c_int, dst_strides),
-                                                         _arr3(C.c_size_t, dst_plane_frame_strides), dst_profile, dst_sc, stats_ptr))
+        self._two_sets(self.L.lumahip_transcode_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc,
+                       nframes, w, h, dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr)
 
     # distortion of given planes against the frames' own encode: out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ}
     # as uint64 (zeroed by the call); the arguments are those of the matching encode call
     def distortion_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides,
                                  out_ptr):
-        self._chk(self.L.lumahip_distortion_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                          _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                          _arr3(C.c_size_t, plane_frame_strides), out_ptr))
+        self._frame_fed(self.L.lumahip_distortion_frames_device, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                        plane_frame_strides, out_ptr)
 
     def distortion_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                         plane_frame_strides, out_ptr):
-        self._chk(self.L.lumahip_distortion_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
-                                                                 sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                                 _arr3(C.c_size_t, plane_frame_strides), out_ptr))
+        self._frame_fed(self.L.lumahip_distortion_frames_device_planar, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h, sc,
+                        profile, plane_ptrs, strides, plane_frame_strides, out_ptr)
 
     def distortion_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                      plane_frame_strides, out_ptr):
-        self._chk(self.L.lumahip_distortion_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                              _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                              _arr3(C.c_size_t, plane_frame_strides), out_ptr))
+        self._frame_fed(self.L.lumahip_distortion_frames_device_f16, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                        plane_frame_strides, out_ptr)
 
     def distortion_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                             plane_frame_strides, out_ptr):
-        self._chk(self.L.lumahip_distortion_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
-                                                                     w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
-                                                                     _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
-                                                                     out_ptr))
+        self._frame_fed(self.L.lumahip_distortion_frames_device_planar_f16, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
+                        sc, profile, plane_ptrs, strides, plane_frame_strides, out_ptr)
 
     # the same per block x block luma pixels (16, 32 or 64): map_ptr receives nframes x nby x nbx x 3 planes x {sse, sad, max_abs,
     # n_differ} as uint64, every word written by the launch (distortion_map_dims, block_sample_counts)
     def distortion_map_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides,
                                      block, map_ptr):
-        self._chk(self.L.lumahip_distortion_map_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                              _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                              _arr3(C.c_size_t, plane_frame_strides), block, map_ptr))
+        self._frame_fed(self.L.lumahip_distortion_map_frames_device, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                        plane_frame_strides, block, map_ptr)
 
     def distortion_map_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                             plane_frame_strides, block, map_ptr):
-        self._chk(self.L.lumahip_distortion_map_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w,
-                                                                     h, sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                                     _arr3(C.c_size_t, plane_frame_strides), block, map_ptr))
+        self._frame_fed(self.L.lumahip_distortion_map_frames_device_planar, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
+                        sc, profile, plane_ptrs, strides, plane_frame_strides, block, map_ptr)
 
     def distortion_map_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                          plane_frame_strides, block, map_ptr):
-        self._chk(self.L.lumahip_distortion_map_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                                  _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                                  _arr3(C.c_size_t, plane_frame_strides), block, map_ptr))
+        self._frame_fed(self.L.lumahip_distortion_map_frames_device_f16, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs,
+                        strides, plane_frame_strides, block, map_ptr)
 
     def distortion_map_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                                 plane_frame_strides, block, map_ptr):
-        self._chk(self.L.lumahip_distortion_map_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
-                                                                         w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
-                                                                         _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
-                                                                         block, map_ptr))
+        self._frame_fed(self.L.lumahip_distortion_map_frames_device_planar_f16, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w,
+                        h, sc, profile, plane_ptrs, strides, plane_frame_strides, block, map_ptr)
 
     # the moments of both signals per block x block luma pixels (8, 16, 32 or 64): mom_ptr receives nframes x nby x nbx x 3 planes x
     # {Se, Sg, See, Sgg, Seg} as uint64, every word written by the launch (moments_map_dims, moments_sample_counts, code_ssim)
     def moments_map_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides, plane_frame_strides,
                                   block, mom_ptr):
-        self._chk(self.L.lumahip_moments_map_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                           _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                           _arr3(C.c_size_t, plane_frame_strides), block, mom_ptr))
+        self._frame_fed(self.L.lumahip_moments_map_frames_device, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                        plane_frame_strides, block, mom_ptr)
 
     def moments_map_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                          plane_frame_strides, block, mom_ptr):
-        self._chk(self.L.lumahip_moments_map_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w,
-                                                                  h, sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                                  _arr3(C.c_size_t, plane_frame_strides), block, mom_ptr))
+        self._frame_fed(self.L.lumahip_moments_map_frames_device_planar, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h, sc,
+                        profile, plane_ptrs, strides, plane_frame_strides, block, mom_ptr)
 
     def moments_map_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                       plane_frame_strides, block, mom_ptr):
-        self._chk(self.L.lumahip_moments_map_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                               _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                               _arr3(C.c_size_t, plane_frame_strides), block, mom_ptr))
+        self._frame_fed(self.L.lumahip_moments_map_frames_device_f16, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs,
+                        strides, plane_frame_strides, block, mom_ptr)
 
     def moments_map_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                              plane_frame_strides, block, mom_ptr):
-        self._chk(self.L.lumahip_moments_map_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
-                                                                      w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
-                                                                      _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
-                                                                      block, mom_ptr))
+        self._frame_fed(self.L.lumahip_moments_map_frames_device_planar_f16, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
+                        sc, profile, plane_ptrs, strides, plane_frame_strides, block, mom_ptr)
 
     # distortion of given planes against the source planes' own transcode: the arguments are transcode_frames_device's, the
     # target-side planes are read, out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ} as uint64 (zeroed by the call)
     def transcode_distortion_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
                                            given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, out_ptr):
-        self._chk(self.L.lumahip_transcode_distortion_frames_device(
-            self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides), _arr3(C.c_size_t, src_plane_frame_strides), src_profile,
-            src_sc, nframes, w, h, _arr3(C.c_void_p, given_plane_ptrs), _arr3(C.c_int, given_strides),
-            _arr3(C.c_size_t, given_plane_frame_strides), dst_profile, dst_sc, out_ptr))
+        self._two_sets(self.L.lumahip_transcode_distortion_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile,
+                       src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, out_ptr)
 
     # the same per block x block luma pixels of the target (16, 32 or 64): map_ptr receives nframes x nby x nbx x 3 planes x {sse, sad,
     # max_abs, n_differ} as uint64, every word written by the launch
     def transcode_distortion_map_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w,
                                                h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, block,
                                                map_ptr):
-        self._chk(self.L.lumahip_transcode_distortion_map_frames_device(
-            self.h, _arr3(C.c_void_p, src_plane_ptrs), _arr3(C.c_int, src_strides), _arr3(C.c_size_t, src_plane_frame_strides), src_profile,
-            src_sc, nframes, w, h, _arr3(C.c_void_p, given_plane_ptrs), _arr3(C.c_int, given_strides),
-            _arr3(C.c_size_t, given_plane_frame_strides), dst_profile, dst_sc, block, map_ptr))
+        self._two_sets(self.L.lumahip_transcode_distortion_map_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
+                       src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
+                       block, map_ptr)
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""
@@ -899,18 +862,16 @@ class Context:
 
     def decode_frames_device(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, rgb_ptr,
                              frame_stride):
-        self._chk(self.L.lumahip_decode_frames_device(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                      _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile,
-                                                      sc, rgb_ptr, frame_stride))
+        self._plane_fed(self.L.lumahip_decode_frames_device, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, rgb_ptr,
+                        frame_stride)
 
     def decode_display_frames_device(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, rgba_ptr,
                                      rgba_stride, rgba_frame_stride, exposure=1.0, gamma=2.2, do_tmo=False,
                                      ldr_sim=False, rgb_ptr=None, frame_stride=0):
         """decode fused with the player's display transform -> RGBA8"""
-        self._chk(self.L.lumahip_decode_display_frames_device(
-            self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
-            nframes, w, h, profile, sc, rgb_ptr, frame_stride, rgba_ptr, rgba_stride, rgba_frame_stride, exposure, gamma,
-            int(bool(do_tmo)), int(bool(ldr_sim))))
+        self._plane_fed(self.L.lumahip_decode_display_frames_device, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc,
+                        rgb_ptr, frame_stride, rgba_ptr, rgba_stride, rgba_frame_stride, exposure, gamma, int(bool(do_tmo)),
+                        int(bool(ldr_sim)))
 
     def quantize_array_device(self, in_ptr, out_ptr, n, ch=0):
         self._chk(self.L.lumahip_quantize_array_device(self.h, in_ptr, out_ptr, n, ch))
@@ -940,47 +901,39 @@ class Context:
     def encode_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                     plane_frame_strides, stats_ptr=None):
         """float frames as three colour-plane base pointers (plane c of frame f at rgb_plane_ptrs[c] + f*frame_stride floats)"""
-        self._chk(self.L.lumahip_encode_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
-                                                             sc, profile, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                             _arr3(C.c_size_t, plane_frame_strides), stats_ptr))
+        self._frame_fed(self.L.lumahip_encode_frames_device_planar, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h, sc,
+                        profile, plane_ptrs, strides, plane_frame_strides, stats_ptr)
 
     def decode_frames_device_rotating(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, base_ptrs, frame_stride):
         """packed frames over three buffers: frame f at base_ptrs[f % 3] + (f // 3) * frame_stride floats"""
-        self._chk(self.L.lumahip_decode_frames_device_rotating(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                               _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile, sc,
-                                                               _arr3(C.c_void_p, base_ptrs), frame_stride))
+        self._plane_fed(self.L.lumahip_decode_frames_device_rotating, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc,
+                        _arr3(C.c_void_p, base_ptrs), frame_stride)
 
     def decode_frames_device_planar(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, rgb_plane_ptrs,
                                     frame_stride):
-        self._chk(self.L.lumahip_decode_frames_device_planar(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                             _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile, sc,
-                                                             _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride))
+        self._plane_fed(self.L.lumahip_decode_frames_device_planar, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc,
+                        _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride)
 
     # binary16 frames (raw device pointers to halves, e.g. a torch.float16 tensor's data_ptr(); strides count halves)
     def encode_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                  plane_frame_strides, stats_ptr=None):
-        self._chk(self.L.lumahip_encode_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, sc, profile,
-                                                          _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                          _arr3(C.c_size_t, plane_frame_strides), stats_ptr))
+        self._frame_fed(self.L.lumahip_encode_frames_device_f16, rgb_ptr, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
+                        plane_frame_strides, stats_ptr)
 
     def encode_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, sc, profile, plane_ptrs, strides,
                                         plane_frame_strides, stats_ptr=None):
-        self._chk(self.L.lumahip_encode_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes,
-                                                                 w, h, sc, profile, _arr3(C.c_void_p, plane_ptrs),
-                                                                 _arr3(C.c_int, strides), _arr3(C.c_size_t, plane_frame_strides),
-                                                                 stats_ptr))
+        self._frame_fed(self.L.lumahip_encode_frames_device_planar_f16, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h, sc,
+                        profile, plane_ptrs, strides, plane_frame_strides, stats_ptr)
 
     def decode_frames_device_f16(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, rgb_ptr,
                                  frame_stride):
-        self._chk(self.L.lumahip_decode_frames_device_f16(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                          _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile,
-                                                          sc, rgb_ptr, frame_stride))
+        self._plane_fed(self.L.lumahip_decode_frames_device_f16, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc,
+                        rgb_ptr, frame_stride)
 
     def decode_frames_device_planar_f16(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc,
                                         rgb_plane_ptrs, frame_stride):
-        self._chk(self.L.lumahip_decode_frames_device_planar_f16(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                                 _arr3(C.c_size_t, plane_frame_strides), nframes, w, h, profile,
-                                                                 sc, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride))
+        self._plane_fed(self.L.lumahip_decode_frames_device_planar_f16, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile,
+                        sc, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride)
 
     def f16_narrow_probe_device(self, out_ptr, first_bits, n):
         """uint16 binary16 bits the decode kernels store for the n consecutive fp32 bit patterns from first_bits"""
@@ -997,9 +950,8 @@ class Context:
                              iters=1) -> float:
         """ms per launch of the decode kernel's loads + stores without arithmetic (overwrites the frames)"""
         ms = C.c_float(0)
-        self._chk(self.L.lumahip_probe_decode_traffic_device(self.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                             _arr3(C.c_size_t, plane_frame_strides), nframes, w, h,
-                                                             _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, iters, C.byref(ms)))
+        self._plane_fed(self.L.lumahip_probe_decode_traffic_device, plane_ptrs, strides, plane_frame_strides, nframes, w, h,
+                        _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, iters, C.byref(ms))
         return float(ms.value)
 
     def probe_encode_traffic(self, rgb_ptr, frame_stride, nframes, w, h, plane_ptrs, strides, plane_frame_strides,
@@ -1071,8 +1023,8 @@ class DecodedRing:
 
     def decode(self, plane_ptrs, strides, plane_frame_strides, nframes, profile, sc, batch):
         """lumahip_decode_frames_device_ring: nframes frames into batch slot `batch` (asynchronous)"""
-        self.ctx._chk(self.L.lumahip_decode_frames_device_ring(self.ctx.h, _arr3(C.c_void_p, plane_ptrs), _arr3(C.c_int, strides),
-                                                               _arr3(C.c_size_t, plane_frame_strides), nframes, profile, sc, self.h, batch))
+        self.ctx._plane_fed(self.L.lumahip_decode_frames_device_ring, plane_ptrs, strides, plane_frame_strides, nframes, profile, sc, self.h,
+                            batch)
 
     def close(self):
         if self.h:

@@ -1754,10 +1754,11 @@ struct MapGeom {
     int mapTilesPerFrame, totalMapTiles;   // nby * g.tilesX, * nframes
 };
 
-struct DistMapArgs {
+// (of both frame-fed map kernels, k_distortion_map and k_moments_map)
+struct MapArgs {
     EncArgs e;         // as DistArgs::e
     DecArgs g;         // as DistArgs::g
-    uint64_t *map;     // [nframes][nby][nbx][3 planes][sse, sad, max_abs, n_differ]; needs no zeroing
+    uint64_t *map;     // [nframes][nby][nbx][3 planes][sse, sad, max_abs, n_differ | se, sg, see, sgg, seg]; needs no zeroing
     MapGeom m;
 };
 
@@ -1936,7 +1937,7 @@ LH_DEV void dist_map_flush(Acc &acc, unsigned long long *s_map, const MapGeom &a
 // loads of the next sub-tile -- of the next map tile behind the last one -- are issued before the flush, so they are in flight
 // across its barriers.
 template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void k_distortion_map(const DistMapArgs a)
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void k_distortion_map(const MapArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(LM == 3 || LM == 7 || LM == 5 || LM == 6, "search records in LDS");
@@ -1988,13 +1989,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
 // another record (MomentBlockAcc): 15 words per block, LDS adds only, no shortcut for waves without a difference.  B = 8 makes a
 // block 2 lanes at VW 4 (map_lanes_meet's pair step alone) and a map tile 32 blocks.
 // Reads 12 + 3 B per pixel (6 + 3 from binary16 frames), writes 120 B per block; no scratch planes, no global atomic, no memset.
-struct MomentsMapArgs {
-    EncArgs e;         // as DistArgs::e
-    DecArgs g;         // as DistArgs::g
-    uint64_t *map;     // [nframes][nby][nbx][3 planes][se, sg, see, sgg, seg]; needs no zeroing
-    MapGeom m;
-};
-
 // Row r of plane pl of the given unit exactly as DistMeasureUnit::row fetches it.  That one keeps its own copy of these lines: with
 // the fetch behind a function -- free, member of a base, by reference or by value -- the compiler allocates the registers of every
 // k_distortion, k_distortion_map and k_transcode_distortion(_map) kernel differently (same instructions, other registers and order;
@@ -2049,7 +2043,7 @@ constexpr int moments_threads_bound(int cs, bool sub, int vw, int lm) { return m
 
 template <int CS, bool SUB, int VW, int LM, bool IN16 = false>
 __global__ __launch_bounds__(moments_threads_bound(CS, SUB, VW, LM)) __attribute__((amdgpu_waves_per_eu(moments_wide(CS, SUB, VW, LM) ? 3 : 4)))
-void k_moments_map(const MomentsMapArgs a)
+void k_moments_map(const MapArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(LM == 3 || LM == 7 || LM == 5 || LM == 6, "search records in LDS");
@@ -2103,7 +2097,7 @@ struct TransDistMapArgs {
     DecArgs d;         // the source planes, as TransArgs::d
     EncArgs e;         // the target quantizer, as TransDistArgs::e
     DecArgs g;         // the given planes, as TransDistArgs::g
-    uint64_t *map;     // as DistMapArgs::map
+    uint64_t *map;     // as MapArgs::map
     MapGeom m;
 };
 

@@ -1,7 +1,9 @@
-// lumahip_distortion.hip -- dispatch of the code-domain distortion kernels (lh::k_distortion, luma_kernels.hpp): how far given code
-// planes are from the planes lumahip_encode_frames_device would write for the same frames, as integer sums per frame and plane.
-// Its own translation unit (float frames; lumahip_distortion_f16.hip holds the binary16-frame kernels): the kernels compile side
-// by side with the encode, decode and transcode units, and no kernel is in two code objects.
+// lumahip_distortion.hip -- the frame-fed measuring calls: how far given code planes are from the planes lumahip_encode_frames_device
+// would write for the same frames, as integer sums per frame and plane (lh::k_distortion, luma_kernels.hpp), per block (k_distortion_map)
+// or as the moments of both signals per block (k_moments_map).  One plan (distortion_plan), one dispatch (measure_frames_impl) and the
+// entry points of all three; of the kernels this unit compiles the float-frame k_distortion only.  The others have a translation unit
+// each that exports their picker (lumahip_distortion_f16.hip, lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip /
+// _f16.hip): they compile side by side, and no kernel is in two code objects.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
@@ -109,40 +111,92 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     return LUMAHIP_OK;
 }
 
-int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out, const DistortionLaunch &o)
+dist_kernel_t pick_dist_f32(int cs, bool sub, int vw, int mode) { return pick_dist<DistFamily, false>(cs, sub, vw, mode); }
+
+int measure_frames_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, DistWhat what, unsigned block, uint64_t *out,
+                        const DistortionLaunch &o)
 {
     DistortionPlan p;
-    if (int rc = distortion_plan(c, f, sc, given, out, DistWhat::Frame, 0, o.stream, p))
+    if (int rc = distortion_plan(c, f, sc, given, out, what, block, o.stream, p))
         return rc;
-    DistArgs a{};
+    const auto no_kernel = [&](const char *name) {
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no %s kernel for colour space %d%s", name, p.cs, p.in16 ? " with binary16 frames" : "");
+    };
+    if (what == DistWhat::Frame) {
+        DistArgs a{};
+        a.e = p.e;
+        a.g = p.g;
+        a.out = out;
+        const dist_kernel_t kern = (p.in16 ? pick_dist_f16 : pick_dist_f32)(p.cs, p.sub, p.vw, p.kmode);
+        if (!kern)
+            return no_kernel("distortion");
+        return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, f.nframes);
+    }
+    const bool moments = what == DistWhat::Moments;
+    MapArgs a{};
     a.e = p.e;
     a.g = p.g;
-    a.out = out;
-    const dist_kernel_t kern = p.in16 ? pick_dist_f16(p.cs, p.sub, p.vw, p.kmode) : pick_dist<DistFamily, false>(p.cs, p.sub, p.vw, p.kmode);
+    a.map = out;
+    a.m = make_map_geom(p.e.g, f.w, f.h, block, p.threads);   // (S >= 1: distortion_plan has clamped the workgroup)
+    const map_kernel_t kern = (moments ? (p.in16 ? pick_moments_map_f16 : pick_moments_map_f32)
+                                       : (p.in16 ? pick_dist_map_f16 : pick_dist_map_f32))(p.cs, p.sub, p.vw, p.kmode);
     if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no distortion kernel for colour space %d%s", p.cs, p.in16 ? " with binary16 frames" : "");
-    return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, f.nframes);
+        return no_kernel(moments ? "moments map" : "distortion map");
+    // grid_for's encode rule over the standard tiles; a workgroup takes whole map tiles
+    const int grid = p.grid < a.m.totalMapTiles ? p.grid : a.m.totalMapTiles;
+    if (int rc = launch_fused(c, kern, grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
+        return rc;
+    HIPCHK(c, hipGetLastError());
+    return LUMAHIP_OK;
+}
+
+// what every frame-fed _device entry point does in front of the dispatch; frames_given: the packed forms' base pointer (the planar
+// forms' three pointers are distortion_plan's to check)
+static int measure_frames_entry(lumahip_ctx *c, bool frames_given, const SrcFrames &f, float sc, const SrcPlanes &given, DistWhat what,
+                                unsigned block, uint64_t *out)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!frames_given)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    return measure_frames_impl(c, f, sc, given, what, block, out, {c->stream, true});
+}
+
+static int map_dims(DistWhat what, unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby)
+{
+    if (!dist_block_ok(what, block) || !nbx || !nby)
+        return LUMAHIP_ERR_ARG;
+    *nbx = (w + block - 1) / block;
+    *nby = (h + block - 1) / block;
+    return LUMAHIP_OK;
 }
 
 }  // namespace lhost
 
-extern "C" int lumahip_distortion_frames_device(lumahip_ctx *c, const float *rgb, size_t frame_stride, unsigned nframes, unsigned w, unsigned h,
-                                                float sc, int profile, const unsigned char *const planes[3], const int stride[3],
-                                                const size_t pfs[3], uint64_t *out_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!rgb)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return distortion_impl(c, packed_frames(rgb, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, out_dev, {c->stream, true});
-}
+// The twelve _device entry points and the two *_map_dims (include/lumahip.h has their full prototypes): the frames, MEASURE_PARAMS,
+// then the call's own tail.
+#define MEASURE_PARAMS                                                                                                                   \
+    size_t frame_stride, unsigned nframes, unsigned w, unsigned h, float sc, int profile, const unsigned char *const planes[3],         \
+        const int stride[3], const size_t pfs[3]
+#define PACKED(what, block, out) \
+    measure_frames_entry(c, rgb != nullptr, packed_frames(rgb, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, DistWhat::what, block, out)
+#define PLANAR(what, block, out) \
+    measure_frames_entry(c, true, planar_frames(rgb_planes, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, DistWhat::what, block, out)
+extern "C" {
+int lumahip_distortion_frames_device(lumahip_ctx *c, const float *rgb, MEASURE_PARAMS, uint64_t *out_dev) { return PACKED(Frame, 0, out_dev); }
+int lumahip_distortion_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], MEASURE_PARAMS, uint64_t *out_dev) { return PLANAR(Frame, 0, out_dev); }
+int lumahip_distortion_frames_device_f16(lumahip_ctx *c, const uint16_t *rgb, MEASURE_PARAMS, uint64_t *out_dev) { return PACKED(Frame, 0, out_dev); }
+int lumahip_distortion_frames_device_planar_f16(lumahip_ctx *c, const uint16_t *const rgb_planes[3], MEASURE_PARAMS, uint64_t *out_dev) { return PLANAR(Frame, 0, out_dev); }
 
-extern "C" int lumahip_distortion_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], size_t frame_stride, unsigned nframes,
-                                                       unsigned w, unsigned h, float sc, int profile, const unsigned char *const planes[3],
-                                                       const int stride[3], const size_t pfs[3], uint64_t *out_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    return distortion_impl(c, planar_frames(rgb_planes, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, out_dev,
-                           {c->stream, true});
-}
+int lumahip_distortion_map_dims(unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby) { return map_dims(DistWhat::Map, w, h, block, nbx, nby); }
+int lumahip_distortion_map_frames_device(lumahip_ctx *c, const float *rgb, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return PACKED(Map, block, map_dev); }
+int lumahip_distortion_map_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return PLANAR(Map, block, map_dev); }
+int lumahip_distortion_map_frames_device_f16(lumahip_ctx *c, const uint16_t *rgb, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return PACKED(Map, block, map_dev); }
+int lumahip_distortion_map_frames_device_planar_f16(lumahip_ctx *c, const uint16_t *const rgb_planes[3], MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return PLANAR(Map, block, map_dev); }
+
+int lumahip_moments_map_dims(unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby) { return map_dims(DistWhat::Moments, w, h, block, nbx, nby); }
+int lumahip_moments_map_frames_device(lumahip_ctx *c, const float *rgb, MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return PACKED(Moments, block, mom_dev); }
+int lumahip_moments_map_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return PLANAR(Moments, block, mom_dev); }
+int lumahip_moments_map_frames_device_f16(lumahip_ctx *c, const uint16_t *rgb, MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return PACKED(Moments, block, mom_dev); }
+int lumahip_moments_map_frames_device_planar_f16(lumahip_ctx *c, const uint16_t *const rgb_planes[3], MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return PLANAR(Moments, block, mom_dev); }
+}  // extern "C"

@@ -1,34 +1,9 @@
-// lumahip_distortion_f16.hip -- the binary16-frame distortion kernels (lh::k_distortion<..., IN16 = true>, luma_kernels.hpp) and the C
-// entry points lumahip_distortion_frames_device_f16 / _planar_f16.  Their own translation unit so that they compile side by side
-// with the float kernels of lumahip_distortion.hip.
+// lumahip_distortion_f16.hip -- the binary16-frame distortion kernels (lh::k_distortion<..., IN16 = true>, luma_kernels.hpp), named
+// here and nowhere else: their own translation unit, so that they compile side by side with the float kernels of
+// lumahip_distortion.hip, which holds the dispatch (measure_frames_impl) and the entry points.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
-
-using namespace lh;
-using namespace lhost;
 
 namespace lhost {
 dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode) { return pick_dist<DistFamily, true>(cs, sub, vw, mode); }
 }  // namespace lhost
-
-extern "C" int lumahip_distortion_frames_device_f16(lumahip_ctx *c, const uint16_t *rgb, size_t frame_stride, unsigned nframes, unsigned w,
-                                                    unsigned h, float sc, int profile, const unsigned char *const planes[3],
-                                                    const int stride[3], const size_t pfs[3], uint64_t *out_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!rgb)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return distortion_impl(c, packed_frames(rgb, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, out_dev, {c->stream, true});
-}
-
-extern "C" int lumahip_distortion_frames_device_planar_f16(lumahip_ctx *c, const uint16_t *const rgb_planes[3], size_t frame_stride,
-                                                           unsigned nframes, unsigned w, unsigned h, float sc, int profile,
-                                                           const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
-                                                           uint64_t *out_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    return distortion_impl(c, planar_frames(rgb_planes, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, out_dev,
-                           {c->stream, true});
-}

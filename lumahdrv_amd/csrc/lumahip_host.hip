@@ -1109,120 +1109,98 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
     return LUMAHIP_OK;
 }
 
-// One float frame and given planes in host memory -> the 12 distortion words (lumahip_distortion.hip), synchronously
-extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
-                                             const unsigned char *const planes[3], const int stride[3], uint64_t out[12])
+// One float frame and given planes in host memory -> what a frame-fed measuring call delivers (lumahip_distortion.hip), synchronously:
+// the 12 distortion words (Frame; block and out_words ignored), or the frame's distortion / moments map of nbx * nby * 12 / 15 words
+static int measure_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile, const unsigned char *const planes[3],
+                              const int stride[3], DistWhat what, unsigned block, uint64_t *out, size_t out_words)
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
     if (!rgb || !planes || !stride || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    const bool map = what != DistWhat::Frame, moments = what == DistWhat::Moments;
+    const char *const name = moments ? "moments map" : "distortion map";
+    if (map && !dist_block_ok(what, block))
+        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", name, moments ? "8, " : "", block);
     StagedPlanes given{"", planes, stride, profile};
-    const size_t nfl = (size_t)3 * w * h;
-    int rc = planes_staging(c, w, h, nullptr, given, 12);
-    if (rc || (rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
-        (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
-        (rc = distortion_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), reinterpret_cast<uint64_t *>(c->d_arr),
-                              {c->stream, false})))
-        return rc;
-    return words_down(c, out);
-}
-
-// ... -> the frame's distortion map (lumahip_distortion_map.hip): nbx * nby * 12 words, synchronously
-extern "C" int lumahip_distortion_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
-                                                 const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *map,
-                                                 size_t map_words)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!rgb || !planes || !stride || !map)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    if (!dist_map_block_ok(block))
-        return fail(c, LUMAHIP_ERR_ARG, "distortion map: block must be 16, 32 or 64 (got %u)", block);
-    StagedPlanes given{"", planes, stride, profile};
-    const size_t nfl = (size_t)3 * w * h, words = dist_map_words(w, h, block);
+    const size_t nfl = (size_t)3 * w * h, words = map ? dist_map_words(w, h, block, dist_words_per_block(what)) : 12;
     int rc = planes_staging(c, w, h, nullptr, given, words);
     if (rc)
         return rc;
-    if (map_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "distortion map: %zu words for a map of %zu", map_words, words);
+    if (map && out_words < words)
+        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", name, out_words, words);
     if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
         (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
-        (rc = distortion_map_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), block,
+        (rc = measure_frames_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), what, block,
                                   reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
         return rc;
-    return words_down(c, map, words);
+    return words_down(c, out, words);
 }
 
-// ... -> the frame's moments map (lumahip_moments_map.hip): nbx * nby * 15 words, synchronously
-extern "C" int lumahip_moments_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
-                                              const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *mom,
-                                              size_t mom_words)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!rgb || !planes || !stride || !mom)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    if (!dist_block_ok(DistWhat::Moments, block))
-        return fail(c, LUMAHIP_ERR_ARG, "moments map: block must be 8, 16, 32 or 64 (got %u)", block);
-    StagedPlanes given{"", planes, stride, profile};
-    const size_t nfl = (size_t)3 * w * h, words = dist_map_words(w, h, block, dist_words_per_block(DistWhat::Moments));
-    int rc = planes_staging(c, w, h, nullptr, given, words);
-    if (rc)
-        return rc;
-    if (mom_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "moments map: %zu words for a map of %zu", mom_words, words);
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
-        (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
-        (rc = moments_map_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), block,
-                               reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
-        return rc;
-    return words_down(c, mom, words);
-}
-
-// Source planes and given planes in host memory -> the 12 words of the transcode distortion (lumahip_transcode_distortion.hip),
-// synchronously; the context's plane staging holds both sets
-extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
-                                                       int src_profile, float src_sc, unsigned w, unsigned h,
-                                                       const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
-                                                       float dst_sc, uint64_t out[12])
+// Source planes and given planes in host memory -> what a plane-fed measuring call delivers (lumahip_transcode.hip), synchronously:
+// the 12 words of the transcode distortion (Measure), or the frame's transcode distortion map of nbx * nby * 12 words (Map); the
+// context's plane staging holds both sets
+static int measure_planes_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile, float src_sc,
+                               unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
+                               float dst_sc, TransWhat what, unsigned block, uint64_t *out, size_t out_words)
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
     if (!src_planes || !src_stride || !given_planes || !given_stride || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    const bool map = what == TransWhat::Map;
+    if (map && !dist_map_block_ok(block))
+        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: block must be 16, 32 or 64 (got %u)", block);
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
-    int rc = planes_staging(c, w, h, &src, given, 12);
-    if (rc || (rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
-        (rc = transcode_distortion_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
+    const size_t words = map ? dist_map_words(w, h, block) : 12;
+    int rc = planes_staging(c, w, h, &src, given, words);
+    if (rc)
         return rc;
-    return words_down(c, out);
+    if (map && out_words < words)
+        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: %zu words for a map of %zu", out_words, words);
+    if ((rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
+        (rc = measure_planes_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, what, block, reinterpret_cast<uint64_t *>(c->d_arr),
+                                  {c->stream, false})))
+        return rc;
+    return words_down(c, out, words);
 }
 
-// ... -> the frame's transcode distortion map (lumahip_transcode_distortion_map.hip): nbx * nby * 12 words, synchronously
+extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                             const unsigned char *const planes[3], const int stride[3], uint64_t out[12])
+{
+    return measure_frame_host(c, rgb, w, h, sc, profile, planes, stride, DistWhat::Frame, 0, out, 12);
+}
+
+extern "C" int lumahip_distortion_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                                 const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *map,
+                                                 size_t map_words)
+{
+    return measure_frame_host(c, rgb, w, h, sc, profile, planes, stride, DistWhat::Map, block, map, map_words);
+}
+
+extern "C" int lumahip_moments_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
+                                              const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *mom,
+                                              size_t mom_words)
+{
+    return measure_frame_host(c, rgb, w, h, sc, profile, planes, stride, DistWhat::Moments, block, mom, mom_words);
+}
+
+extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                       int src_profile, float src_sc, unsigned w, unsigned h,
+                                                       const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
+                                                       float dst_sc, uint64_t out[12])
+{
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
+                               TransWhat::Measure, 0, out, 12);
+}
+
 extern "C" int lumahip_transcode_distortion_map_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
                                                            int src_profile, float src_sc, unsigned w, unsigned h,
                                                            const unsigned char *const given_planes[3], const int given_stride[3],
                                                            int dst_profile, float dst_sc, unsigned block, uint64_t *map, size_t map_words)
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!src_planes || !src_stride || !given_planes || !given_stride || !map)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    if (!dist_map_block_ok(block))
-        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: block must be 16, 32 or 64 (got %u)", block);
-    StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
-    const size_t words = dist_map_words(w, h, block);
-    int rc = planes_staging(c, w, h, &src, given, words);
-    if (rc)
-        return rc;
-    if (map_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: %zu words for a map of %zu", map_words, words);
-    if ((rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
-        (rc = transcode_distortion_map_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, block, reinterpret_cast<uint64_t *>(c->d_arr),
-                                            {c->stream, false})))
-        return rc;
-    return words_down(c, map, words);
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
+                               TransWhat::Map, block, map, map_words);
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the

@@ -14,15 +14,16 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
-//                       be, for this unit and the next two --, the transcode dispatch and its two entry points
-//   lumahip_transcode_distortion.hip  pick_planes<TransDistFamily, .> (every k_transcode_distortion), its dispatch and device entry point
-//   lumahip_transcode_distortion_map.hip  pick_planes<TransDistMapFamily, .> (every k_transcode_distortion_map), its dispatch and device entry point
-//   lumahip_distortion.hip / lumahip_distortion_f16.hip  pick_dist<DistFamily, false / true> (every k_distortion), distortion_plan -- what a launch that scores given
-//                       planes against frames may be, for these units and the next --, the distortion dispatch and the _device entry points
-//   lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip  pick_dist<DistMapFamily, .> (every k_distortion_map), the map's dispatch
-//                       and its _device entry points
-//   lumahip_moments_map.hip / lumahip_moments_map_f16.hip  pick_dist<MomentsMapFamily, .> (every k_moments_map), the moments map's
-//                       dispatch and its _device entry points
+//                       be --, the transcode dispatch and its entry point; measure_planes_impl, the one dispatch of the two plane-fed
+//                       measuring calls, and their two _device entry points
+//   lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip  pick_planes<TransDistFamily | TransDistMapFamily, .> (every
+//                       k_transcode_distortion / k_transcode_distortion_map), exported as pick_transdist / pick_transdist_map; nothing else
+//   lumahip_distortion.hip  pick_dist<DistFamily, false> (every float-frame k_distortion), distortion_plan -- what a launch that scores
+//                       given planes against frames may be --, measure_frames_impl, the one dispatch of the frame-fed measuring calls
+//                       (distortion, distortion map, moments map), their twelve _device entry points and the two *_map_dims
+//   lumahip_distortion_f16.hip, lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip / _f16.hip  pick_dist<DistFamily, true>,
+//                       pick_dist<DistMapFamily, .>, pick_dist<MomentsMapFamily, .> (the other frame-fed measuring kernels), exported
+//                       as pick_dist_f16, pick_dist_map_f32 / _f16, pick_moments_map_f32 / _f16; nothing else
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -540,16 +541,11 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 
-// ---- lumahip_distortion.hip / lumahip_distortion_f16.hip: pick_dist<DistFamily, false / true> of lumahip_pick.hpp (every
-// k_distortion; the binary16-frame ones compile side by side with the float ones and are exported as pick_dist_f16)
+// ---- lumahip_distortion.hip: the frame-fed measuring calls
 struct DistortionLaunch {
     hipStream_t stream;
     bool lanes = false;   // as EncodeLaunch::lanes
 };
-// the frames of f under the context's quantizer and sc against the given planes: 12 words per frame at out_dev
-int distortion_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, uint64_t *out_dev, const DistortionLaunch &o);
-typedef void (*dist_kernel_t)(const lh::DistArgs);
-dist_kernel_t pick_dist_f16(int cs, bool sub, int vw, int mode);
 // What distortion_plan decides for a launch that scores given planes against the frames' encode: the kernel's key as pick_dist
 // takes it, the launch shape and the kernel arguments of both sides
 struct DistortionPlan {
@@ -577,12 +573,6 @@ static inline size_t dist_map_words(unsigned w, unsigned h, unsigned block, int 
 int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, DistWhat what, unsigned map_block,
                     hipStream_t stream, DistortionPlan &p);
 
-// ---- lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip: pick_dist<DistMapFamily, false / true> of lumahip_pick.hpp (every
-// k_distortion_map; the binary16-frame ones are exported as pick_dist_map_f16)
-// the same comparison per block x block luma pixels: nframes * nby * nbx * 12 words at map_dev, every one written by the launch
-int distortion_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *map_dev, const DistortionLaunch &o);
-typedef void (*dist_map_kernel_t)(const lh::DistMapArgs);
-dist_map_kernel_t pick_dist_map_f16(int cs, bool sub, int vw, int mode);
 // what the map kernels' helpers read beside g, the launch's frame-major geometry; threads = its workgroup, a power of two of at most 32 * block
 static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsigned h, unsigned block, int threads)
 {
@@ -596,24 +586,31 @@ static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsi
     return m;
 }
 
-// ---- lumahip_moments_map.hip / lumahip_moments_map_f16.hip: pick_dist<MomentsMapFamily, false / true> of lumahip_pick.hpp (every
-// k_moments_map; the binary16-frame ones are exported as pick_moments_map_f16)
-// the five moment sums per plane and block x block luma pixels: nframes * nby * nbx * 15 words at mom_dev, every one written by the launch
-int moments_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *mom_dev, const DistortionLaunch &o);
-typedef void (*moments_map_kernel_t)(const lh::MomentsMapArgs);
-moments_map_kernel_t pick_moments_map_f16(int cs, bool sub, int vw, int mode);
+// The one dispatch of the frame-fed measuring calls: the frames of f under the context's quantizer and sc against the given planes.
+// Frame: 12 words per frame at out (zeroed in front of the launch; block ignored); Map / Moments: nframes * nby * nbx * 12 / 15 words,
+// every one written by the launch
+int measure_frames_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, DistWhat what, unsigned block, uint64_t *out,
+                        const DistortionLaunch &o);
+// pick_dist<Family, IN16> of lumahip_pick.hpp as the six kernel units export it (each compiles the kernels it names, side by side with
+// the others): lumahip_distortion.hip / _f16.hip, lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip / _f16.hip
+typedef void (*dist_kernel_t)(const lh::DistArgs);
+typedef void (*map_kernel_t)(const lh::MapArgs);
+dist_kernel_t pick_dist_f32(int cs, bool sub, int vw, int mode), pick_dist_f16(int cs, bool sub, int vw, int mode);
+map_kernel_t pick_dist_map_f32(int cs, bool sub, int vw, int mode), pick_dist_map_f16(int cs, bool sub, int vw, int mode);
+map_kernel_t pick_moments_map_f32(int cs, bool sub, int vw, int mode), pick_moments_map_f16(int cs, bool sub, int vw, int mode);
 
-// ---- lumahip_transcode_distortion.hip: pick_planes<TransDistFamily, .> of lumahip_pick.hpp (every k_transcode_distortion)
-// the source planes' transcode (transcode_impl's planes, never written) against the given planes: 12 words per frame at out_dev
-int transcode_distortion_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
-                              float dst_sc, uint64_t *out_dev, const TranscodeLaunch &o);
+// ---- lumahip_transcode.hip: the plane-fed measuring calls
+// The one dispatch of both: the source planes' transcode (transcode_impl's planes, never written) against the given planes.
+// what: Measure -- 12 words per frame at out (zeroed in front of the launch; block ignored) -- or Map -- nframes * nby * nbx * 12 words,
+// every one written by the launch
+int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
+                        float dst_sc, TransWhat what, unsigned block, uint64_t *out, const TranscodeLaunch &o);
+// pick_planes<TransDistFamily | TransDistMapFamily, vw> of lumahip_pick.hpp as lumahip_transcode_distortion.hip /
+// lumahip_transcode_distortion_map.hip export it (each compiles the 48 kernels it names)
 typedef void (*transdist_kernel_t)(const lh::TransDistArgs);
-
-// ---- lumahip_transcode_distortion_map.hip: pick_planes<TransDistMapFamily, .> of lumahip_pick.hpp (every k_transcode_distortion_map)
-// the same comparison per block x block luma pixels: nframes * nby * nbx * 12 words at map_dev, every one written by the launch
-int transcode_distortion_map_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
-                                  float dst_sc, unsigned block, uint64_t *map_dev, const TranscodeLaunch &o);
 typedef void (*transdist_map_kernel_t)(const lh::TransDistMapArgs);
+transdist_kernel_t pick_transdist(int vw, int csd, bool subd, int cse, bool sube, int mode);
+transdist_map_kernel_t pick_transdist_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

@@ -1,67 +1,12 @@
-// lumahip_moments_map.hip -- dispatch of the moments map kernels (lh::k_moments_map, luma_kernels.hpp): per block of 8, 16, 32 or 64
+// lumahip_moments_map.hip -- the float-frame moments map kernels (lh::k_moments_map, luma_kernels.hpp): per block of 8, 16, 32 or 64
 // luma pixels squared and per plane the five sums a structural-similarity index needs of the frames' codes e and the given samples g
-// -- sum e, sum g, sum e^2, sum g^2, sum e g --, every word of the map written once by one launch.  Its own translation unit (float
-// frames; lumahip_moments_map_f16.hip holds the binary16-frame kernels): the kernels compile side by side with the other units', and
-// no kernel is in two code objects.
+// -- sum e, sum g, sum e^2, sum g^2, sum e g --, every word of the map written once by one launch.  Named here and nowhere else: their
+// own translation unit (lumahip_moments_map_f16.hip holds the binary16-frame kernels), so that they compile side by side with the
+// other units' and no kernel is in two code objects.  The dispatch (measure_frames_impl) and the entry points are
+// lumahip_distortion.hip's.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
-using namespace lh;
-using namespace lhost;
-
 namespace lhost {
-
-int moments_map_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, unsigned block, uint64_t *mom, const DistortionLaunch &o)
-{
-    DistortionPlan p;
-    if (int rc = distortion_plan(c, f, sc, given, mom, DistWhat::Moments, block, o.stream, p))
-        return rc;
-    MomentsMapArgs a{};
-    a.e = p.e;
-    a.g = p.g;
-    a.map = mom;
-    a.m = make_map_geom(p.e.g, f.w, f.h, block, p.threads);   // (S >= 1: distortion_plan has clamped the workgroup)
-    const moments_map_kernel_t kern =
-        p.in16 ? pick_moments_map_f16(p.cs, p.sub, p.vw, p.kmode) : pick_dist<MomentsMapFamily, false>(p.cs, p.sub, p.vw, p.kmode);
-    if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no moments map kernel for colour space %d%s", p.cs, p.in16 ? " with binary16 frames" : "");
-    // grid_for's encode rule over the standard tiles; a workgroup takes whole map tiles
-    const int grid = p.grid < a.m.totalMapTiles ? p.grid : a.m.totalMapTiles;
-    if (int rc = launch_fused(c, kern, grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
-        return rc;
-    HIPCHK(c, hipGetLastError());
-    return LUMAHIP_OK;
-}
-
+map_kernel_t pick_moments_map_f32(int cs, bool sub, int vw, int mode) { return pick_dist<MomentsMapFamily, false>(cs, sub, vw, mode); }
 }  // namespace lhost
-
-extern "C" int lumahip_moments_map_dims(unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby)
-{
-    if (!dist_block_ok(DistWhat::Moments, block) || !nbx || !nby)
-        return LUMAHIP_ERR_ARG;
-    *nbx = (w + block - 1) / block;
-    *nby = (h + block - 1) / block;
-    return LUMAHIP_OK;
-}
-
-extern "C" int lumahip_moments_map_frames_device(lumahip_ctx *c, const float *rgb, size_t frame_stride, unsigned nframes, unsigned w, unsigned h,
-                                                 float sc, int profile, const unsigned char *const planes[3], const int stride[3],
-                                                 const size_t pfs[3], unsigned block, uint64_t *mom_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!rgb)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return moments_map_impl(c, packed_frames(rgb, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, block, mom_dev,
-                            {c->stream, true});
-}
-
-extern "C" int lumahip_moments_map_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], size_t frame_stride, unsigned nframes,
-                                                        unsigned w, unsigned h, float sc, int profile, const unsigned char *const planes[3],
-                                                        const int stride[3], const size_t pfs[3], unsigned block, uint64_t *mom_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    return moments_map_impl(c, planar_frames(rgb_planes, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, block, mom_dev,
-                            {c->stream, true});
-}

@@ -3,12 +3,13 @@
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
-// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_planes<TransFamily, 4 | 2>;
-// lumahip_transcode_distortion.hip takes pick_planes<TransDistFamily, 4 | 2>; lumahip_transcode_distortion_map.hip takes
-// pick_planes<TransDistMapFamily, 4 | 2>; lumahip_distortion.hip /
-// lumahip_distortion_f16.hip take pick_dist<DistFamily, false / true>; lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip
-// take pick_dist<DistMapFamily, false / true>; lumahip_moments_map.hip / lumahip_moments_map_f16.hip take
-// pick_dist<MomentsMapFamily, false / true>.  Included by those thirteen units only.
+// export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_planes<TransFamily, 4 | 2>.  The eight measuring
+// units take one picker each and export it to the two dispatch functions (measure_planes_impl, measure_frames_impl):
+// lumahip_transcode_distortion.hip pick_planes<TransDistFamily, 4 | 2> as pick_transdist; lumahip_transcode_distortion_map.hip
+// pick_planes<TransDistMapFamily, 4 | 2> as pick_transdist_map; lumahip_distortion.hip / lumahip_distortion_f16.hip
+// pick_dist<DistFamily, false / true> as pick_dist_f32 / _f16; lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip
+// pick_dist<DistMapFamily, false / true> as pick_dist_map_f32 / _f16; lumahip_moments_map.hip / lumahip_moments_map_f16.hip
+// pick_dist<MomentsMapFamily, false / true> as pick_moments_map_f32 / _f16.  Included by those thirteen units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -160,12 +161,12 @@ struct DistFamily {
     static kernel_t kernel() { return lh::k_distortion<CS, SUB, VW, LM, IN16>; }
 };
 struct DistMapFamily {
-    using kernel_t = dist_map_kernel_t;
+    using kernel_t = map_kernel_t;
     template <int CS, bool SUB, int VW, int LM, bool IN16>
     static kernel_t kernel() { return lh::k_distortion_map<CS, SUB, VW, LM, IN16>; }
 };
 struct MomentsMapFamily {   // (launch bound: lh::moments_threads_bound, which distortion_plan clamps the launch to)
-    using kernel_t = moments_map_kernel_t;
+    using kernel_t = map_kernel_t;
     template <int CS, bool SUB, int VW, int LM, bool IN16>
     static kernel_t kernel() { return lh::k_moments_map<CS, SUB, VW, LM, IN16>; }
 };

@@ -1,6 +1,8 @@
 // lumahip_transcode.hip -- dispatch of the fused transcode kernels (lh::k_transcode, luma_kernels.hpp): code planes under the
 // context's source quantizer -> code planes under its quantizer, no float frame between them.  Its own translation unit: the 48
-// kernels compile side by side with the encode and decode units, and no kernel is in two code objects.
+// kernels compile side by side with the encode and decode units, and no kernel is in two code objects.  Also the plan of every
+// launch over two plane sets (transcode_plan) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the two
+// measuring calls over them, whose kernels lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip compile.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
@@ -157,6 +159,50 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     return LUMAHIP_OK;
 }
 
+int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
+                        float dst_sc, TransWhat what, unsigned block, uint64_t *out, const TranscodeLaunch &o)
+{
+    TranscodePlan p;
+    if (int rc = transcode_plan(c, src, src_sc, nframes, w, h, given, dst_sc, what, out, block, o.stream, p))
+        return rc;
+    DecArgs g{};
+    g.g = p.d.g;
+    read_planes(g, given, p.vw);
+    if (what != TransWhat::Map) {
+        TransDistArgs a{};
+        a.d = p.d;
+        a.e = p.e;
+        a.g = g;
+        a.out = out;
+        const transdist_kernel_t kern = pick_transdist(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
+        if (!kern)
+            return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode distortion kernel for colour spaces %d -> %d", p.csd, p.cse);
+        return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, nframes);
+    }
+    TransDistMapArgs a{};
+    a.d = p.d;
+    a.e = p.e;
+    a.g = g;
+    a.map = out;
+    a.m = p.m;
+    const transdist_map_kernel_t kern = pick_transdist_map(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
+    if (!kern)
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode distortion map kernel for colour spaces %d -> %d", p.csd, p.cse);
+    if (int rc = launch_fused(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
+        return rc;
+    HIPCHK(c, hipGetLastError());
+    return LUMAHIP_OK;
+}
+
+// what both plane-fed measuring _device entry points do in front of the dispatch
+static int measure_planes_entry(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
+                                float dst_sc, TransWhat what, unsigned block, uint64_t *out)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    return measure_planes_impl(c, src, src_sc, nframes, w, h, given, dst_sc, what, block, out, {c->stream, true});
+}
+
 // channel 0 of the decoded and colour-transformed frame (one frame, planes without a frame stride) into out_dev, w*h floats
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s)
 {
@@ -198,3 +244,16 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
     return transcode_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, nframes, w, h, {dst_planes, dst_stride, dst_pfs, dst_profile}, dst_sc,
                           stats, {c->stream, true});
 }
+
+// The two plane-fed measuring entry points (include/lumahip.h has their full prototypes): MEASURE_PARAMS, then the call's own tail.
+#define MEASURE_PARAMS                                                                                                                      \
+    const unsigned char *const src_planes[3], const int src_stride[3], const size_t src_pfs[3], int src_profile, float src_sc, unsigned nframes, \
+        unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], const size_t given_pfs[3], int dst_profile, \
+        float dst_sc
+#define MEASURE(what, block, out)                                                                                                                \
+    measure_planes_entry(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, nframes, w, h, {given_planes, given_stride, given_pfs, dst_profile}, \
+                         dst_sc, TransWhat::what, block, out)
+extern "C" {
+int lumahip_transcode_distortion_frames_device(lumahip_ctx *c, MEASURE_PARAMS, uint64_t *out_dev) { return MEASURE(Measure, 0, out_dev); }
+int lumahip_transcode_distortion_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return MEASURE(Map, block, map_dev); }
+}  // extern "C"

@@ -1,49 +1,14 @@
-// lumahip_transcode_distortion_map.hip -- dispatch of the transcode distortion map kernels (lh::k_transcode_distortion_map,
-// luma_kernels.hpp): what lumahip_transcode_distortion_frames_device sums per frame, per block of 16, 32 or 64 luma pixels squared,
-// every word of the map written once by one launch.  What the launch may be and how it runs is transcode_plan's decision
-// (lumahip_transcode.hip), shared with the transcode call and the transcode distortion.  Its own translation unit: the 48 kernels
-// compile side by side with the other units, and no kernel is in two code objects.
+// lumahip_transcode_distortion_map.hip -- the transcode distortion map kernels (lh::k_transcode_distortion_map, luma_kernels.hpp):
+// what lumahip_transcode_distortion_frames_device sums per frame, per block of 16, 32 or 64 luma pixels squared, every word of the
+// map written once by one launch.  Named here and nowhere else: their own translation unit, so that the 48 kernels compile side by
+// side with the other units and no kernel is in two code objects.  What a launch may be (transcode_plan), the dispatch
+// (measure_planes_impl) and the entry point are lumahip_transcode.hip's.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
-using namespace lh;
-using namespace lhost;
-
 namespace lhost {
-
-int transcode_distortion_map_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
-                                  float dst_sc, unsigned block, uint64_t *map, const TranscodeLaunch &o)
+transdist_map_kernel_t pick_transdist_map(int vw, int csd, bool subd, int cse, bool sube, int mode)
 {
-    TranscodePlan p;
-    if (int rc = transcode_plan(c, src, src_sc, nframes, w, h, given, dst_sc, TransWhat::Map, map, block, o.stream, p))
-        return rc;
-    TransDistMapArgs a{};
-    a.d = p.d;
-    a.e = p.e;
-    a.g.g = p.d.g;
-    read_planes(a.g, given, p.vw);
-    a.map = map;
-    a.m = p.m;
-    const transdist_map_kernel_t kern = p.vw == 4 ? pick_planes<TransDistMapFamily, 4>(p.csd, p.subd, p.cse, p.sube, p.kmode)
-                                                  : pick_planes<TransDistMapFamily, 2>(p.csd, p.subd, p.cse, p.sube, p.kmode);
-    if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode distortion map kernel for colour spaces %d -> %d", p.csd, p.cse);
-    if (int rc = launch_fused(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
-        return rc;
-    HIPCHK(c, hipGetLastError());
-    return LUMAHIP_OK;
+    return vw == 4 ? pick_planes<TransDistMapFamily, 4>(csd, subd, cse, sube, mode) : pick_planes<TransDistMapFamily, 2>(csd, subd, cse, sube, mode);
 }
-
 }  // namespace lhost
-
-extern "C" int lumahip_transcode_distortion_map_frames_device(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
-                                                              const size_t src_pfs[3], int src_profile, float src_sc, unsigned nframes, unsigned w,
-                                                              unsigned h, const unsigned char *const given_planes[3], const int given_stride[3],
-                                                              const size_t given_pfs[3], int dst_profile, float dst_sc, unsigned block,
-                                                              uint64_t *map_dev)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    return transcode_distortion_map_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, nframes, w, h,
-                                         {given_planes, given_stride, given_pfs, dst_profile}, dst_sc, block, map_dev, {c->stream, true});
-}

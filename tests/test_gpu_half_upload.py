@@ -134,8 +134,6 @@ def test_batched_and_streaming_entry_points(oracle_mod, name):
         c._chk(c.L.lumahip_encode_stream_push(c.h, scratch.ctypes.data_as(C.c_void_p), w, h, C.c_float(sc), 2, pp, sa))
         scratch[...] = -1.0
 
-    c.L.lumahip_encode_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_float, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
-    c.L.lumahip_encode_stream_pop.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     m = C.c_float(0)
     push(0)
     for i in range(1, 5):
