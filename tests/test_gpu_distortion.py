@@ -8,6 +8,7 @@ against GIVEN planes.  Every expectation is exact equality of all twelve integer
    (258,6) (64,32) (6,4) x 3 frames x preScalings {1, 20, 0.01}; sentinel bytes in every gap; the planar and binary16 forms.
 3. Accumulator width (one wave carries more than 2^32).  4. Persistent loop and frame change (2 workgroups of 64 threads).
 5. Unordered section, one 1280x720 frame, repeatability, inputs untouched.  6. The host form.  7. Errors: nothing is launched.
+Every k_distortion instantiation, against the oracle's planes: tests/test_gpu_measuring_kernels.py test_measuring_matrix[distortion-*].
 """
 import os
 

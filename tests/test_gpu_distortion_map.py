@@ -11,6 +11,7 @@ words behind it, which must survive.
 3. The map folds to lumahip_distortion_frames_device's words (in every case of 2).   4. One block's sse beyond 2^32.
 5. Launch shapes: 2 workgroups of 64 threads, 1024 threads asked for, the default.   6. A 720p frame twice and in an unordered section.
 7. The host form.   8. Errors: nothing is launched.
+Every k_distortion_map instantiation, against the oracle's planes: tests/test_gpu_measuring_kernels.py test_measuring_matrix[distortion_map-*].
 """
 import ctypes as C
 import os

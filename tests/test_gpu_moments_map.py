@@ -11,6 +11,7 @@ buffer holds the 0xC3 pattern with 16 guard words behind it, which must survive.
 3. The planar and binary16 forms.   4. Sums beyond 2^32, and the 2-lane meeting on the same frame.
 5. Launch shapes: 2 workgroups of 64 threads, 1024 threads asked for, the default.   6. A 720p frame twice and in an unordered section.
 7. The host form.   8. Errors: nothing is launched.
+Every k_moments_map instantiation, against the oracle's planes: tests/test_gpu_measuring_kernels.py test_measuring_matrix[moments_map-*].
 """
 import ctypes as C
 import os
