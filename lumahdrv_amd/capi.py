@@ -177,6 +177,14 @@ _ABI = {
 }
 SYMBOLS = tuple(_ABI)
 
+# The calls include/lumahip_measure.h declares (measuring calls added after lumahip.h's list was closed), bound like _ABI's:
+# tests/test_transcode_moments_map_host.py holds this table against that header.
+_ABI_MEASURE = {
+    "lumahip_transcode_moments_map_frames_device": (_i, _TWO_SETS + (_u, _vp)),
+    "lumahip_transcode_moments_map_frame_host": (_i, _TWO_SETS_HOST + (_u, _vp, _sz)),
+}
+MEASURE_SYMBOLS = tuple(_ABI_MEASURE)
+
 
 class LumaHipError(RuntimeError):
     """Counterpart of the reference's LumaException (include/luma/luma_exception.h:53-71)."""
@@ -209,7 +217,8 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_decode.hip", "lumahip_misc.hip", "lut_index.cpp", "lut_index.hpp", "flags.mk", "f16_narrow.hpp",
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
-                  "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip")
+                  "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip",
+                  "lumahip_transcode_moments_map.hip")
 
 
 def kernel_source_sha() -> str:
@@ -242,7 +251,7 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (restype, argtypes) in _ABI.items():
+    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
@@ -542,13 +551,13 @@ class Context:
         return self._measured(fn, args, w, h, words, dims, block)
 
     def _measure_planes(self, fn, planes, strides, w, h, given_planes, given_strides, src_sc, src_profile, dst_sc, dst_profile, dims=None,
-                        block=None):
+                        block=None, words=4):
         """the plane-fed measuring host forms"""
         planes = [np.ascontiguousarray(p) for p in planes]
         given_planes = [np.ascontiguousarray(p) for p in given_planes]
         args = (_arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
                 _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc)
-        return self._measured(fn, args, w, h, 4, dims, block)
+        return self._measured(fn, args, w, h, words, dims, block)
 
     # ---- configuration
     def set_stream(self, hip_stream: int | None):
@@ -674,6 +683,14 @@ class Context:
         (nby, nbx, 3, 4) uint64 array, in one launch; block_sample_counts(w, h, dst_profile, block) gives the samples behind each entry"""
         return self._measure_planes(self.L.lumahip_transcode_distortion_map_frame_host, planes, strides, w, h, given_planes, given_strides,
                                     src_sc, src_profile, dst_sc, dst_profile, distortion_map_dims, block)
+
+    def transcode_moments_map_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
+                                    dst_profile=2, block=8) -> np.ndarray:
+        """moments_map_frame's five sums per block of block x block luma pixels (8, 16, 32 or 64) of the target, with e the codes
+        transcode_frame would write for the source planes: a (nby, nbx, 3, 5) uint64 array, in one launch.  moments_map_dims,
+        moments_sample_counts(w, h, dst_profile, block) and code_ssim apply unchanged"""
+        return self._measure_planes(self.L.lumahip_transcode_moments_map_frame_host, planes, strides, w, h, given_planes, given_strides,
+                                    src_sc, src_profile, dst_sc, dst_profile, moments_map_dims, block, words=5)
 
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
@@ -853,6 +870,16 @@ class Context:
         self._two_sets(self.L.lumahip_transcode_distortion_map_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
                        src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
                        block, map_ptr)
+
+    # the moments of the source planes' transcode and the given planes per block x block luma pixels of the target (8, 16, 32 or 64):
+    # mom_ptr receives nframes x nby x nbx x 3 planes x {Se, Sg, See, Sgg, Seg} as uint64, every word written by the launch
+    # (moments_map_dims, moments_sample_counts(w, h, dst_profile, block) and code_ssim apply unchanged)
+    def transcode_moments_map_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
+                                            given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, block,
+                                            mom_ptr):
+        self._two_sets(self.L.lumahip_transcode_moments_map_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
+                       src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
+                       block, mom_ptr)
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

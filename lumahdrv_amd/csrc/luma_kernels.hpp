@@ -644,7 +644,7 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
 // block only (MomentBlockAcc, the same dist_map_flush):
 //                                                        store (EncStoreUnit)   measure (DistMeasureUnit)   ... per block                 moments per block (MomentMeasureUnit)
 //   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion                k_distortion_map              k_moments_map
-//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion      k_transcode_distortion_map    (not built yet)
+//   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion      k_transcode_distortion_map    k_transcode_moments_map
 //                   enc_transform
 // A kernel is its front end, its consumer and the persistent loop that orders their loads against each other; the loops differ on
 // purpose (stores before the next loads / the given words travelling along, one flush site) and stay written out.  Also written
@@ -2146,6 +2146,85 @@ __global__ __launch_bounds__((TransDistBound<CSD, CSE>::value)) void k_transcode
             float c0[2 * VW], c1[2 * VW], c2[2 * VW];
             enc_transform<CSE, VW, Front::YE, false, false>(u, a.e, ke, c0, c1, c2, st);
             const DistMeasureUnit<SUBE, VW, DistBlockAcc> out{given, a.g, acc, mask};
+            enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+        }
+        const bool last = s + 1 == a.m.S;
+        const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
+        const int t = map_subtile(a.m, a.d.g, mn, sn);
+        dec_load<SUBD, VW>(nxt, a.d, t, tx, ty, NW);
+        dec_issue<SUBE, VW>(given, a.g, t, tx, ty, NW);
+        if (last) {
+            dist_map_flush<VW>(acc, s_map, a.m, a.d.g, a.map, m, tx);
+            acc.reset();
+        }
+        cur = nxt;
+        m = mn;
+        s = sn;
+    }
+}
+
+// ---- TRANSCODE MOMENTS MAP --------------------------------------------------------------------------
+// k_moments_map's five sums per plane for every B x B block of luma pixels of the TARGET (B = 8, 16, 32 or 64), e what k_transcode
+// would store for the source planes and g the given sample: k_transcode_distortion_map with the consumer (MomentMeasureUnit) and
+// the record (MomentBlockAcc) changed, everything else as written out there -- argument struct included (TransDistMapArgs; map:
+// 15 words per block).  Reads 3 + 3 B per pixel (profile 2 on both sides), writes 120 B per block; no float frame, no scratch
+// planes, no global atomic, no memset.
+// Register budget (profiles/transcode_moments_map_codegen.txt has the compiler's table): the record is 24 registers against
+// DistBlockAcc's 15.  The Lu'v' -> Lu'v' kernels at VW 4 sit at 120 - 128 registers in k_transcode_distortion_map, some with scratch
+// already: they are allocated for three waves per SIMD (168 registers) in workgroups of at most 512 threads, as the moments_wide
+// kernels of k_moments_map.  The Lu'v' -> Lu'v' kernels at VW 2 keep 1024 threads and four waves (128 registers), the pairs with YCbCr
+// TransDistBound's 512 threads, which leaves them two waves per SIMD (256 registers).  transcode_plan clamps the launch to
+// transmoments_threads_bound: a launch never exceeds what its kernel was compiled for.
+constexpr bool transmoments_any_y(int csd, int cse) { return csd == CS_YCBCR || cse == CS_YCBCR; }
+constexpr int transmoments_threads_bound(int csd, int cse, int vw) { return (transmoments_any_y(csd, cse) || vw == 4) ? 512 : 1024; }
+constexpr int transmoments_waves(int csd, int cse, int vw) { return transmoments_any_y(csd, cse) ? 2 : vw == 4 ? 3 : 4; }
+
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__(transmoments_threads_bound(CSD, CSE, VW)) __attribute__((amdgpu_waves_per_eu(transmoments_waves(CSD, CSE, VW))))
+void k_transcode_moments_map(const TransDistMapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *const s_map = dist_map_words<MomentBlockAcc>();
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    MomentBlockAcc acc;
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    DecUnit<SUBD, VW> cur, nxt;
+    DecRaw<SUBE, VW> given;
+    int m = blockIdx.x, s = 0;
+    {
+        const int t = map_subtile(a.m, a.d.g, m, 0);
+        dec_load<SUBD, VW>(cur, a.d, t, tx, ty, NW);
+        dec_issue<SUBE, VW>(given, a.g, t, tx, ty, NW);
+    }
+    while (m < a.m.totalMapTiles) {   // workgroup-uniform
+        if (cur.valid) {
+            EncUnit<VW> u;
+            if constexpr (Front::YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    dec_values<CSD, SUBD, VW, false, true, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+                else
+                    dec_values<CSD, SUBD, VW, false, true, false>(cur, a.d, kd, s_lut, s_uv, u.in);
+            } else {
+                dec_values<CSD, SUBD, VW, true>(cur, a.d, kd, s_lut, s_uv, u.in);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, Front::YE, false, false>(u, a.e, ke, c0, c1, c2, st);
+            const MomentMeasureUnit<SUBE, VW> out{given, a.g, acc, mask};
             enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
         }
         const bool last = s + 1 == a.m.S;

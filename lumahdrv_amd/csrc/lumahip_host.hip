@@ -1138,8 +1138,8 @@ static int measure_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsi
 }
 
 // Source planes and given planes in host memory -> what a plane-fed measuring call delivers (lumahip_transcode.hip), synchronously:
-// the 12 words of the transcode distortion (Measure), or the frame's transcode distortion map of nbx * nby * 12 words (Map); the
-// context's plane staging holds both sets
+// the 12 words of the transcode distortion (Measure), or the frame's transcode distortion / moments map of nbx * nby * 12 / 15 words
+// (Map / Moments); the context's plane staging holds both sets
 static int measure_planes_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile, float src_sc,
                                unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
                                float dst_sc, TransWhat what, unsigned block, uint64_t *out, size_t out_words)
@@ -1148,16 +1148,18 @@ static int measure_planes_host(lumahip_ctx *c, const unsigned char *const src_pl
         return LUMAHIP_ERR_ARG;
     if (!src_planes || !src_stride || !given_planes || !given_stride || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const bool map = what == TransWhat::Map;
-    if (map && !dist_map_block_ok(block))
-        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: block must be 16, 32 or 64 (got %u)", block);
+    const bool map = trans_is_map(what), moments = what == TransWhat::Moments;
+    const DistWhat kind = moments ? DistWhat::Moments : DistWhat::Map;   // (of a map mode)
+    const char *const name = moments ? "transcode moments map" : "transcode distortion map";
+    if (map && !dist_block_ok(kind, block))
+        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", name, moments ? "8, " : "", block);
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
-    const size_t words = map ? dist_map_words(w, h, block) : 12;
+    const size_t words = map ? dist_map_words(w, h, block, dist_words_per_block(kind)) : 12;
     int rc = planes_staging(c, w, h, &src, given, words);
     if (rc)
         return rc;
     if (map && out_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "transcode distortion map: %zu words for a map of %zu", out_words, words);
+        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", name, out_words, words);
     if ((rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
         (rc = measure_planes_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, what, block, reinterpret_cast<uint64_t *>(c->d_arr),
                                   {c->stream, false})))
@@ -1201,6 +1203,15 @@ extern "C" int lumahip_transcode_distortion_map_frame_host(lumahip_ctx *c, const
 {
     return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
                                TransWhat::Map, block, map, map_words);
+}
+
+extern "C" int lumahip_transcode_moments_map_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                        int src_profile, float src_sc, unsigned w, unsigned h,
+                                                        const unsigned char *const given_planes[3], const int given_stride[3],
+                                                        int dst_profile, float dst_sc, unsigned block, uint64_t *mom, size_t mom_words)
+{
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
+                               TransWhat::Moments, block, mom, mom_words);
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the

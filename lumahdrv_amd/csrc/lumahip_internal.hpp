@@ -6,7 +6,8 @@
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which instantiation of the fused kernels a launch takes: pick_enc<IN16> / pick_dec<OUT16> / pick_dist<IN16> /
-//                       pick_planes<TransFamily | TransDistFamily | TransDistMapFamily, VW>, included by the kernel units below and by nothing else
+//                       pick_planes<TransFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, VW>, included by the
+//                       kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
 //                       tables next to the kernel that builds them
@@ -14,10 +15,12 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
-//                       be --, the transcode dispatch and its entry point; measure_planes_impl, the one dispatch of the two plane-fed
-//                       measuring calls, and their two _device entry points
-//   lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip  pick_planes<TransDistFamily | TransDistMapFamily, .> (every
-//                       k_transcode_distortion / k_transcode_distortion_map), exported as pick_transdist / pick_transdist_map; nothing else
+//                       be --, the transcode dispatch and its entry point; measure_planes_impl, the one dispatch of the three plane-fed
+//                       measuring calls, and their three _device entry points
+//   lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip  pick_planes<
+//                       TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, .> (every k_transcode_distortion /
+//                       k_transcode_distortion_map / k_transcode_moments_map), exported as pick_transdist / pick_transdist_map /
+//                       pick_transdist_moments_map; nothing else
 //   lumahip_distortion.hip  pick_dist<DistFamily, false> (every float-frame k_distortion), distortion_plan -- what a launch that scores
 //                       given planes against frames may be --, measure_frames_impl, the one dispatch of the frame-fed measuring calls
 //                       (distortion, distortion map, moments map), their twelve _device entry points and the two *_map_dims
@@ -45,6 +48,7 @@
 
 #define LUMAHIP_EXPERIMENTAL   /* the library defines what the experimental section of the header declares */
 #include "../../include/lumahip.h"
+#include "../../include/lumahip_measure.h"
 #include "luma_kernels.hpp"
 #include "host_lut.hpp"
 #include "lut_index.hpp"
@@ -526,16 +530,20 @@ struct TranscodePlan {
     size_t lds;      // dynamic LDS of the launch (the measuring kernels' words are static and counted in the budget)
     lh::DecArgs d;   // q, g, src, stride, src_frame_stride, sc, bps, aligned of the source planes
     lh::EncArgs e;   // q (the composite records for kmode 5), g, sc, bps, aligned of the target side
-    lh::MapGeom m;   // TransWhat::Map only
+    lh::MapGeom m;   // TransWhat::Map / Moments only
 };
-enum class TransWhat { Store, Measure, Map };
+enum class TransWhat { Store, Measure, Map, Moments };
+static inline bool trans_is_map(TransWhat what) { return what == TransWhat::Map || what == TransWhat::Moments; }
 // Store: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one), out is ignored;
 // Measure: tgt are the given planes of lumahip_transcode_distortion_frames_device (read only: any overlap with the source
 // is fine), out its 12 * nframes words (non-null, 8-byte aligned, sharing no byte with either plane set), the workgroup is
 // clamped to the measuring kernels' launch bound;
 // Map: as Measure with out = the map of lumahip_transcode_distortion_map_frames_device (its own byte count is what may not
 // overlap), map_block 16, 32 or 64, lh::DIST_MAP_LDS_WORDS of LDS to meet in, the workgroup clamped further to 32 * map_block
-// threads and the grid to the number of map tiles.  Every error is raised here, before anything of the launch is queued.
+// threads and the grid to the number of map tiles;
+// Moments: as Map with out = the map of lumahip_transcode_moments_map_frames_device -- map_block 8, 16, 32 or 64, 15 words per block,
+// lh::MOMENTS_MAP_LDS_WORDS of LDS, the workgroup clamped to its kernels' launch bound (lh::transmoments_threads_bound) in the place
+// of the measuring kernels'.  Every error is raised here, the block size first, before anything of the launch is queued.
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
                    TransWhat mode, const uint64_t *out, unsigned map_block, hipStream_t stream, TranscodePlan &p);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
@@ -601,16 +609,17 @@ map_kernel_t pick_moments_map_f32(int cs, bool sub, int vw, int mode), pick_mome
 
 // ---- lumahip_transcode.hip: the plane-fed measuring calls
 // The one dispatch of both: the source planes' transcode (transcode_impl's planes, never written) against the given planes.
-// what: Measure -- 12 words per frame at out (zeroed in front of the launch; block ignored) -- or Map -- nframes * nby * nbx * 12 words,
-// every one written by the launch
+// what: Measure -- 12 words per frame at out (zeroed in front of the launch; block ignored) -- or Map / Moments -- nframes * nby * nbx *
+// 12 / 15 words, every one written by the launch
 int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
                         float dst_sc, TransWhat what, unsigned block, uint64_t *out, const TranscodeLaunch &o);
-// pick_planes<TransDistFamily | TransDistMapFamily, vw> of lumahip_pick.hpp as lumahip_transcode_distortion.hip /
-// lumahip_transcode_distortion_map.hip export it (each compiles the 48 kernels it names)
+// pick_planes<TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, vw> of lumahip_pick.hpp as lumahip_transcode_distortion.hip /
+// lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip export it (each compiles the 48 kernels it names)
 typedef void (*transdist_kernel_t)(const lh::TransDistArgs);
 typedef void (*transdist_map_kernel_t)(const lh::TransDistMapArgs);
 transdist_kernel_t pick_transdist(int vw, int csd, bool subd, int cse, bool sube, int mode);
 transdist_map_kernel_t pick_transdist_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
+transdist_map_kernel_t pick_transdist_moments_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

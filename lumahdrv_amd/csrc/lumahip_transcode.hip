@@ -1,8 +1,9 @@
 // lumahip_transcode.hip -- dispatch of the fused transcode kernels (lh::k_transcode, luma_kernels.hpp): code planes under the
 // context's source quantizer -> code planes under its quantizer, no float frame between them.  Its own translation unit: the 48
 // kernels compile side by side with the encode and decode units, and no kernel is in two code objects.  Also the plan of every
-// launch over two plane sets (transcode_plan) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the two
-// measuring calls over them, whose kernels lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip compile.
+// launch over two plane sets (transcode_plan) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the three
+// measuring calls over them, whose kernels lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip /
+// lumahip_transcode_moments_map.hip compile.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
@@ -14,15 +15,18 @@ namespace lhost {
 // The one place that decides what a launch over (source planes, target-side planes) may be and how it runs: argument checks, the
 // supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (TransWhat::Store: tgt =
 // the planes it writes; out = nullptr), for the transcode distortion (Measure: tgt = the given planes it reads, out = its words)
-// and for the transcode distortion map (Map: the same, out = the map of blocks of map_block luma pixels).
+// and for the transcode distortion map and the transcode moments map (Map / Moments: the same, out = the map of blocks of map_block
+// luma pixels; what differs between the two -- blocks accepted, words per block, LDS to meet in, the kernels' launch bound -- is
+// derived from the mode, as distortion_plan derives it from DistWhat).
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
                    TransWhat mode, const uint64_t *out, unsigned map_block, hipStream_t stream, TranscodePlan &p)
 {
-    const bool map = mode == TransWhat::Map, measure = mode != TransWhat::Store;
-    const char *const what = map ? "transcode distortion map" : measure ? "transcode distortion" : "transcode";
-    const char *const out_name = map ? "map_dev" : "out_dev";
-    if (map && !dist_map_block_ok(map_block))
-        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be 16, 32 or 64 (got %u)", what, map_block);
+    const bool moments = mode == TransWhat::Moments, map = trans_is_map(mode), measure = mode != TransWhat::Store;
+    const DistWhat kind = moments ? DistWhat::Moments : DistWhat::Map;   // (of a map mode: the record of its blocks)
+    const char *const what = moments ? "transcode moments map" : map ? "transcode distortion map" : measure ? "transcode distortion" : "transcode";
+    const char *const out_name = moments ? "mom_dev" : map ? "map_dev" : "out_dev";
+    if (map && !dist_block_ok(kind, map_block))
+        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", what, moments ? "8, " : "", map_block);
     if (!src.planes || !src.stride || !src.pfs || !tgt.planes || !tgt.stride || !tgt.pfs || nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     for (int k = 0; k < 3; k++)
@@ -52,11 +56,12 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
         // both plane sets are read only and may overlap each other; the words may not share a byte with anything the launch reads
         if (map) {
             if (!out || !is_aligned(out, 8))
-                return fail(c, LUMAHIP_ERR_ARG, "map_dev must be non-null and 8-byte aligned");
+                return fail(c, LUMAHIP_ERR_ARG, "%s must be non-null and 8-byte aligned", out_name);
         } else if ((rc = check_out_words(c, out))) {
             return rc;
         }
-        const size_t out_bytes = map ? (size_t)nframes * dist_map_words(w, h, map_block) * sizeof(uint64_t) : out_words_bytes(nframes);
+        const size_t out_bytes =
+            map ? (size_t)nframes * dist_map_words(w, h, map_block, dist_words_per_block(kind)) * sizeof(uint64_t) : out_words_bytes(nframes);
         for (int k = 0; k < 3; k++) {
             if (out_overlaps_plane(out, out_bytes, src, k, w, h, nframes))
                 return fail(c, LUMAHIP_ERR_ARG, "%s overlaps source plane %d", out_name, k);
@@ -85,7 +90,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     const size_t lds = (any_y ? sizeof(PowfTablesWide) : 0) + lut_lds_bytes(sq.q) + (csd == CS_YCBCR ? lut_lds_bytes(sq.q) + 2 * col : col) +
                        round16((size_t)qe.nbuckets * (qe.mode == LUT_LINKEY_LDS ? 8 : 4));
     // the words the waves of a measuring workgroup meet in: 12, or the blocks of a map tile
-    const size_t acc_lds = map ? DIST_MAP_LDS_WORDS * sizeof(uint64_t) : measure ? 128 : 0;
+    const size_t acc_lds = moments ? MOMENTS_MAP_LDS_WORDS * sizeof(uint64_t) : map ? DIST_MAP_LDS_WORDS * sizeof(uint64_t) : measure ? 128 : 0;
     if (lds + acc_lds > LUMAHIP_LDS_PER_WORKGROUP)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the tables of both sides take %zu bytes of LDS, a workgroup has %zu", what, lds + acc_lds,
                     LUMAHIP_LDS_PER_WORKGROUP);
@@ -103,7 +108,10 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.threads = block_threads_for(c, lds, long_launch && !any_y, any_y);
     // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
     // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
-    p.threads = std::min(p.threads, measure ? TransDistFamily::bound(any_y) : TransFamily::bound(any_y));
+    // (the moments kernels: for lh::transmoments_threads_bound, the function their launch bound is written with)
+    p.threads = std::min(p.threads, moments   ? transmoments_threads_bound(csd, cse, p.vw)
+                                    : measure ? TransDistFamily::bound(any_y)
+                                              : TransFamily::bound(any_y));
     // the map: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
     if (map)
         p.threads = std::min(p.threads, 32 * (int)map_block);
@@ -168,7 +176,7 @@ int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsi
     DecArgs g{};
     g.g = p.d.g;
     read_planes(g, given, p.vw);
-    if (what != TransWhat::Map) {
+    if (!trans_is_map(what)) {
         TransDistArgs a{};
         a.d = p.d;
         a.e = p.e;
@@ -185,16 +193,17 @@ int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsi
     a.g = g;
     a.map = out;
     a.m = p.m;
-    const transdist_map_kernel_t kern = pick_transdist_map(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
+    const bool moments = what == TransWhat::Moments;
+    const transdist_map_kernel_t kern = (moments ? pick_transdist_moments_map : pick_transdist_map)(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
     if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode distortion map kernel for colour spaces %d -> %d", p.csd, p.cse);
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode %s map kernel for colour spaces %d -> %d", moments ? "moments" : "distortion", p.csd, p.cse);
     if (int rc = launch_fused(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
         return rc;
     HIPCHK(c, hipGetLastError());
     return LUMAHIP_OK;
 }
 
-// what both plane-fed measuring _device entry points do in front of the dispatch
+// what the plane-fed measuring _device entry points do in front of the dispatch
 static int measure_planes_entry(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
                                 float dst_sc, TransWhat what, unsigned block, uint64_t *out)
 {
@@ -245,7 +254,8 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
                           stats, {c->stream, true});
 }
 
-// The two plane-fed measuring entry points (include/lumahip.h has their full prototypes): MEASURE_PARAMS, then the call's own tail.
+// The three plane-fed measuring entry points (include/lumahip.h and, for the moments map, include/lumahip_measure.h have their full
+// prototypes): MEASURE_PARAMS, then the call's own tail.
 #define MEASURE_PARAMS                                                                                                                      \
     const unsigned char *const src_planes[3], const int src_stride[3], const size_t src_pfs[3], int src_profile, float src_sc, unsigned nframes, \
         unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], const size_t given_pfs[3], int dst_profile, \
@@ -256,4 +266,5 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
 extern "C" {
 int lumahip_transcode_distortion_frames_device(lumahip_ctx *c, MEASURE_PARAMS, uint64_t *out_dev) { return MEASURE(Measure, 0, out_dev); }
 int lumahip_transcode_distortion_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return MEASURE(Map, block, map_dev); }
+int lumahip_transcode_moments_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return MEASURE(Moments, block, mom_dev); }
 }  // extern "C"
