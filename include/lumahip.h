@@ -49,6 +49,8 @@ extern "C" {
  *     lumahip_moments_map_frames_device / _planar / _f16 / _planar_f16 and lumahip_moments_map_frame_host.
  *     Declared in include/lumahip_measure.h, which includes this header: the transcode moments map calls
  *     lumahip_transcode_moments_map_frames_device and lumahip_transcode_moments_map_frame_host.
+ *     Declared in include/lumahip_compare.h, which includes this header and is the open one (later additions go there): the
+ *     plane-to-plane measures of two sets of code planes, which need no quantizer.
  *   5 (round 6): additions -- lumahip_pool_create_small, lumahip_decoded_ring_* / lumahip_decode_frames_device_ring.
  *   4 (round 5): additions -- lumahip_rb_table_info, lumahip_lin_index_host, LUMAHIP_POOL_ROTATING, the lumahip_tune keys
  *     "ycbcr_rb_tables" / "rb_near_y" / "rb_near_c" / "lin_index"; lumahip_quantizer_info may answer search mode 7.  Behaviour:

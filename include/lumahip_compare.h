@@ -1,0 +1,72 @@
+/* lumahip_compare.h -- calls of liblumahip.so that compare two sets of code planes as they are, and the header later additions to
+ * the library go into: include/lumahip.h's and include/lumahip_measure.h's lists of declarations are closed, this one is open.  The
+ * library exports these symbols beside the other headers'; LUMAHIP_ABI_VERSION stays 5 (additions that change no existing symbol:
+ * detect them with dlsym).  Including this header includes lumahip.h. */
+#ifndef LUMAHIP_COMPARE_H
+#define LUMAHIP_COMPARE_H
+
+#include "lumahip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Plane-to-plane measures: how far apart two sets of code planes are -- the planes a caller handed to a video encoder and the
+ * planes the video decoder gave back, two decoded streams, or one stream against itself a frame later.
+ *
+ * Take two plane sets A and B of one profile (0..3), nframes frames of w x h, each set with its own base pointers, row strides
+ * and frame strides.  Per sample position, e is the unsigned sample present in A and g the one in B.  Both are read as the decoder
+ * reads them: one byte, or two bytes little-endian, not masked beyond that and not clamped to any table.
+ *
+ * Three results, with words, layouts, block membership, edge cuts and co-sited 4:2:0 chroma exactly as the existing calls define
+ * them (lumahip_distortion_frames_device, lumahip_distortion_map_frames_device, lumahip_moments_map_frames_device):
+ *   distortion      sse, sad, max_abs, n_differ per frame and plane:  out_dev[(f*3 + p)*4 + k], zero-initialised by the call;
+ *   distortion map  the same four per block of 16, 32 or 64:          map_dev[(((f*nby + by)*nbx + bx)*3 + p)*4 + k], every word
+ *                   written exactly once, no initialisation queued;
+ *   moments map     sum e, sum g, sum e*e, sum g*g, sum e*g per block of 8, 16, 32 or 64:
+ *                                                                     mom_dev[(((f*nby + by)*nbx + bx)*3 + p)*5 + k], likewise.
+ * lumahip_distortion_map_dims and lumahip_moments_map_dims give the sizes.  All arithmetic is integer, so results are
+ * bit-reproducible for every launch shape.
+ *
+ * No quantizer is needed.  The calls work on a context that never had lumahip_set_quantizer called (no LUMAHIP_ERR_STATE).  They
+ * read neither quantizer and change neither.
+ *
+ * Overlap.  A and B may overlap each other in any way, since both are read only.  In particular B may be A one frame later
+ * (b_planes_dev[p] = a_planes_dev[p] + a_plane_frame_stride[p], nframes - 1), which gives temporal differences from one buffer.
+ * The output may share no byte with either set.
+ *
+ * Tuning and errors.  The calls are asynchronous on the context's stream and never wait on the host.  They take part in unordered
+ * sections.  They honour lumahip_tune "grid_enc", "lane_grid_enc", "block" and "blocks_per_cu", as the other measuring calls do
+ * (a workgroup of a map call is at most 32 * block threads, since it owns whole blocks).  Errors come before anything is
+ * launched, and the output is then untouched: LUMAHIP_ERR_ARG for odd sizes, bad strides, a bad profile, a null plane pointer, or
+ * a null or misaligned (8 bytes) output; LUMAHIP_ERR_ARG for an output overlapping either set, a block outside the call's set, or
+ * host-form word counts that are too small.
+ *
+ * The host forms upload both plane sets of one frame (no frame strides), run one launch, download the 12 words into `out`, or
+ * the nbx*nby*12 / nbx*nby*15 words into `map` / `mom`, and return synchronously. */
+int lumahip_planes_distortion_frames_device(lumahip_ctx *ctx, const unsigned char *const a_planes_dev[3], const int a_stride[3],
+                                            const size_t a_plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h,
+                                            const unsigned char *const b_planes_dev[3], const int b_stride[3],
+                                            const size_t b_plane_frame_stride[3], int profile, uint64_t *out_dev);
+int lumahip_planes_distortion_map_frames_device(lumahip_ctx *ctx, const unsigned char *const a_planes_dev[3], const int a_stride[3],
+                                                const size_t a_plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h,
+                                                const unsigned char *const b_planes_dev[3], const int b_stride[3],
+                                                const size_t b_plane_frame_stride[3], int profile, unsigned block, uint64_t *map_dev);
+int lumahip_planes_moments_map_frames_device(lumahip_ctx *ctx, const unsigned char *const a_planes_dev[3], const int a_stride[3],
+                                             const size_t a_plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h,
+                                             const unsigned char *const b_planes_dev[3], const int b_stride[3],
+                                             const size_t b_plane_frame_stride[3], int profile, unsigned block, uint64_t *mom_dev);
+int lumahip_planes_distortion_frame_host(lumahip_ctx *ctx, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w,
+                                         unsigned h, const unsigned char *const b_planes[3], const int b_stride[3], int profile,
+                                         uint64_t out[12]);
+int lumahip_planes_distortion_map_frame_host(lumahip_ctx *ctx, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w,
+                                             unsigned h, const unsigned char *const b_planes[3], const int b_stride[3], int profile,
+                                             unsigned block, uint64_t *map, size_t map_words);
+int lumahip_planes_moments_map_frame_host(lumahip_ctx *ctx, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w,
+                                          unsigned h, const unsigned char *const b_planes[3], const int b_stride[3], int profile,
+                                          unsigned block, uint64_t *mom, size_t mom_words);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* LUMAHIP_COMPARE_H */

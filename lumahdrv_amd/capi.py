@@ -185,6 +185,20 @@ _ABI_MEASURE = {
 }
 MEASURE_SYMBOLS = tuple(_ABI_MEASURE)
 
+# The calls include/lumahip_compare.h declares, bound like _ABI's.  That header is the open one -- later additions to the library go
+# there and here --, and tests/test_planes_measure_host.py holds this table and the header to each other whatever their number.
+_TWO_PLANE_SETS = (_vp, _p3, _i3, _s3, _u, _u, _u, _p3, _i3, _s3, _i)          # A's triplets, nframes, w, h, B's triplets, profile
+_TWO_PLANE_SETS_HOST = (_vp, _p3, _i3, _u, _u, _p3, _i3, _i)                   # A's planes, strides, w, h, B's planes, strides, profile
+_ABI_COMPARE = {
+    "lumahip_planes_distortion_frames_device": (_i, _TWO_PLANE_SETS + (_vp,)),
+    "lumahip_planes_distortion_map_frames_device": (_i, _TWO_PLANE_SETS + (_u, _vp)),
+    "lumahip_planes_moments_map_frames_device": (_i, _TWO_PLANE_SETS + (_u, _vp)),
+    "lumahip_planes_distortion_frame_host": (_i, _TWO_PLANE_SETS_HOST + (_vp,)),
+    "lumahip_planes_distortion_map_frame_host": (_i, _TWO_PLANE_SETS_HOST + (_u, _vp, _sz)),
+    "lumahip_planes_moments_map_frame_host": (_i, _TWO_PLANE_SETS_HOST + (_u, _vp, _sz)),
+}
+COMPARE_SYMBOLS = tuple(_ABI_COMPARE)
+
 
 class LumaHipError(RuntimeError):
     """Counterpart of the reference's LumaException (include/luma/luma_exception.h:53-71)."""
@@ -218,7 +232,7 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
                   "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip",
-                  "lumahip_transcode_moments_map.hip")
+                  "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip")
 
 
 def kernel_source_sha() -> str:
@@ -251,7 +265,7 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()):
+    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()) + list(_ABI_COMPARE.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
@@ -559,6 +573,21 @@ class Context:
                 _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc)
         return self._measured(fn, args, w, h, words, dims, block)
 
+    def _measure_two_sets(self, fn, a_planes, a_strides, w, h, b_planes, b_strides, profile, words, dims=None, block=None):
+        """the plane-to-plane measuring host forms"""
+        a_planes = [np.ascontiguousarray(p) for p in a_planes]
+        b_planes = [np.ascontiguousarray(p) for p in b_planes]
+        args = (_arr3(C.c_void_p, [p.ctypes.data for p in a_planes]), _arr3(C.c_int, a_strides), w, h,
+                _arr3(C.c_void_p, [p.ctypes.data for p in b_planes]), _arr3(C.c_int, b_strides), profile)
+        return self._measured(fn, args, w, h, words, dims, block)
+
+    def _two_plane_sets(self, fn, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h, b_plane_ptrs, b_strides,
+                        b_plane_frame_strides, profile, *tail):
+        """the plane-to-plane measuring device calls"""
+        self._chk(fn(self.h, _arr3(C.c_void_p, a_plane_ptrs), _arr3(C.c_int, a_strides), _arr3(C.c_size_t, a_plane_frame_strides), nframes,
+                     w, h, _arr3(C.c_void_p, b_plane_ptrs), _arr3(C.c_int, b_strides), _arr3(C.c_size_t, b_plane_frame_strides), profile,
+                     *tail))
+
     # ---- configuration
     def set_stream(self, hip_stream: int | None):
         """hip_stream: a hipStream_t handle (0 = the default stream, as torch's default stream reports);
@@ -691,6 +720,23 @@ class Context:
         moments_sample_counts(w, h, dst_profile, block) and code_ssim apply unchanged"""
         return self._measure_planes(self.L.lumahip_transcode_moments_map_frame_host, planes, strides, w, h, given_planes, given_strides,
                                     src_sc, src_profile, dst_sc, dst_profile, moments_map_dims, block, words=5)
+
+    def planes_distortion_frame(self, a_planes, a_strides, w, h, b_planes, b_strides, profile=2) -> np.ndarray:
+        """two sets of code planes of one profile, three (rows, stride) uint8 arrays each, compared as they are (no quantizer
+        needed): a (3, 4) uint64 array, per plane {sse, sad, max_abs, n_differ} of A's samples e against B's samples g"""
+        return self._measure_two_sets(self.L.lumahip_planes_distortion_frame_host, a_planes, a_strides, w, h, b_planes, b_strides, profile, 4)
+
+    def planes_distortion_map_frame(self, a_planes, a_strides, w, h, b_planes, b_strides, profile=2, block=16) -> np.ndarray:
+        """planes_distortion_frame's words per block of block x block luma pixels (16, 32 or 64): a (nby, nbx, 3, 4) uint64 array, in
+        one launch; block_sample_counts gives the samples behind each entry"""
+        return self._measure_two_sets(self.L.lumahip_planes_distortion_map_frame_host, a_planes, a_strides, w, h, b_planes, b_strides,
+                                      profile, 4, distortion_map_dims, block)
+
+    def planes_moments_map_frame(self, a_planes, a_strides, w, h, b_planes, b_strides, profile=2, block=8) -> np.ndarray:
+        """per block of block x block luma pixels (8, 16, 32 or 64) and plane the five sums {Se, Sg, See, Sgg, Seg} of A's samples e
+        and B's samples g: a (nby, nbx, 3, 5) uint64 array, in one launch; moments_map_dims, moments_sample_counts and code_ssim apply"""
+        return self._measure_two_sets(self.L.lumahip_planes_moments_map_frame_host, a_planes, a_strides, w, h, b_planes, b_strides, profile,
+                                      5, moments_map_dims, block)
 
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
@@ -880,6 +926,27 @@ class Context:
         self._two_sets(self.L.lumahip_transcode_moments_map_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
                        src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
                        block, mom_ptr)
+
+    # two sets of code planes of one profile compared as they are (include/lumahip_compare.h; no quantizer needed): out_ptr receives
+    # nframes x 3 planes x {sse, sad, max_abs, n_differ} as uint64 (zeroed by the call), e from set A and g from set B
+    def planes_distortion_frames_device(self, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h, b_plane_ptrs, b_strides,
+                                        b_plane_frame_strides, profile, out_ptr):
+        self._two_plane_sets(self.L.lumahip_planes_distortion_frames_device, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h,
+                             b_plane_ptrs, b_strides, b_plane_frame_strides, profile, out_ptr)
+
+    # the same per block x block luma pixels (16, 32 or 64): map_ptr receives nframes x nby x nbx x 3 planes x 4 words, every word
+    # written by the launch
+    def planes_distortion_map_frames_device(self, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h, b_plane_ptrs, b_strides,
+                                            b_plane_frame_strides, profile, block, map_ptr):
+        self._two_plane_sets(self.L.lumahip_planes_distortion_map_frames_device, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w,
+                             h, b_plane_ptrs, b_strides, b_plane_frame_strides, profile, block, map_ptr)
+
+    # the moments of both sets per block x block luma pixels (8, 16, 32 or 64): mom_ptr receives nframes x nby x nbx x 3 planes x
+    # {Se, Sg, See, Sgg, Seg} as uint64, every word written by the launch
+    def planes_moments_map_frames_device(self, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h, b_plane_ptrs, b_strides,
+                                         b_plane_frame_strides, profile, block, mom_ptr):
+        self._two_plane_sets(self.L.lumahip_planes_moments_map_frames_device, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h,
+                             b_plane_ptrs, b_strides, b_plane_frame_strides, profile, block, mom_ptr)
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

@@ -30,3 +30,6 @@ FLAGS_lumahip_distortion_map_f16 := $(FLAGS_lumahip_encode)
 #   lumahip_moments_map / _f16: the same -- k_moments_map is k_distortion_map with another consumer.
 FLAGS_lumahip_moments_map := $(FLAGS_lumahip_encode)
 FLAGS_lumahip_moments_map_f16 := $(FLAGS_lumahip_encode)
+#   lumahip_planes_measure: the decode unit's (the default strategy) -- its kernels are the decode kernels' plane loads and integer
+#   accumulation, with none of the encode arithmetic max-ilp was measured on.
+FLAGS_lumahip_planes_measure :=

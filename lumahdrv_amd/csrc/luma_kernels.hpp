@@ -646,6 +646,8 @@ LH_DEV void enc_emit(int f, int ux, int uy, const float (&c0)[2 * VW], const flo
 //   frames in       FrameFront; enc_load, enc_transform  k_encode               k_distortion                k_distortion_map              k_moments_map
 //   code planes in  PlaneFront; dec_load, dec_values,    k_transcode            k_transcode_distortion      k_transcode_distortion_map    k_transcode_moments_map
 //                   enc_transform
+//   code planes in, as they are: dec_issue, planes_rows  --                     k_planes_distortion         k_planes_distortion_map       k_planes_moments_map
+//                   (no enc_codes: the planes' own samples are handed to the consumer in its order)
 // A kernel is its front end, its consumer and the persistent loop that orders their loads against each other; the loops differ on
 // purpose (stores before the next loads / the given words travelling along, one flush site) and stay written out.  Also written
 // out: the stage_tables calls and, in the plane-fed kernels, the LDS pointers, kd / ke and the per-unit dec_values / enc_transform
@@ -2240,6 +2242,141 @@ void k_transcode_moments_map(const TransDistMapArgs a)
         m = mn;
         s = sn;
     }
+}
+
+// ---- PLANES IN, AS THEY ARE -------------------------------------------------------------------------
+// The third front end over the same three consumers: e is not computed, it is the sample present in a plane set A, as g is the one
+// present in a set B -- both read as the decoder reads them, no quantizer on either side (DecArgs::q stays unused), no tables, no
+// dynamic LDS, no transform, no search.  Reads 3 + 3 B per pixel at profile 2.  With no arithmetic to hide them behind, the loads are
+// these kernels' limit -- their latency, not their bytes: 0.18 - 0.42 of the HBM rate as measured, profile 0 no faster than profile 2
+// (DESIGN.md 3.13 has the counters and the open point).
+//   k_planes_distortion        DistMeasureUnit<., ., DistAcc>,       dist_words / dist_flush,               k_distortion's loop
+//   k_planes_distortion_map    DistMeasureUnit<., ., DistBlockAcc>,  dist_map_words / dist_map_flush,       k_distortion_map's loop
+//   k_planes_moments_map       MomentMeasureUnit,                    dist_map_words<MomentBlockAcc> / ...,  k_distortion_map's loop
+// Both sets' words are fetched by dec_issue one iteration ahead, A's right in front of B's; A's rows are unpacked where they are
+// consumed (given_row: vector words where the set is `aligned`, load_samples byte by byte where it is not, decided per set) and
+// handed over in enc_codes' order.  The consumers' mask is a no-op on unpacked samples.
+struct PlanesMeasureArgs {
+    DecArgs a;         // set A (e): g, src, stride, src_frame_stride, bps, aligned
+    DecArgs g;         // set B (g): the same geometry and sample size, its own pointers, strides and `aligned`
+    uint64_t *out;     // DistArgs::out (zeroed before the launch), or MapArgs::map (needs no zeroing)
+    MapGeom m;         // the map kernels only
+};
+
+// the rows of unit `e` of set A to the consumer, in enc_codes' order
+template <bool SUB, int VW, typename Out>
+LH_DEV void planes_rows(const DecRaw<SUB, VW> &e, const DecArgs &a, const Out &out)
+{
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        int row[VW];
+        given_row<SUB, VW, VW>(e, a, 0, r, row);
+        out.template row<VW>(0, r, row);
+    }
+    if constexpr (SUB) {
+        constexpr int NQ = VW / 2;
+        int k1[NQ], k2[NQ];
+        given_row<SUB, VW, NQ>(e, a, 1, 0, k1);
+        given_row<SUB, VW, NQ>(e, a, 2, 0, k2);
+        out.template row<NQ>(1, 0, k1);
+        out.template row<NQ>(2, 0, k2);
+    } else {
+#pragma unroll
+        for (int pl = 1; pl < 3; pl++) {
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                int row[VW];
+                given_row<SUB, VW, VW>(e, a, pl, r, row);
+                out.template row<VW>(pl, r, row);
+            }
+        }
+    }
+}
+
+// Register budget (profiles/planes_measure_codegen.txt has the compiler's table): the accumulators (15 - 24 registers) and the raw
+// words of both sets; every variant fits the 128 registers of a 1024-thread workgroup without scratch, so the bound stays there and
+// no waves-per-SIMD target is asked for.
+constexpr int PLANES_MEASURE_BOUND = 1024;
+
+template <bool SUB, int VW>
+__global__ __launch_bounds__(PLANES_MEASURE_BOUND) void k_planes_distortion(const PlanesMeasureArgs a)
+{
+    unsigned long long *const s_acc = dist_words();
+    __syncthreads();   // (no stage_tables behind the zeroing here)
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    DistAcc acc;
+    DecRaw<SUB, VW> e, given;
+    dec_issue<SUB, VW>(e, a.a, blockIdx.x, tx, ty, NW);
+    dec_issue<SUB, VW>(given, a.g, blockIdx.x, tx, ty, NW);
+    for (int t = blockIdx.x;; t += G) {
+        const bool done = t >= a.a.g.totalTiles;        // workgroup-uniform, as the frame index is
+        dist_flush(acc, s_acc, done ? -2 : t / a.a.g.tilesPerFrame, a.out);
+        if (done)
+            break;
+        if (e.valid) {
+            const DistMeasureUnit<SUB, VW> out{given, a.g, acc, mask};
+            planes_rows<SUB, VW>(e, a.a, out);
+        }
+        dec_issue<SUB, VW>(e, a.a, t + G, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t + G, tx, ty, NW);
+    }
+}
+
+// the loop of both map kernels: k_distortion_map's, the next sub-tile's loads issued before the flush
+template <bool SUB, int VW, typename Acc, typename Unit>
+LH_DEV void planes_map_loop(const PlanesMeasureArgs &a, unsigned long long *s_map)
+{
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    Acc acc;
+    DecRaw<SUB, VW> e, given;
+    int m = blockIdx.x, s = 0;
+    {
+        const int t = map_subtile(a.m, a.a.g, m, 0);
+        dec_issue<SUB, VW>(e, a.a, t, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
+    }
+    while (m < a.m.totalMapTiles) {   // workgroup-uniform
+        if (e.valid) {
+            const Unit out{given, a.g, acc, mask};
+            planes_rows<SUB, VW>(e, a.a, out);
+        }
+        const bool last = s + 1 == a.m.S;
+        const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
+        const int t = map_subtile(a.m, a.a.g, mn, sn);
+        dec_issue<SUB, VW>(e, a.a, t, tx, ty, NW);
+        dec_issue<SUB, VW>(given, a.g, t, tx, ty, NW);
+        if (last) {
+            dist_map_flush<VW>(acc, s_map, a.m, a.a.g, a.out, m, tx);
+            acc.reset();
+        }
+        m = mn;
+        s = sn;
+    }
+}
+
+template <bool SUB, int VW>
+__global__ __launch_bounds__(PLANES_MEASURE_BOUND) void k_planes_distortion_map(const PlanesMeasureArgs a)
+{
+    unsigned long long *const s_map = dist_map_words();
+    __syncthreads();
+    planes_map_loop<SUB, VW, DistBlockAcc, DistMeasureUnit<SUB, VW, DistBlockAcc>>(a, s_map);
+}
+
+template <bool SUB, int VW>
+__global__ __launch_bounds__(PLANES_MEASURE_BOUND) void k_planes_moments_map(const PlanesMeasureArgs a)
+{
+    unsigned long long *const s_map = dist_map_words<MomentBlockAcc>();
+    __syncthreads();
+    planes_map_loop<SUB, VW, MomentBlockAcc, MomentMeasureUnit<SUB, VW>>(a, s_map);
 }
 
 // ---- stand-alone colour transform (LumaQuantizer::transformColorSpace as public API) ---------------

@@ -1011,15 +1011,22 @@ struct StagedPlanes {
 
 // What those calls open with, after their null checks: the geometry against the target-side set `tgt`, the source set's profile and
 // quantizer (src = nullptr: frames in, one set), both layouts, d_planes large enough for [src][tgt] and d_arr for the `words`
-// 64-bit words of a measuring call (12; a map's; 0: none)
-static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes &tgt, size_t words)
+// 64-bit words of a measuring call (12; a map's; 0: none).  quantizers = false: the two sets are compared as they are (the
+// plane-to-plane measures), neither quantizer is asked for
+static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes &tgt, size_t words, bool quantizers = true)
 {
-    int rc = check_geom(c, w, h, tgt.profile, c->q.cs);
+    int rc = LUMAHIP_OK;
+    if (quantizers)
+        rc = check_geom(c, w, h, tgt.profile, c->q.cs);
+    else if (w == 0 || h == 0 || (w & 1) || (h & 1))
+        rc = fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (must be even, non-zero)", w, h);
+    else if (tgt.profile < 0 || tgt.profile > 3)
+        rc = fail(c, LUMAHIP_ERR_ARG, "profile must be 0..3 (got %d)", tgt.profile);
     if (rc)
         return rc;
     if (src && (src->profile < 0 || src->profile > 3))
         return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src->profile);
-    if (src && !c->src.have)
+    if (quantizers && src && !c->src.have)
         return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
     HIPCHK(c, hipSetDevice(c->device));
     c->up_ramp = 0;
@@ -1212,6 +1219,55 @@ extern "C" int lumahip_transcode_moments_map_frame_host(lumahip_ctx *c, const un
 {
     return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
                                TransWhat::Moments, block, mom, mom_words);
+}
+
+// Two plane sets of one frame in host memory -> what a plane-to-plane measuring call delivers (lumahip_planes_measure.hip),
+// synchronously: the 12 distortion words (Frame; block and out_words ignored), or the frame's distortion / moments map of
+// nbx * nby * 12 / 15 words; the context's plane staging holds both sets.  No quantizer is read.
+static int compare_planes_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w, unsigned h,
+                               const unsigned char *const b_planes[3], const int b_stride[3], int profile, DistWhat what, unsigned block,
+                               uint64_t *out, size_t out_words)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!a_planes || !a_stride || !b_planes || !b_stride || !out)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    const bool map = what != DistWhat::Frame, moments = what == DistWhat::Moments;
+    const char *const name = moments ? "planes moments map" : "planes distortion map";
+    if (map && !dist_block_ok(what, block))
+        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", name, moments ? "8, " : "", block);
+    StagedPlanes a{"set A ", a_planes, a_stride, profile}, b{"set B ", b_planes, b_stride, profile};
+    int rc = planes_staging(c, w, h, &a, b, 0, false);   // (the words' count needs a checked geometry)
+    if (rc)
+        return rc;
+    const size_t words = map ? dist_map_words(w, h, block, dist_words_per_block(what)) : 12;
+    if (map && out_words < words)
+        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", name, out_words, words);
+    if ((rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, words * sizeof(uint64_t))) || (rc = planes_up(c, a, h)) || (rc = planes_up(c, b, h)) ||
+        (rc = planes_measure_impl(c, a.dev(), 1, w, h, b.dev(), what, block, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
+        return rc;
+    return words_down(c, out, words);
+}
+
+extern "C" int lumahip_planes_distortion_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w,
+                                                    unsigned h, const unsigned char *const b_planes[3], const int b_stride[3], int profile,
+                                                    uint64_t out[12])
+{
+    return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Frame, 0, out, 12);
+}
+
+extern "C" int lumahip_planes_distortion_map_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3],
+                                                        unsigned w, unsigned h, const unsigned char *const b_planes[3], const int b_stride[3],
+                                                        int profile, unsigned block, uint64_t *map, size_t map_words)
+{
+    return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Map, block, map, map_words);
+}
+
+extern "C" int lumahip_planes_moments_map_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3],
+                                                     unsigned w, unsigned h, const unsigned char *const b_planes[3], const int b_stride[3],
+                                                     int profile, unsigned block, uint64_t *mom, size_t mom_words)
+{
+    return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Moments, block, mom, mom_words);
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the

@@ -27,6 +27,9 @@
 //   lumahip_distortion_f16.hip, lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip / _f16.hip  pick_dist<DistFamily, true>,
 //                       pick_dist<DistMapFamily, .>, pick_dist<MomentsMapFamily, .> (the other frame-fed measuring kernels), exported
 //                       as pick_dist_f16, pick_dist_map_f32 / _f16, pick_moments_map_f32 / _f16; nothing else
+//   lumahip_planes_measure.hip  the twelve k_planes_distortion / k_planes_distortion_map / k_planes_moments_map kernels (two plane sets
+//                       as they are, no quantizer), their picker, planes_plan, the dispatch planes_measure_impl and the three
+//                       _device entry points of include/lumahip_compare.h
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -49,6 +52,7 @@
 #define LUMAHIP_EXPERIMENTAL   /* the library defines what the experimental section of the header declares */
 #include "../../include/lumahip.h"
 #include "../../include/lumahip_measure.h"
+#include "../../include/lumahip_compare.h"
 #include "luma_kernels.hpp"
 #include "host_lut.hpp"
 #include "lut_index.hpp"
@@ -388,7 +392,7 @@ struct DecodeLaunch {
 static inline size_t lut_lds_bytes(const QuantDev &q) { return ((size_t)(q.lut_len + q.pad) * 4 + 15) & ~(size_t)15; }   // the luminance table, or the y table, in LDS
 size_t lds_bytes(const lumahip_ctx *c, bool encode_side, int cs_eff, bool ycode = false, bool half = false);   // ycode: the composite-record encode kernels; half: + the half-input table
 int block_threads_for(const lumahip_ctx *c, size_t lds, bool few_waves = false, bool valu_bound = false);
-int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers = 0, int ycbcr = 0, bool transcode = false);   // few_writers: 0 no, 1 yes, 2 yes with the colour planes in separate buffers; ycbcr: 0 no, 1 yes, 2 the half-input encode kernels; transcode: the k_transcode family (dir 0)
+int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers = 0, int ycbcr = 0, bool transcode = false, int own_per_cu = 0);   // few_writers: 0 no, 1 yes, 2 yes with the colour planes in separate buffers; ycbcr: 0 no, 1 yes, 2 the half-input encode kernels; transcode: the k_transcode family (dir 0); own_per_cu > 0: this family's own workgroups per CU in the place of the rules' (the tune keys keep their precedence)
 // ---- lumahip_core.hip
 int ensure_search_index(lumahip_ctx *c, hipStream_t s);   // every encode-side launch calls this first (lazy build / process-wide cache); s: the stream that launch goes to
 bool ycbcr_composite_ready(const lumahip_ctx *c);   // encode: the composite luma -> code records exist and fit LDS
@@ -620,6 +624,17 @@ typedef void (*transdist_map_kernel_t)(const lh::TransDistMapArgs);
 transdist_kernel_t pick_transdist(int vw, int csd, bool subd, int cse, bool sube, int mode);
 transdist_map_kernel_t pick_transdist_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
 transdist_map_kernel_t pick_transdist_moments_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
+
+// ---- lumahip_planes_measure.hip: two plane sets as they are (include/lumahip_compare.h)
+struct PlanesLaunch {
+    hipStream_t stream;
+    bool lanes = false;   // as EncodeLaunch::lanes
+};
+// e = the samples of set a, g = those of set b (one profile: b.profile is read, a.profile must equal it), no quantizer read.
+// Frame: 12 words per frame at out (zeroed in front of the launch; block ignored); Map / Moments: nframes * nby * nbx * 12 / 15 words,
+// every one written by the launch.  Every error is raised before anything is queued.
+int planes_measure_impl(lumahip_ctx *c, const SrcPlanes &a, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &b, DistWhat what,
+                        unsigned block, uint64_t *out, const PlanesLaunch &o);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

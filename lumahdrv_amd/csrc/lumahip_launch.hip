@@ -66,8 +66,8 @@ int block_threads_for(const lumahip_ctx *c, size_t lds, bool few_waves, bool val
 // settings in one process (tools/bench/ab_inproc.py, profiles/r02_grid_sweep.txt) and then re-derived over {720p, 1080p, 4K, 8K} x
 // {1, 2, 4, 8, 20, 50 frames} x {Lu'v', YCbCr} x {encode, decode} with every setting interleaved in one process
 // (tools/bench/launch_rules_sweep.py, profiles/r03_launch_rules.txt: before / after tables).  lumahip_tune "grid_enc" / "grid_dec"
-// (absolute) and "blocks_per_cu" (per CU, both directions) are measurement overrides.
-int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers, int ycbcr, bool transcode)
+// (absolute) and "blocks_per_cu" (per CU, both directions) are measurement overrides.  own_per_cu: see below.
+int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int few_writers, int ycbcr, bool transcode, int own_per_cu)
 {
     int per_cu = c->blocks_per_cu > 0 ? c->blocks_per_cu : 2048 / threads;
     const bool rule = c->blocks_per_cu == 0;
@@ -115,6 +115,10 @@ int grid_for(const lumahip_ctx *c, int threads, int total_tiles, int dir, int fe
     // profiles/r04_half_table_grid.txt, tools/bench/half_grid_sweep.py.
     if (ycbcr == 2 && rule && threads == 1024)
         per_cu = total_tiles < 3000 ? 1 : total_tiles < 12000 ? 3 : 12;
+    // A family with a measured per-CU value of its own (own_per_cu > 0; no existing caller passes one) takes it where the rules above
+    // would have decided: "blocks_per_cu" still goes before it, and the lane and grid overrides below after it, as for every rule.
+    if (own_per_cu > 0 && rule)
+        per_cu = own_per_cu;
     long g = (long)c->num_cu * per_cu;
     // Inside an unordered section every launch keeps the grid it would have alone: two lanes of 3 (encode) / 5 (decode)
     // workgroups per CU each measured best (profiles/r03_layout_lab.txt: encode 0.780 of the roofline against 0.751 ordered,
