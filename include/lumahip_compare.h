@@ -66,6 +66,57 @@ int lumahip_planes_moments_map_frame_host(lumahip_ctx *ctx, const unsigned char 
                                           unsigned h, const unsigned char *const b_planes[3], const int b_stride[3], int profile,
                                           unsigned block, uint64_t *mom, size_t mom_words);
 
+/* Content light level: what an HDR10 deliverable states about its own content -- how bright the brightest pixel is (MaxCLL) and how
+ * bright the brightest frame is on average (MaxFALL), both over max(R, G, B) in cd/m2 -- as eight integers per frame, of frames as
+ * they are or of a stream that is only held as code planes.
+ *
+ * The statistic (normative).  Inputs are a float frame F of w x h pixels and a `scale` that is finite and > 0; pass the stream's
+ * preScaling to get cd/m2.  Per pixel, in fp32, nothing contracted:
+ *   r = R * scale, g = G * scale, b = B * scale   one rounded multiply each (skipped when scale == 1.0f, since x * 1.0f is x);
+ *   m = fmaxf(fmaxf(r, g), b)                     a NaN channel is ignored; m is NaN only if all three are;
+ *   y = (0.212656f * r + 0.715158f * g) + 0.072186f * b
+ *                                                 the Y row of the RGB -> XYZ matrix in its association order, not clamped; with
+ *                                                 scale equal to the preScaling, the value whose clamp the Lu'v' encoder quantizes;
+ *   q(v), in units of 1/256:  t = v * 256.0f;  q = 0 where !(t > 0) (NaN, negatives, both zeros, -inf);  q = 0xFFFFFFFF where
+ *                             t >= 4294967296.0f (such pixels are counted as "over");  otherwise q = floor(t).
+ * Per frame f, eight uint64_t words out[f * LUMAHIP_LIGHT_WORDS + k]:
+ *   k  0  sum of q(m)      1  max of q(m)      2  pixels with m * 256 >= 2^32      3  pixels with m NaN
+ *      4  sum of q(y)      5  max of q(y)      6  pixels with y * 256 >= 2^32      7  pixels with y NaN
+ * All words are integers, so they are bit-reproducible for every launch shape and order of arrival (an 8K frame of saturated
+ * pixels sums to 1.4e17, which fits).  MaxCLL = ceil(max over f of word 1 / 256), MaxFALL = ceil(max over f of word 0 /
+ * (256 * w * h)), each capped at 65535 where it is stored in 16 bits: every pixel is in the divisor, as CTA-861.3 averages over the
+ * whole picture.
+ *
+ * The plane-fed form is by definition the frame-fed form applied to the floats lumahip_decode_frames_device writes for those planes
+ * under the context's quantizer and the given sc; no float frame is written.  It needs the quantizer (LUMAHIP_ERR_STATE without)
+ * and the tables that call stages in on-chip memory: a transfer-function or chroma depth beyond 12 bits, or a YCbCr stream without
+ * its y table, is LUMAHIP_ERR_UNSUPPORTED.  The frame-fed forms read no quantizer and work on a context that never had one.
+ *
+ * Frame layouts, strides counted in elements and alignment are the encode calls' (lumahip_encode_frames_device, _planar, _f16,
+ * _planar_f16); the frames are only read, so their colour planes may overlap each other.  The calls are asynchronous on the
+ * context's stream, never wait on the host, zero their words themselves, take part in unordered sections and honour lumahip_tune
+ * "grid_enc", "lane_grid_enc", "block" and "blocks_per_cu".  Errors come before anything is launched, and the output is then
+ * untouched: LUMAHIP_ERR_ARG for odd or zero sizes, nframes 0, a scale that is not finite and > 0, a null frame or plane pointer, bad
+ * strides, a bad profile, a null or misaligned (8 bytes) out_dev, or an out_dev whose nframes * 64 bytes share a byte with what is read.
+ *
+ * The host forms upload one frame (packed floats, 3 * w * h) or one frame's planes, run one launch, download the eight words and
+ * return synchronously. */
+#define LUMAHIP_LIGHT_WORDS 8
+int lumahip_light_level_frames_device(lumahip_ctx *ctx, const float *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w, unsigned h,
+                                      float scale, uint64_t *out_dev);
+int lumahip_light_level_frames_device_planar(lumahip_ctx *ctx, const float *const planes_dev[3], size_t frame_stride, unsigned nframes,
+                                             unsigned w, unsigned h, float scale, uint64_t *out_dev);
+int lumahip_light_level_frames_device_f16(lumahip_ctx *ctx, const uint16_t *rgb_dev, size_t frame_stride, unsigned nframes, unsigned w,
+                                          unsigned h, float scale, uint64_t *out_dev);
+int lumahip_light_level_frames_device_planar_f16(lumahip_ctx *ctx, const uint16_t *const planes_dev[3], size_t frame_stride, unsigned nframes,
+                                                 unsigned w, unsigned h, float scale, uint64_t *out_dev);
+int lumahip_planes_light_level_frames_device(lumahip_ctx *ctx, const unsigned char *const planes_dev[3], const int stride[3],
+                                             const size_t plane_frame_stride[3], unsigned nframes, unsigned w, unsigned h, int profile, float sc,
+                                             float scale, uint64_t *out_dev);
+int lumahip_light_level_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned w, unsigned h, float scale, uint64_t out[8]);
+int lumahip_planes_light_level_frame_host(lumahip_ctx *ctx, const unsigned char *const planes[3], const int stride[3], unsigned w, unsigned h,
+                                          int profile, float sc, float scale, uint64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

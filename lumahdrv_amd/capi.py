@@ -189,6 +189,7 @@ MEASURE_SYMBOLS = tuple(_ABI_MEASURE)
 # there and here --, and tests/test_planes_measure_host.py holds this table and the header to each other whatever their number.
 _TWO_PLANE_SETS = (_vp, _p3, _i3, _s3, _u, _u, _u, _p3, _i3, _s3, _i)          # A's triplets, nframes, w, h, B's triplets, profile
 _TWO_PLANE_SETS_HOST = (_vp, _p3, _i3, _u, _u, _p3, _i3, _i)                   # A's planes, strides, w, h, B's planes, strides, profile
+_LIGHT_FRAMES = (_vp, _vp, _sz, _u, _u, _u, _f, _vp)                            # frames, frame_stride, nframes, w, h, scale, out
 _ABI_COMPARE = {
     "lumahip_planes_distortion_frames_device": (_i, _TWO_PLANE_SETS + (_vp,)),
     "lumahip_planes_distortion_map_frames_device": (_i, _TWO_PLANE_SETS + (_u, _vp)),
@@ -196,6 +197,13 @@ _ABI_COMPARE = {
     "lumahip_planes_distortion_frame_host": (_i, _TWO_PLANE_SETS_HOST + (_vp,)),
     "lumahip_planes_distortion_map_frame_host": (_i, _TWO_PLANE_SETS_HOST + (_u, _vp, _sz)),
     "lumahip_planes_moments_map_frame_host": (_i, _TWO_PLANE_SETS_HOST + (_u, _vp, _sz)),
+    "lumahip_light_level_frames_device": (_i, _LIGHT_FRAMES),
+    "lumahip_light_level_frames_device_planar": (_i, (_vp, _p3) + _LIGHT_FRAMES[2:]),
+    "lumahip_light_level_frames_device_f16": (_i, _LIGHT_FRAMES),
+    "lumahip_light_level_frames_device_planar_f16": (_i, (_vp, _p3) + _LIGHT_FRAMES[2:]),
+    "lumahip_planes_light_level_frames_device": (_i, _PLANES + (_f, _vp)),
+    "lumahip_light_level_frame_host": (_i, (_vp, _vp, _u, _u, _f, _vp)),
+    "lumahip_planes_light_level_frame_host": (_i, _PLANES_HOST + (_f, _vp)),
 }
 COMPARE_SYMBOLS = tuple(_ABI_COMPARE)
 
@@ -232,7 +240,7 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
                   "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip",
-                  "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip")
+                  "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip", "lumahip_light_level.hip")
 
 
 def kernel_source_sha() -> str:
@@ -426,6 +434,23 @@ def code_psnr(sse, nsamples, peak) -> float:
     if int(sse) == 0:
         return float("inf")
     return 10.0 * float(np.log10(float(peak) * float(peak) * float(nsamples) / float(sse)))
+
+
+LIGHT_WORDS = 8   # include/lumahip_compare.h LUMAHIP_LIGHT_WORDS
+
+
+def content_light_level(words, w: int, h: int):
+    """(MaxCLL, MaxFALL) in cd/m2 of a stream from the eight words per frame of the light-level calls (run with scale = the stream's
+    preScaling): words is (nframes, 8), or one frame's 8.  MaxCLL = ceil(max_f words[f][1] / 256), MaxFALL = ceil(max_f words[f][0] /
+    (256 w h)) -- every pixel is in the divisor, as CTA-861.3 averages over the whole picture -- both capped at 65535, the largest value
+    the HDR10 side data holds.  Python integers throughout."""
+    rows = np.asarray(words, dtype=np.uint64).reshape(-1, LIGHT_WORDS)
+    if rows.shape[0] == 0:
+        return 0, 0
+    peak = max(int(r[1]) for r in rows)
+    total = max(int(r[0]) for r in rows)
+    den = 256 * int(w) * int(h)
+    return min(65535, -(-peak // 256)), min(65535, -(-total // den))
 
 
 def distortion_map_dims(w: int, h: int, block: int):
@@ -738,6 +763,25 @@ class Context:
         return self._measure_two_sets(self.L.lumahip_planes_moments_map_frame_host, a_planes, a_strides, w, h, b_planes, b_strides, profile,
                                       5, moments_map_dims, block)
 
+    def light_level_frame(self, rgb: np.ndarray, scale=1.0) -> np.ndarray:
+        """rgb: (3,h,w) float32.  Returns the frame's eight uint64 words {sum q(m), max q(m), over, NaN; the same of y}, m = max(R, G, B)
+        and y the luminance after `* scale`, in units of 1/256 (include/lumahip_compare.h); content_light_level folds them.  No
+        quantizer needed"""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        _, h, w = rgb.shape
+        out = np.zeros(LIGHT_WORDS, dtype=np.uint64)
+        self._chk(self.L.lumahip_light_level_frame_host(self.h, rgb.ctypes.data, w, h, scale, out.ctypes.data))
+        return out
+
+    def planes_light_level_frame(self, planes, strides, w, h, sc=1.0, profile=2, scale=1.0) -> np.ndarray:
+        """light_level_frame of the frame decode_frame(planes, strides, w, h, sc, profile) would return, in one launch and without
+        that frame: eight uint64 words"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        out = np.zeros(LIGHT_WORDS, dtype=np.uint64)
+        self._chk(self.L.lumahip_planes_light_level_frame_host(self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]),
+                                                               _arr3(C.c_int, strides), w, h, profile, sc, scale, out.ctypes.data))
+        return out
+
     def encode_frame_f16(self, rgb: np.ndarray, sc=1.0, profile=2, align=32, strides=None):
         """rgb: (3,h,w) np.float16 (LumaFrame layout of halves; 6 B per pixel cross to the device).  Returns (planes, strides,
         mean_lum), equal to encode_frame of the same frame widened to float32."""
@@ -947,6 +991,27 @@ class Context:
                                          b_plane_frame_strides, profile, block, mom_ptr):
         self._two_plane_sets(self.L.lumahip_planes_moments_map_frames_device, a_plane_ptrs, a_strides, a_plane_frame_strides, nframes, w, h,
                              b_plane_ptrs, b_strides, b_plane_frame_strides, profile, block, mom_ptr)
+
+    # content light level (include/lumahip_compare.h): out_ptr receives nframes x 8 uint64 words (zeroed by the call); the frame
+    # arguments are those of the matching encode call, no quantizer needed
+    def light_level_frames_device(self, rgb_ptr, frame_stride, nframes, w, h, scale, out_ptr):
+        self._chk(self.L.lumahip_light_level_frames_device(self.h, rgb_ptr, frame_stride, nframes, w, h, scale, out_ptr))
+
+    def light_level_frames_device_planar(self, rgb_plane_ptrs, frame_stride, nframes, w, h, scale, out_ptr):
+        self._chk(self.L.lumahip_light_level_frames_device_planar(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w, h,
+                                                                  scale, out_ptr))
+
+    def light_level_frames_device_f16(self, rgb_ptr, frame_stride, nframes, w, h, scale, out_ptr):
+        self._chk(self.L.lumahip_light_level_frames_device_f16(self.h, rgb_ptr, frame_stride, nframes, w, h, scale, out_ptr))
+
+    def light_level_frames_device_planar_f16(self, rgb_plane_ptrs, frame_stride, nframes, w, h, scale, out_ptr):
+        self._chk(self.L.lumahip_light_level_frames_device_planar_f16(self.h, _arr3(C.c_void_p, rgb_plane_ptrs), frame_stride, nframes, w,
+                                                                      h, scale, out_ptr))
+
+    # the same of the frames decode_frames_device would write for these planes under the context's quantizer and sc, never written
+    def planes_light_level_frames_device(self, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile, sc, scale, out_ptr):
+        self._plane_fed(self.L.lumahip_planes_light_level_frames_device, plane_ptrs, strides, plane_frame_strides, nframes, w, h, profile,
+                        sc, scale, out_ptr)
 
     def mean_luminance_reference_device(self, rgb_ptr, w, h, sc=1.0) -> float:
         """the reference's sequentially-summed mean of transformed channel 0 (exact; ~25 ms at 4K)"""

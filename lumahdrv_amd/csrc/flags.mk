@@ -33,3 +33,6 @@ FLAGS_lumahip_moments_map_f16 := $(FLAGS_lumahip_encode)
 #   lumahip_planes_measure: the decode unit's (the default strategy) -- its kernels are the decode kernels' plane loads and integer
 #   accumulation, with none of the encode arithmetic max-ilp was measured on.
 FLAGS_lumahip_planes_measure :=
+#   lumahip_light_level: the decode unit's (the default strategy) -- its kernels are loads, the decode arithmetic of the plane-fed
+#   family and integer accumulation; not measured either way.
+FLAGS_lumahip_light_level :=

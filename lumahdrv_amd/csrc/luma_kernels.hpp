@@ -2379,6 +2379,245 @@ __global__ __launch_bounds__(PLANES_MEASURE_BOUND) void k_planes_moments_map(con
     planes_map_loop<SUB, VW, MomentBlockAcc, MomentMeasureUnit<SUB, VW>>(a, s_map);
 }
 
+// ---- CONTENT LIGHT LEVEL ----------------------------------------------------------------------------
+// A fourth consumer, which needs neither enc_codes nor given planes: what an HDR10 deliverable states about its own content, per
+// frame, over m = max(R, G, B) (MaxCLL / MaxFALL) and over the luminance y = rgb_to_xyz's Y row without clamp_xyz, both after
+// `* scale` (the stream's preScaling gives cd/m2) and in units of 1/256 (include/lumahip_compare.h has the normative text):
+//   out[f * 8 + .] = { sum q(m), max q(m), #(m * 256 >= 2^32), #(m NaN), sum q(y), max q(y), #(y * 256 >= 2^32), #(y NaN) }
+// Two front ends: the frames themselves (k_light_level: enc_load, float or binary16; 12 / 6 B per pixel read, nothing written) and
+// code planes (k_planes_light_level: dec_load + dec_values under the context's quantizer, i.e. exactly the floats the decode
+// kernels would store; 3 B per pixel at profile 2).  Integers throughout: the words do not depend on the launch shape or on the
+// order of arrival.
+constexpr int LIGHT_WORDS = 8;
+
+// q: a non-negative value in units of 1/256 as an unsigned 32-bit integer.  The three cases are written out as selects (no branch
+// per pixel), and the conversion only ever sees a value inside its range
+LH_DEV uint32_t light_q(float v, uint32_t &over)
+{
+    const float t = v * 256.0f;
+    const bool positive = t > 0.0f;              // false for NaN, negatives, both zeros, -inf
+    const bool big = t >= 4294967296.0f;
+    over += big;
+    const uint32_t fl = (uint32_t)((positive && !big) ? t : 0.0f);   // 0 <= . < 2^32: the conversion truncates, which is the floor
+    return big ? 0xFFFFFFFFu : fl;
+}
+
+// the larger of two floats, a NaN ignored: fmaxf
+LH_DEV float light_max(float a, float b) { return fmaxf(a, b); }
+
+struct LightAcc {
+    uint64_t sum[2];               // [0] of q(m), [1] of q(y)
+    uint32_t mx[2], over[2], nan[2];   // (a lane's share of one frame is far below 2^32 pixels)
+    int frame = -1;                // no frame yet
+    LH_DEVS LightAcc() { reset(); }
+    LH_DEVS void reset()
+    {
+        sum[0] = sum[1] = 0;
+        mx[0] = mx[1] = over[0] = over[1] = nan[0] = nan[1] = 0;
+    }
+};
+
+// the consumer: a unit's floats in the layout of EncUnit::in
+template <int VW>
+struct LightUnit {
+    LightAcc &acc;
+    float scale;
+    LH_DEVS void take(const float (&in)[3][2][VW]) const
+    {
+#pragma unroll
+        for (int r = 0; r < 2; r++)
+#pragma unroll
+            for (int i = 0; i < VW; i++) {
+                float R = in[0][r][i], G = in[1][r][i], B = in[2][r][i];
+                if (scale != 1.0f) {   // (kernel argument: uniform; x * 1.0f == x)
+                    R *= scale;
+                    G *= scale;
+                    B *= scale;
+                }
+                const float m = light_max(light_max(R, G), B);
+                const float y = (0.212656f * R + 0.715158f * G) + 0.072186f * B;
+                const uint32_t qm = light_q(m, acc.over[0]), qy = light_q(y, acc.over[1]);
+                acc.sum[0] += qm;
+                acc.sum[1] += qy;
+                acc.mx[0] = qm > acc.mx[0] ? qm : acc.mx[0];
+                acc.mx[1] = qy > acc.mx[1] ? qy : acc.mx[1];
+                acc.nan[0] += m != m;
+                acc.nan[1] += y != y;
+            }
+    }
+};
+
+// The 8 words of LDS in which the waves of a light-level workgroup meet, zeroed: called before the front end's stage_tables (or a
+// barrier of the kernel's own).  Must stay LH_DEV, as dist_words
+LH_DEV unsigned long long *light_words()
+{
+    __shared__ unsigned long long s_acc[LIGHT_WORDS];
+    if (threadIdx.x < LIGHT_WORDS)
+        s_acc[threadIdx.x] = 0;
+    return s_acc;
+}
+
+// one step of the meeting of a wave's lanes (map_lanes_step's, for LightAcc)
+template <typename Xch>
+LH_DEV void light_lanes_step(LightAcc &acc, Xch xch)
+{
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const uint32_t lo = xch((uint32_t)acc.sum[k]), hi = xch((uint32_t)(acc.sum[k] >> 32));
+        acc.sum[k] += ((uint64_t)hi << 32) | lo;
+        const uint32_t m = xch(acc.mx[k]);
+        acc.mx[k] = m > acc.mx[k] ? m : acc.mx[k];
+        acc.over[k] += xch(acc.over[k]);
+        acc.nan[k] += xch(acc.nan[k]);
+    }
+}
+
+// dist_flush's pattern: the one flush site of a light-level loop, called by every thread of the workgroup at the top of every
+// iteration with f = the frame of the iteration's tile, or -2 past the last tile.  When the frame changes, the 32 lanes of each half
+// of a wave add up among themselves (DPP and one swizzle, as map_lanes_meet: every lane has something to add here, and 256 lanes on
+// 8 LDS words would serialise), lanes 0 and 32 add into the 8 words of LDS, and one thread per word hands it to out[frame * 8 + .]
+// -- one 64-bit global atomic per workgroup, frame and word -- and clears it.
+LH_DEV void light_flush(LightAcc &acc, unsigned long long *s_acc, int f, uint64_t *out)
+{
+    if (f != acc.frame) {
+        if (acc.frame >= 0) {
+            light_lanes_step(acc, [](uint32_t v) { return dpp_lane<0xb1>(v); });    // quad_perm [1, 0, 3, 2]
+            light_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x4e>(v); });    // quad_perm [2, 3, 0, 1]
+            light_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x141>(v); });   // row_half_mirror
+            light_lanes_step(acc, [](uint32_t v) { return dpp_lane<0x140>(v); });   // row_mirror
+            light_lanes_step(acc, [](uint32_t v) { return swz16_lane(v); });        // the other row of 32
+            if ((threadIdx.x & 31) == 0) {
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    atomicAdd(&s_acc[4 * k + 0], (unsigned long long)acc.sum[k]);
+                    atomicMax(&s_acc[4 * k + 1], (unsigned long long)acc.mx[k]);
+                    atomicAdd(&s_acc[4 * k + 2], (unsigned long long)acc.over[k]);
+                    atomicAdd(&s_acc[4 * k + 3], (unsigned long long)acc.nan[k]);
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x < LIGHT_WORDS) {
+                const unsigned long long v = s_acc[threadIdx.x];
+                s_acc[threadIdx.x] = 0;
+                unsigned long long *dst = reinterpret_cast<unsigned long long *>(out) + (size_t)acc.frame * LIGHT_WORDS + threadIdx.x;
+                if (v != 0) {
+                    if ((threadIdx.x & 3) == 1)
+                        atomicMax(dst, v);
+                    else
+                        atomicAdd(dst, v);
+                }
+            }
+            __syncthreads();
+        }
+        acc.reset();
+        acc.frame = f;
+    }
+}
+
+struct LightArgs {
+    EncArgs e;       // g, src, frame_stride of the frames; everything else unused (no quantizer, no tables)
+    float scale;
+    uint64_t *out;   // [nframes][LIGHT_WORDS], zeroed before the launch
+};
+
+// Register budget: two units in flight (2 x 24 floats at VW 4) and the accumulators (10); every variant fits the 128 registers of
+// a 1024-thread workgroup (profiles/light_level_codegen.txt has the compiler's table).
+constexpr int LIGHT_BOUND = 1024;
+
+// The kernel has no arithmetic to speak of and no stores behind which a single-buffered load could hide (what that costs the
+// plane-to-plane kernels: DESIGN.md 3.13), so it holds TWO units: the loads of tile t + G are issued before unit t is consumed,
+// and the wait in front of unit t leaves them in flight.  The two units take turns -- `step` is called with them one way
+// round, then the other -- so that neither is ever copied (a copy would wait for its loads); the flush stays one site, in `step`.
+template <int VW, bool IN16>
+__global__ __launch_bounds__(LIGHT_BOUND) void k_light_level(const LightArgs a)
+{
+    unsigned long long *const s_acc = light_words();
+    __syncthreads();   // (no stage_tables behind the zeroing here)
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    LightAcc acc;
+    const LightUnit<VW> unit{acc, a.scale};
+    EncUnit<VW> u0, u1;
+    int t = blockIdx.x;
+    // tile t is in `cur`; false past the last tile
+    const auto step = [&](EncUnit<VW> &cur, EncUnit<VW> &nxt) {
+        const bool done = t >= a.e.g.totalTiles;        // workgroup-uniform, as the frame index is
+        light_flush(acc, s_acc, done ? -2 : t / a.e.g.tilesPerFrame, a.out);
+        if (done)
+            return false;
+        enc_load<VW, IN16>(nxt, a.e, t + G, tx, ty, NW);
+        if (cur.valid)
+            unit.take(cur.in);
+        t += G;
+        return true;
+    };
+    enc_load<VW, IN16>(u0, a.e, t, tx, ty, NW);
+    while (step(u0, u1) && step(u1, u0)) {
+    }
+}
+
+struct PlanesLightArgs {
+    DecArgs d;       // q, g, src, stride, src_frame_stride, sc, bps, aligned of the planes, as TransArgs::d under the context's quantizer
+    float scale;
+    uint64_t *out;   // LightArgs::out
+};
+
+// what stage_tables stages for the planes' quantizer: the decode kernels' tables in LDS (transfer function and chroma depth up to 12 bits)
+template <int CS>
+struct LightFront {
+    static constexpr bool Y = CS == CS_YCBCR;
+    static constexpr int WHAT = STAGE_LUT | (Y ? STAGE_POWF | STAGE_YT | STAGE_CT : CS == CS_LUV ? STAGE_UV : 0);
+    // threads per workgroup the variants are register-allocated for: as TransDistBound, the YCbCr arithmetic wants its 128 registers
+    static constexpr int bound = Y ? 512 : 1024;
+};
+
+// k_transcode's source-side loop (dec_load of the next unit behind the current one's arithmetic; not tuned here) in front of LightUnit
+template <int CS, bool SUB, int VW>
+__global__ __launch_bounds__((LightFront<CS>::bound)) void k_planes_light_level(const PlanesLightArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using Front = LightFront<CS>;
+    unsigned long long *const s_acc = light_words();
+    stage_tables<Front::WHAT>(smem, a.d.q);
+    constexpr int off = lds_table_offset<Front::WHAT>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const XformConst k = make_xform_const<CS>(a.d.sc, a.d.q.Lmax, reinterpret_cast<const PowfTablesWide *>(smem));
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+
+    LightAcc acc;
+    const LightUnit<VW> unit{acc, a.scale};
+    DecUnit<SUB, VW> cur, nxt;
+    dec_load<SUB, VW>(cur, a.d, blockIdx.x, tx, ty, NW);
+    for (int t = blockIdx.x;; t += G) {
+        const bool done = t >= a.d.g.totalTiles;        // workgroup-uniform, as the frame index is
+        light_flush(acc, s_acc, done ? -2 : t / a.d.g.tilesPerFrame, a.out);
+        if (done)
+            break;
+        if (cur.valid) {
+            float vals[3][2][VW];
+            if constexpr (Front::Y) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (k.sc_mode == 1)
+                    dec_values<CS, SUB, VW, false, true, true>(cur, a.d, k, s_lut, s_uv, vals);
+                else
+                    dec_values<CS, SUB, VW, false, true, false>(cur, a.d, k, s_lut, s_uv, vals);
+            } else {
+                dec_values<CS, SUB, VW, CS == CS_LUV>(cur, a.d, k, s_lut, s_uv, vals);
+            }
+            unit.take(vals);
+        }
+        dec_load<SUB, VW>(nxt, a.d, t + G, tx, ty, NW);
+        cur = nxt;
+    }
+}
+
 // ---- stand-alone colour transform (LumaQuantizer::transformColorSpace as public API) ---------------
 struct XfArgs {
     float *buf;

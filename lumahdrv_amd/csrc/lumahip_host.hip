@@ -1270,6 +1270,52 @@ extern "C" int lumahip_planes_moments_map_frame_host(lumahip_ctx *c, const unsig
     return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Moments, block, mom, mom_words);
 }
 
+// ---- content light level (lumahip_light_level.hip): one frame, or one frame's planes, up; one launch; the eight words down
+extern "C" int lumahip_light_level_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float scale, uint64_t out[8])
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!rgb || !out)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (w == 0 || h == 0 || (w & 1) || (h & 1))
+        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (must be even, non-zero)", w, h);
+    // (light_plan's checks of the caller's values, here too: nothing of a refused call is uploaded)
+    if (!(scale > 0.0f) || !std::isfinite(scale))
+        return fail(c, LUMAHIP_ERR_ARG, "light level: scale must be finite and > 0 (got %g)", (double)scale);
+    HIPCHK(c, hipSetDevice(c->device));
+    c->up_ramp = 0;
+    const size_t nfl = (size_t)3 * w * h;
+    int rc;
+    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
+        (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, LIGHT_WORDS * sizeof(uint64_t))))
+        return rc;
+    const SrcFrames f = packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h);
+    if ((rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) ||
+        (rc = light_level_impl(c, &f, nullptr, 1, w, h, 1.0f, scale, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
+        return rc;
+    return words_down(c, out, LIGHT_WORDS);
+}
+
+extern "C" int lumahip_planes_light_level_frame_host(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], unsigned w,
+                                                     unsigned h, int profile, float sc, float scale, uint64_t out[8])
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!planes || !stride || !out)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    if (!(scale > 0.0f) || !std::isfinite(scale))
+        return fail(c, LUMAHIP_ERR_ARG, "light level: scale must be finite and > 0 (got %g)", (double)scale);
+    StagedPlanes given{"", planes, stride, profile};
+    int rc = planes_staging(c, w, h, nullptr, given, LIGHT_WORDS);   // (the geometry, the profile and the quantizer's presence)
+    if (rc)
+        return rc;
+    const SrcPlanes pl = given.dev();
+    if ((rc = planes_up(c, given, h)) ||
+        (rc = light_level_impl(c, nullptr, &pl, 1, w, h, sc, scale, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
+        return rc;
+    return words_down(c, out, LIGHT_WORDS);
+}
+
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the
 // caller's halves go up as they are (no round-trip test, unlike the half upload above) and the decoded halves come down as the
 // kernel wrote them.

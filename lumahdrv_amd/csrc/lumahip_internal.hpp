@@ -30,6 +30,9 @@
 //   lumahip_planes_measure.hip  the twelve k_planes_distortion / k_planes_distortion_map / k_planes_moments_map kernels (two plane sets
 //                       as they are, no quantizer), their picker, planes_plan, the dispatch planes_measure_impl and the three
 //                       _device entry points of include/lumahip_compare.h
+//   lumahip_light_level.hip  the twenty k_light_level / k_planes_light_level kernels (content light level of frames as they are and of
+//                       code planes under the context's quantizer), their pickers, light_plan, the dispatch light_level_impl and the
+//                       five _device entry points of include/lumahip_compare.h
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
 //                       batched and stream push / pop forms                                               (no kernels)
@@ -490,11 +493,12 @@ int launch_fused(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, s
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
     return LUMAHIP_OK;
 }
-// ... of a measuring kernel (A::out): its words are zeroed in front of it, and nothing follows it
+// ... of a measuring kernel (A::out): its words_per_frame words per frame are zeroed in front of it, and nothing follows it
 template <typename A>
-int launch_measuring(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, size_t lds, hipStream_t s, const A &a, unsigned nframes)
+int launch_measuring(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, size_t lds, hipStream_t s, const A &a, unsigned nframes,
+                     unsigned words_per_frame = 12)
 {
-    HIPCHK(c, hipMemsetAsync(a.out, 0, out_words_bytes(nframes), s));
+    HIPCHK(c, hipMemsetAsync(a.out, 0, (size_t)nframes * words_per_frame * sizeof(uint64_t), s));   // (12: out_words_bytes(nframes))
     if (int rc = launch_fused(c, kern, grid, threads, lds, s, a))
         return rc;
     HIPCHK(c, hipGetLastError());
@@ -635,6 +639,16 @@ struct PlanesLaunch {
 // every one written by the launch.  Every error is raised before anything is queued.
 int planes_measure_impl(lumahip_ctx *c, const SrcPlanes &a, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &b, DistWhat what,
                         unsigned block, uint64_t *out, const PlanesLaunch &o);
+
+// ---- lumahip_light_level.hip: the content light level of frames or of code planes (include/lumahip_compare.h)
+struct LightLaunch {
+    hipStream_t stream;
+    bool lanes = false;   // as EncodeLaunch::lanes
+};
+// Exactly one of f (frames as they are; no quantizer read, sc ignored) and pl (code planes under the context's quantizer and sc) is
+// non-null.  lh::LIGHT_WORDS words per frame at out (zeroed in front of the launch).  Every error is raised before anything is queued.
+int light_level_impl(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, unsigned nframes, unsigned w, unsigned h, float sc, float scale,
+                     uint64_t *out, const LightLaunch &o);
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);
