@@ -1,9 +1,11 @@
 // lumahip_distortion.hip -- the frame-fed measuring calls: how far given code planes are from the planes lumahip_encode_frames_device
 // would write for the same frames, as integer sums per frame and plane (lh::k_distortion, luma_kernels.hpp), per block (k_distortion_map)
-// or as the moments of both signals per block (k_moments_map).  One plan (distortion_plan), one dispatch (measure_frames_impl) and the
-// entry points of all three; of the kernels this unit compiles the float-frame k_distortion only.  The others have a translation unit
-// each that exports their picker (lumahip_distortion_f16.hip, lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip /
-// _f16.hip): they compile side by side, and no kernel is in two code objects.
+// or as the moments of both signals per block (k_moments_map).  One plan (distortion_plan: what is this family's own -- the quantizer it
+// needs, its supported set and LDS budget, vector width, workgroup and grid; the rest is lumahip_internal.hpp's MeasureOut and shared
+// checks), one dispatch (measure_frames_impl) and the entry points of all three; of the kernels this unit compiles the float-frame
+// k_distortion only.  The others have a translation unit each that exports their picker (lumahip_distortion_f16.hip,
+// lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip / _f16.hip): they compile side by side, and no kernel is in two
+// code objects.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
@@ -12,49 +14,25 @@ using namespace lhost;
 
 namespace lhost {
 
-int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, DistWhat kind, unsigned map_block,
+int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const MeasureOut &m, const uint64_t *out,
                     hipStream_t stream, DistortionPlan &p)
 {
-    const char *const what = kind == DistWhat::Moments ? "moments map" : kind == DistWhat::Map ? "distortion map" : "distortion";
-    const char *const out_name = kind == DistWhat::Moments ? "mom_dev" : kind == DistWhat::Map ? "map_dev" : "out_dev";
-    if (kind == DistWhat::Frame)
-        map_block = 0;
-    else if (!dist_block_ok(kind, map_block))
-        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", what, kind == DistWhat::Moments ? "8, " : "", map_block);
+    const char *const what = m.call;
+    const DistWhat kind = m.kind;
+    int rc = m.check_block(c);
+    if (rc)
+        return rc;
     const bool in16 = f.elem == Elem::F16;
     const unsigned nframes = f.nframes, w = f.w, h = f.h;
     const int profile = given.profile;
-    if (!f.plane[0] || !f.plane[1] || !f.plane[2] || !given.planes || !given.stride || !given.pfs || nframes == 0)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    for (int k = 0; k < 3; k++)
-        if (!given.planes[k])
-            return fail(c, LUMAHIP_ERR_ARG, "null plane %d", k);
+    if ((rc = check_plane_sets(c, {{given}}, f.plane[0] && f.plane[1] && f.plane[2] && nframes != 0)))
+        return rc;
     const int cs = c->q.cs;
-    int rc = check_geom(c, w, h, profile, cs);
-    if (rc)
+    if ((rc = check_geom(c, w, h, profile, cs)) || (rc = check_layout(c, f, true, given.stride, given.pfs, profile)) || (rc = m.check_out(c, out)))
         return rc;
-    if ((rc = check_layout(c, f, true, given.stride, given.pfs, profile)))
-        return rc;
-    if (map_block) {
-        if (!out || !is_aligned(out, 8))
-            return fail(c, LUMAHIP_ERR_ARG, "map_dev must be non-null and 8-byte aligned");
-    } else if ((rc = check_out_words(c, out))) {
-        return rc;
-    }
-    const size_t out_bytes =
-        map_block ? (size_t)nframes * dist_map_words(w, h, map_block, dist_words_per_block(kind)) * sizeof(uint64_t) : out_words_bytes(nframes);
-    const size_t esz = elem_size(f.elem);
     bool al4;
-    if ((rc = check_frame_alignment(c, f, esz, &al4)))
+    if ((rc = check_frame_alignment(c, f, elem_size(f.elem), &al4)) || (rc = check_out_overlap(c, m, out, &f, {{given, "given "}})))
         return rc;
-    // the words may not share a byte with anything the launch reads
-    const size_t frame_span = ((size_t)(nframes - 1) * f.frame_stride + (size_t)w * h) * esz;
-    for (int k = 0; k < 3; k++) {
-        if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)f.plane[k], frame_span))
-            return fail(c, LUMAHIP_ERR_ARG, "%s overlaps colour plane %d of the frames", out_name, k);
-        if (out_overlaps_plane(out, out_bytes, given, k, w, h, nframes))
-            return fail(c, LUMAHIP_ERR_ARG, "%s overlaps given plane %d", out_name, k);
-    }
     HIPCHK(c, hipSetDevice(c->device));
     if ((rc = ensure_search_index(c, stream)))
         return rc;
@@ -67,7 +45,7 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     bool ycode = !in16 && ycbcr_composite_ready(c);
     const float *half = nullptr;
     // (+ the words the waves of a workgroup meet in: 12, or the blocks of a map tile)
-    const size_t meet = (kind == DistWhat::Moments ? MOMENTS_MAP_LDS_WORDS : kind == DistWhat::Map ? DIST_MAP_LDS_WORDS : 16) * sizeof(uint64_t);
+    const size_t meet = m.lds_bytes();
     if (in16 && ycbcr_composite_ready(c) && c->half_mode != 0 && lds_bytes(c, true, cs, true, true) + meet <= LUMAHIP_LDS_PER_WORKGROUP) {
         if ((rc = half_table_for(c, sc, &half)))
             return rc;
@@ -85,9 +63,7 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     p.vw = al4 ? 4 : 2;
     const bool long_launch = (unsigned long long)w * h * nframes >= 60000000ull;   // as the encode dispatch
     p.threads = block_threads_for(c, lds, long_launch && cs != CS_YCBCR, cs == CS_YCBCR && !half);
-    // the map: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
-    if (map_block && p.threads > 64 * (int)map_block / 2)
-        p.threads = 64 * (int)map_block / 2;
+    p.threads = m.clamp_threads(p.threads);
     p.kmode = half ? 6 : ycode ? 5 : mode;
     // ... and the moments kernels that are register-allocated for fewer threads run with at most those
     if (kind == DistWhat::Moments && p.threads > moments_threads_bound(cs, p.sub, p.vw, p.kmode))
@@ -107,67 +83,48 @@ int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlane
     p.e.sc = sc;
     read_planes(p.g, given, p.vw);
     p.e.bps = p.g.bps;
+    // grid_for's encode rule over the standard tiles
     p.grid = grid_for(c, p.threads, p.e.g.totalTiles, 0, 0, half ? 2 : cs == CS_YCBCR ? 1 : 0);
+    map_shape(m, p.e.g, p.threads, p.m, p.grid);   // (S >= 1: the workgroup is clamped above)
     return LUMAHIP_OK;
 }
 
 dist_kernel_t pick_dist_f32(int cs, bool sub, int vw, int mode) { return pick_dist<DistFamily, false>(cs, sub, vw, mode); }
 
-int measure_frames_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, DistWhat what, unsigned block, uint64_t *out,
-                        const DistortionLaunch &o)
+int measure_frames_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const MeasureOut &m, uint64_t *out,
+                        const StreamLaunch &o)
 {
     DistortionPlan p;
-    if (int rc = distortion_plan(c, f, sc, given, out, what, block, o.stream, p))
+    if (int rc = distortion_plan(c, f, sc, given, m, out, o.stream, p))
         return rc;
-    const auto no_kernel = [&](const char *name) {
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no %s kernel for colour space %d%s", name, p.cs, p.in16 ? " with binary16 frames" : "");
+    const auto no_kernel = [&] {
+        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no %s kernel for colour space %d%s", m.call, p.cs, p.in16 ? " with binary16 frames" : "");
     };
-    if (what == DistWhat::Frame) {
+    if (!m.map()) {
         DistArgs a{};
         a.e = p.e;
         a.g = p.g;
         a.out = out;
         const dist_kernel_t kern = (p.in16 ? pick_dist_f16 : pick_dist_f32)(p.cs, p.sub, p.vw, p.kmode);
-        if (!kern)
-            return no_kernel("distortion");
-        return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, f.nframes);
+        return kern ? launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a) : no_kernel();
     }
-    const bool moments = what == DistWhat::Moments;
     MapArgs a{};
     a.e = p.e;
     a.g = p.g;
     a.map = out;
-    a.m = make_map_geom(p.e.g, f.w, f.h, block, p.threads);   // (S >= 1: distortion_plan has clamped the workgroup)
-    const map_kernel_t kern = (moments ? (p.in16 ? pick_moments_map_f16 : pick_moments_map_f32)
-                                       : (p.in16 ? pick_dist_map_f16 : pick_dist_map_f32))(p.cs, p.sub, p.vw, p.kmode);
-    if (!kern)
-        return no_kernel(moments ? "moments map" : "distortion map");
-    // grid_for's encode rule over the standard tiles; a workgroup takes whole map tiles
-    const int grid = p.grid < a.m.totalMapTiles ? p.grid : a.m.totalMapTiles;
-    if (int rc = launch_fused(c, kern, grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
-        return rc;
-    HIPCHK(c, hipGetLastError());
-    return LUMAHIP_OK;
-}
-
-// what every frame-fed _device entry point does in front of the dispatch; frames_given: the packed forms' base pointer (the planar
-// forms' three pointers are distortion_plan's to check)
-static int measure_frames_entry(lumahip_ctx *c, bool frames_given, const SrcFrames &f, float sc, const SrcPlanes &given, DistWhat what,
-                                unsigned block, uint64_t *out)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!frames_given)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return measure_frames_impl(c, f, sc, given, what, block, out, {c->stream, true});
+    a.m = p.m;
+    const map_kernel_t kern = (m.kind == DistWhat::Moments ? (p.in16 ? pick_moments_map_f16 : pick_moments_map_f32)
+                                                           : (p.in16 ? pick_dist_map_f16 : pick_dist_map_f32))(p.cs, p.sub, p.vw, p.kmode);
+    return kern ? launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a) : no_kernel();
 }
 
 static int map_dims(DistWhat what, unsigned w, unsigned h, unsigned block, unsigned *nbx, unsigned *nby)
 {
-    if (!dist_block_ok(what, block) || !nbx || !nby)
+    const MeasureOut m(what, "", block, 1, w, h);
+    if (!m.block_ok() || !nbx || !nby)
         return LUMAHIP_ERR_ARG;
-    *nbx = (w + block - 1) / block;
-    *nby = (h + block - 1) / block;
+    *nbx = m.nbx();
+    *nby = m.nby();
     return LUMAHIP_OK;
 }
 
@@ -178,10 +135,15 @@ static int map_dims(DistWhat what, unsigned w, unsigned h, unsigned block, unsig
 #define MEASURE_PARAMS                                                                                                                   \
     size_t frame_stride, unsigned nframes, unsigned w, unsigned h, float sc, int profile, const unsigned char *const planes[3],         \
         const int stride[3], const size_t pfs[3]
-#define PACKED(what, block, out) \
-    measure_frames_entry(c, rgb != nullptr, packed_frames(rgb, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, DistWhat::what, block, out)
-#define PLANAR(what, block, out) \
-    measure_frames_entry(c, true, planar_frames(rgb_planes, frame_stride, nframes, w, h), sc, {planes, stride, pfs, profile}, DistWhat::what, block, out)
+#define CALL_Frame "distortion"
+#define CALL_Map "distortion map"
+#define CALL_Moments "moments map"
+#define ENTRY(given, frames, what, block, out)                                                                                          \
+    device_entry(c, given, [&](const StreamLaunch &o) {                                                                                \
+        return measure_frames_impl(c, frames, sc, {planes, stride, pfs, profile}, {DistWhat::what, CALL_##what, block, nframes, w, h}, out, o); \
+    })
+#define PACKED(what, block, out) ENTRY(rgb != nullptr, packed_frames(rgb, frame_stride, nframes, w, h), what, block, out)
+#define PLANAR(what, block, out) ENTRY(true, planar_frames(rgb_planes, frame_stride, nframes, w, h), what, block, out)
 extern "C" {
 int lumahip_distortion_frames_device(lumahip_ctx *c, const float *rgb, MEASURE_PARAMS, uint64_t *out_dev) { return PACKED(Frame, 0, out_dev); }
 int lumahip_distortion_frames_device_planar(lumahip_ctx *c, const float *const rgb_planes[3], MEASURE_PARAMS, uint64_t *out_dev) { return PLANAR(Frame, 0, out_dev); }

@@ -1010,18 +1010,14 @@ struct StagedPlanes {
 };
 
 // What those calls open with, after their null checks: the geometry against the target-side set `tgt`, the source set's profile and
-// quantizer (src = nullptr: frames in, one set), both layouts, d_planes large enough for [src][tgt] and d_arr for the `words`
-// 64-bit words of a measuring call (12; a map's; 0: none).  quantizers = false: the two sets are compared as they are (the
-// plane-to-plane measures), neither quantizer is asked for
-static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes &tgt, size_t words, bool quantizers = true)
+// quantizer (src = nullptr: frames in, one set; tgt = nullptr too: a frame alone, quantizers = false), the layouts, d_planes large
+// enough for [src][tgt].  quantizers = false: the sets are taken as they are (the plane-to-plane measures, the light level of a
+// frame), neither quantizer is asked for
+static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes *tgt, bool quantizers = true)
 {
-    int rc = LUMAHIP_OK;
-    if (quantizers)
-        rc = check_geom(c, w, h, tgt.profile, c->q.cs);
-    else if (w == 0 || h == 0 || (w & 1) || (h & 1))
-        rc = fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (must be even, non-zero)", w, h);
-    else if (tgt.profile < 0 || tgt.profile > 3)
-        rc = fail(c, LUMAHIP_ERR_ARG, "profile must be 0..3 (got %d)", tgt.profile);
+    int rc = quantizers ? check_geom(c, w, h, tgt->profile, c->q.cs) : check_size(c, w, h);
+    if (!rc && !quantizers && tgt)
+        rc = check_profile(c, tgt->profile);
     if (rc)
         return rc;
     if (src && (src->profile < 0 || src->profile > 3))
@@ -1030,7 +1026,7 @@ static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *
         return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
     HIPCHK(c, hipSetDevice(c->device));
     c->up_ramp = 0;
-    StagedPlanes *const sets[2] = {src, &tgt};
+    StagedPlanes *const sets[2] = {src, tgt};
     size_t total = 0;
     for (StagedPlanes *s : sets) {
         if (!s)
@@ -1041,8 +1037,7 @@ static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *
             return fail(c, LUMAHIP_ERR_ARG, "%splane %d: null or stride %d < row bytes %d", s->name, p, s->stride[p], s->L.row_bytes[p]);
         total += s->L.total;
     }
-    if ((rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, total)) ||
-        (words && (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, words * sizeof(uint64_t)))))
+    if (total && (rc = ensure(c, (void **)&c->d_planes, &c->d_planes_cap, total)))
         return rc;
     size_t off = 0;
     for (StagedPlanes *s : sets) {
@@ -1065,7 +1060,7 @@ static int planes_up(lumahip_ctx *c, const StagedPlanes &s, unsigned h)
 }
 
 // what the measuring calls close with: the 12 words, or a map's, down (synchronises the stream)
-static int words_down(lumahip_ctx *c, uint64_t *out, size_t words = 12)
+static int words_down(lumahip_ctx *c, uint64_t *out, size_t words)
 {
     if (words == 12)
         return read_small(c, reinterpret_cast<float *>(out), reinterpret_cast<const float *>(c->d_arr), 24, c->stream);
@@ -1088,7 +1083,7 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
     if (!src_planes || !src_stride || !dst_planes || !dst_stride)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, dst{"destination ", dst_planes, dst_stride, dst_profile};
-    int rc = planes_staging(c, w, h, &src, dst, 0);
+    int rc = planes_staging(c, w, h, &src, &dst);
     if (rc)
         return rc;
     if (!c->d_stats)
@@ -1116,82 +1111,88 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
     return LUMAHIP_OK;
 }
 
-// One float frame and given planes in host memory -> what a frame-fed measuring call delivers (lumahip_distortion.hip), synchronously:
-// the 12 distortion words (Frame; block and out_words ignored), or the frame's distortion / moments map of nbx * nby * 12 / 15 words
-static int measure_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile, const unsigned char *const planes[3],
-                              const int stride[3], DistWhat what, unsigned block, uint64_t *out, size_t out_words)
+// The one host form of the eleven measuring _frame_host entry points: one frame's inputs in host memory -> what the call delivers
+// (m, of one frame), synchronously on the context's stream.  The inputs: a float frame (frame; rgb may then not be null) and / or the
+// plane sets src and tgt as planes_staging takes them (quantizers: its flag), which the context's staging holds while `dispatch(f, d_out,
+// launch)` runs the family's device dispatch on them: f = the staged frame, d_out = m.words() device words.  scale: the light level's,
+// or nullptr.  The errors come in one order for every call: null arguments, the block, the scale, the staging's (geometry, profiles,
+// quantizers, strides), out_words below a map's words (per-frame words: ignored) -- before anything is uploaded.
+template <typename F>
+static int measure_host(lumahip_ctx *c, const MeasureOut &m, bool frame, const float *rgb, StagedPlanes *src, StagedPlanes *tgt, bool quantizers,
+                        const float *scale, uint64_t *out, size_t out_words, F dispatch)
 {
     if (!c)
         return LUMAHIP_ERR_ARG;
-    if (!rgb || !planes || !stride || !out)
+    if ((frame && !rgb) || (src && (!src->planes || !src->stride)) || (tgt && (!tgt->planes || !tgt->stride)) || !out)
         return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const bool map = what != DistWhat::Frame, moments = what == DistWhat::Moments;
-    const char *const name = moments ? "moments map" : "distortion map";
-    if (map && !dist_block_ok(what, block))
-        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", name, moments ? "8, " : "", block);
-    StagedPlanes given{"", planes, stride, profile};
-    const size_t nfl = (size_t)3 * w * h, words = map ? dist_map_words(w, h, block, dist_words_per_block(what)) : 12;
-    int rc = planes_staging(c, w, h, nullptr, given, words);
-    if (rc)
+    int rc;
+    // (the scale's test sits where it always sat: behind the size of a frame that comes alone, in front of a plane set's staging)
+    if ((rc = m.check_block(c)) || (scale && ((!tgt && (rc = check_size(c, m.w, m.h))) || (rc = check_light_scale(c, *scale)))) ||
+        (rc = planes_staging(c, m.w, m.h, src, tgt, quantizers)))
         return rc;
-    if (map && out_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", name, out_words, words);
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
-        (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) || (rc = planes_up(c, given, h)) ||
-        (rc = measure_frames_impl(c, packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h), sc, given.dev(), what, block,
-                                  reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
+    // (the words' count needs a checked geometry)
+    if (m.map() && out_words < m.words())
+        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", m.call, out_words, m.words());
+    const size_t nfl = (size_t)3 * m.w * m.h;
+    if ((rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, m.bytes())) ||
+        (frame && ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
+                   (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))) ||
+        (src && (rc = planes_up(c, *src, m.h))) || (tgt && (rc = planes_up(c, *tgt, m.h))) ||
+        (rc = dispatch(packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, m.w, m.h), reinterpret_cast<uint64_t *>(c->d_arr),
+                       StreamLaunch{c->stream, false})))
         return rc;
-    return words_down(c, out, words);
+    return words_down(c, out, m.words());
 }
 
-// Source planes and given planes in host memory -> what a plane-fed measuring call delivers (lumahip_transcode.hip), synchronously:
-// the 12 words of the transcode distortion (Measure), or the frame's transcode distortion / moments map of nbx * nby * 12 / 15 words
-// (Map / Moments); the context's plane staging holds both sets
-static int measure_planes_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile, float src_sc,
-                               unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
-                               float dst_sc, TransWhat what, unsigned block, uint64_t *out, size_t out_words)
+// ... of the frame-fed calls (lumahip_distortion.hip): one float frame and given planes
+static int measure_frame_host(lumahip_ctx *c, const float *rgb, float sc, int profile, const unsigned char *const planes[3], const int stride[3],
+                              const MeasureOut &m, uint64_t *out, size_t out_words)
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!src_planes || !src_stride || !given_planes || !given_stride || !out)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const bool map = trans_is_map(what), moments = what == TransWhat::Moments;
-    const DistWhat kind = moments ? DistWhat::Moments : DistWhat::Map;   // (of a map mode)
-    const char *const name = moments ? "transcode moments map" : "transcode distortion map";
-    if (map && !dist_block_ok(kind, block))
-        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", name, moments ? "8, " : "", block);
+    StagedPlanes given{"", planes, stride, profile};
+    return measure_host(c, m, true, rgb, nullptr, &given, true, nullptr, out, out_words, [&](const SrcFrames &f, uint64_t *d, const StreamLaunch &o) {
+        return measure_frames_impl(c, f, sc, given.dev(), m, d, o);
+    });
+}
+
+// ... of the plane-fed calls (lumahip_transcode.hip): source planes and given planes
+static int measure_planes_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile, float src_sc,
+                               const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile, float dst_sc,
+                               const MeasureOut &m, uint64_t *out, size_t out_words)
+{
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
-    const size_t words = map ? dist_map_words(w, h, block, dist_words_per_block(kind)) : 12;
-    int rc = planes_staging(c, w, h, &src, given, words);
-    if (rc)
-        return rc;
-    if (map && out_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", name, out_words, words);
-    if ((rc = planes_up(c, src, h)) || (rc = planes_up(c, given, h)) ||
-        (rc = measure_planes_impl(c, src.dev(), src_sc, 1, w, h, given.dev(), dst_sc, what, block, reinterpret_cast<uint64_t *>(c->d_arr),
-                                  {c->stream, false})))
-        return rc;
-    return words_down(c, out, words);
+    return measure_host(c, m, false, nullptr, &src, &given, true, nullptr, out, out_words, [&](const SrcFrames &, uint64_t *d, const StreamLaunch &o) {
+        return measure_planes_impl(c, src.dev(), src_sc, given.dev(), dst_sc, m, d, o);
+    });
+}
+
+// ... of the plane-to-plane calls (lumahip_planes_measure.hip): two plane sets of one profile; no quantizer is read
+static int compare_planes_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3], const unsigned char *const b_planes[3],
+                               const int b_stride[3], int profile, const MeasureOut &m, uint64_t *out, size_t out_words)
+{
+    StagedPlanes a{"set A ", a_planes, a_stride, profile}, b{"set B ", b_planes, b_stride, profile};
+    return measure_host(c, m, false, nullptr, &a, &b, false, nullptr, out, out_words, [&](const SrcFrames &, uint64_t *d, const StreamLaunch &o) {
+        return planes_measure_impl(c, a.dev(), b.dev(), m, d, o);
+    });
 }
 
 extern "C" int lumahip_distortion_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                              const unsigned char *const planes[3], const int stride[3], uint64_t out[12])
 {
-    return measure_frame_host(c, rgb, w, h, sc, profile, planes, stride, DistWhat::Frame, 0, out, 12);
+    return measure_frame_host(c, rgb, sc, profile, planes, stride, {DistWhat::Frame, "distortion", 0, 1, w, h}, out, 12);
 }
 
 extern "C" int lumahip_distortion_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                                  const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *map,
                                                  size_t map_words)
 {
-    return measure_frame_host(c, rgb, w, h, sc, profile, planes, stride, DistWhat::Map, block, map, map_words);
+    return measure_frame_host(c, rgb, sc, profile, planes, stride, {DistWhat::Map, "distortion map", block, 1, w, h}, map, map_words);
 }
 
 extern "C" int lumahip_moments_map_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float sc, int profile,
                                               const unsigned char *const planes[3], const int stride[3], unsigned block, uint64_t *mom,
                                               size_t mom_words)
 {
-    return measure_frame_host(c, rgb, w, h, sc, profile, planes, stride, DistWhat::Moments, block, mom, mom_words);
+    return measure_frame_host(c, rgb, sc, profile, planes, stride, {DistWhat::Moments, "moments map", block, 1, w, h}, mom, mom_words);
 }
 
 extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
@@ -1199,8 +1200,8 @@ extern "C" int lumahip_transcode_distortion_frame_host(lumahip_ctx *c, const uns
                                                        const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile,
                                                        float dst_sc, uint64_t out[12])
 {
-    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
-                               TransWhat::Measure, 0, out, 12);
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, given_planes, given_stride, dst_profile, dst_sc,
+                               {DistWhat::Frame, "transcode distortion", 0, 1, w, h}, out, 12);
 }
 
 extern "C" int lumahip_transcode_distortion_map_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
@@ -1208,8 +1209,8 @@ extern "C" int lumahip_transcode_distortion_map_frame_host(lumahip_ctx *c, const
                                                            const unsigned char *const given_planes[3], const int given_stride[3],
                                                            int dst_profile, float dst_sc, unsigned block, uint64_t *map, size_t map_words)
 {
-    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
-                               TransWhat::Map, block, map, map_words);
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, given_planes, given_stride, dst_profile, dst_sc,
+                               {DistWhat::Map, "transcode distortion map", block, 1, w, h}, map, map_words);
 }
 
 extern "C" int lumahip_transcode_moments_map_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
@@ -1217,103 +1218,51 @@ extern "C" int lumahip_transcode_moments_map_frame_host(lumahip_ctx *c, const un
                                                         const unsigned char *const given_planes[3], const int given_stride[3],
                                                         int dst_profile, float dst_sc, unsigned block, uint64_t *mom, size_t mom_words)
 {
-    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, w, h, given_planes, given_stride, dst_profile, dst_sc,
-                               TransWhat::Moments, block, mom, mom_words);
-}
-
-// Two plane sets of one frame in host memory -> what a plane-to-plane measuring call delivers (lumahip_planes_measure.hip),
-// synchronously: the 12 distortion words (Frame; block and out_words ignored), or the frame's distortion / moments map of
-// nbx * nby * 12 / 15 words; the context's plane staging holds both sets.  No quantizer is read.
-static int compare_planes_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w, unsigned h,
-                               const unsigned char *const b_planes[3], const int b_stride[3], int profile, DistWhat what, unsigned block,
-                               uint64_t *out, size_t out_words)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!a_planes || !a_stride || !b_planes || !b_stride || !out)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    const bool map = what != DistWhat::Frame, moments = what == DistWhat::Moments;
-    const char *const name = moments ? "planes moments map" : "planes distortion map";
-    if (map && !dist_block_ok(what, block))
-        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", name, moments ? "8, " : "", block);
-    StagedPlanes a{"set A ", a_planes, a_stride, profile}, b{"set B ", b_planes, b_stride, profile};
-    int rc = planes_staging(c, w, h, &a, b, 0, false);   // (the words' count needs a checked geometry)
-    if (rc)
-        return rc;
-    const size_t words = map ? dist_map_words(w, h, block, dist_words_per_block(what)) : 12;
-    if (map && out_words < words)
-        return fail(c, LUMAHIP_ERR_ARG, "%s: %zu words for a map of %zu", name, out_words, words);
-    if ((rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, words * sizeof(uint64_t))) || (rc = planes_up(c, a, h)) || (rc = planes_up(c, b, h)) ||
-        (rc = planes_measure_impl(c, a.dev(), 1, w, h, b.dev(), what, block, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
-        return rc;
-    return words_down(c, out, words);
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, given_planes, given_stride, dst_profile, dst_sc,
+                               {DistWhat::Moments, "transcode moments map", block, 1, w, h}, mom, mom_words);
 }
 
 extern "C" int lumahip_planes_distortion_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w,
                                                     unsigned h, const unsigned char *const b_planes[3], const int b_stride[3], int profile,
                                                     uint64_t out[12])
 {
-    return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Frame, 0, out, 12);
+    return compare_planes_host(c, a_planes, a_stride, b_planes, b_stride, profile, {DistWhat::Frame, "planes distortion", 0, 1, w, h}, out, 12);
 }
 
 extern "C" int lumahip_planes_distortion_map_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3],
                                                         unsigned w, unsigned h, const unsigned char *const b_planes[3], const int b_stride[3],
                                                         int profile, unsigned block, uint64_t *map, size_t map_words)
 {
-    return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Map, block, map, map_words);
+    return compare_planes_host(c, a_planes, a_stride, b_planes, b_stride, profile, {DistWhat::Map, "planes distortion map", block, 1, w, h}, map,
+                               map_words);
 }
 
 extern "C" int lumahip_planes_moments_map_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3],
                                                      unsigned w, unsigned h, const unsigned char *const b_planes[3], const int b_stride[3],
                                                      int profile, unsigned block, uint64_t *mom, size_t mom_words)
 {
-    return compare_planes_host(c, a_planes, a_stride, w, h, b_planes, b_stride, profile, DistWhat::Moments, block, mom, mom_words);
+    return compare_planes_host(c, a_planes, a_stride, b_planes, b_stride, profile, {DistWhat::Moments, "planes moments map", block, 1, w, h}, mom,
+                               mom_words);
 }
 
 // ---- content light level (lumahip_light_level.hip): one frame, or one frame's planes, up; one launch; the eight words down
 extern "C" int lumahip_light_level_frame_host(lumahip_ctx *c, const float *rgb, unsigned w, unsigned h, float scale, uint64_t out[8])
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!rgb || !out)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    if (w == 0 || h == 0 || (w & 1) || (h & 1))
-        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (must be even, non-zero)", w, h);
-    // (light_plan's checks of the caller's values, here too: nothing of a refused call is uploaded)
-    if (!(scale > 0.0f) || !std::isfinite(scale))
-        return fail(c, LUMAHIP_ERR_ARG, "light level: scale must be finite and > 0 (got %g)", (double)scale);
-    HIPCHK(c, hipSetDevice(c->device));
-    c->up_ramp = 0;
-    const size_t nfl = (size_t)3 * w * h;
-    int rc;
-    if ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
-        (rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, LIGHT_WORDS * sizeof(uint64_t))))
-        return rc;
-    const SrcFrames f = packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, w, h);
-    if ((rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)) ||
-        (rc = light_level_impl(c, &f, nullptr, 1, w, h, 1.0f, scale, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
-        return rc;
-    return words_down(c, out, LIGHT_WORDS);
+    const MeasureOut m(DistWhat::Light, "light level", 0, 1, w, h);
+    return measure_host(c, m, true, rgb, nullptr, nullptr, false, &scale, out, 0, [&](const SrcFrames &f, uint64_t *d, const StreamLaunch &o) {
+        return light_level_impl(c, &f, nullptr, 1.0f, scale, m, d, o);
+    });
 }
 
 extern "C" int lumahip_planes_light_level_frame_host(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], unsigned w,
                                                      unsigned h, int profile, float sc, float scale, uint64_t out[8])
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!planes || !stride || !out)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    if (!(scale > 0.0f) || !std::isfinite(scale))
-        return fail(c, LUMAHIP_ERR_ARG, "light level: scale must be finite and > 0 (got %g)", (double)scale);
-    StagedPlanes given{"", planes, stride, profile};
-    int rc = planes_staging(c, w, h, nullptr, given, LIGHT_WORDS);   // (the geometry, the profile and the quantizer's presence)
-    if (rc)
-        return rc;
-    const SrcPlanes pl = given.dev();
-    if ((rc = planes_up(c, given, h)) ||
-        (rc = light_level_impl(c, nullptr, &pl, 1, w, h, sc, scale, reinterpret_cast<uint64_t *>(c->d_arr), {c->stream, false})))
-        return rc;
-    return words_down(c, out, LIGHT_WORDS);
+    const MeasureOut m(DistWhat::Light, "light level", 0, 1, w, h);
+    StagedPlanes given{"", planes, stride, profile};   // (staged under the quantizer's demands: the geometry, the profile, its presence)
+    return measure_host(c, m, false, nullptr, nullptr, &given, true, &scale, out, 0, [&](const SrcFrames &, uint64_t *d, const StreamLaunch &o) {
+        const SrcPlanes pl = given.dev();
+        return light_level_impl(c, nullptr, &pl, sc, scale, m, d, o);
+    });
 }
 
 // ---- binary16 frames (halves by type): 6 B per pixel cross PCIe in either direction.  One piece, on the context's stream: the

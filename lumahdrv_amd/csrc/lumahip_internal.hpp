@@ -33,9 +33,15 @@
 //   lumahip_light_level.hip  the twenty k_light_level / k_planes_light_level kernels (content light level of frames as they are and of
 //                       code planes under the context's quantizer), their pickers, light_plan, the dispatch light_level_impl and the
 //                       five _device entry points of include/lumahip_compare.h
+//   The four plans of the measuring calls (transcode_plan, distortion_plan, planes_plan, light_plan) keep what is a family's own:
+//   the quantizers it needs, its supported set and LDS budget, vector width, the workgroup bound and grid_for's arguments.  What a
+//   launch delivers -- words, the output's name in messages, valid blocks, LDS to meet in, zeroed or not -- is one record, MeasureOut,
+//   below; the checks of the plane sets, the size, the layout, the output pointer and its overlaps, the map's shape (map_shape), the
+//   closing launch (launch_measure), the launch options (StreamLaunch) and the entry helper (device_entry) stand beside it, once.
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
-//                       batched and stream push / pop forms                                               (no kernels)
+//                       batched and stream push / pop forms, the one host form of the eleven measuring calls (measure_host)
+//                                                                                                         (no kernels)
 //   lumahip_pool.hip    the HBM chunk pool;  lumahip_multi.hip  many GPUs in one process                  (no kernels)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -439,17 +445,102 @@ static inline size_t plane_extent(unsigned w, unsigned h, int profile, int p, in
 }
 static inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 static inline bool ranges_overlap(uintptr_t a, size_t na, uintptr_t b, size_t nb) { return a < b + nb && b < a + na; }
-// ---- the 12 words per frame of the measuring calls (out_dev)
-static inline size_t out_words_bytes(unsigned nframes) { return (size_t)nframes * 12 * sizeof(uint64_t); }
-static inline int check_out_words(lumahip_ctx *c, const uint64_t *out)
+
+// ---- what a measuring launch delivers: the one record every measuring call builds, once, from its kind, its name in messages, its
+// block and its geometry, and hands to its plan, its closing launch and (the host forms) its staging.
+//   Frame    12 words per frame (block ignored), zeroed in front of the launch, 16 words of LDS to meet in;
+//   Map      the distortion map -- blocks of 16, 32 or 64 luma pixels, 12 words each, every one written by the launch,
+//            lh::DIST_MAP_LDS_WORDS of LDS;
+//   Moments  the moments map -- blocks of 8, 16, 32 or 64, 15 words each, every one written by the launch, lh::MOMENTS_MAP_LDS_WORDS;
+//   Light    the content light level -- lh::LIGHT_WORDS words per frame (block ignored), zeroed in front of the launch, as many of LDS.
+enum class DistWhat { Frame, Map, Moments, Light };
+struct MeasureOut {
+    DistWhat kind;
+    const char *call;   // in messages: "distortion map", "transcode moments map", "planes distortion", ...
+    unsigned block, nframes, w, h;
+    MeasureOut(DistWhat kind_, const char *call_, unsigned block_, unsigned nframes_, unsigned w_, unsigned h_)
+        : kind(kind_), call(call_), block(kind_ == DistWhat::Map || kind_ == DistWhat::Moments ? block_ : 0), nframes(nframes_), w(w_), h(h_)
+    {
+    }
+    bool map() const { return kind == DistWhat::Map || kind == DistWhat::Moments; }
+    bool block_ok() const { return !map() || block == 16 || block == 32 || block == 64 || (kind == DistWhat::Moments && block == 8); }
+    // the first error of every call that takes a block
+    int check_block(lumahip_ctx *c) const
+    {
+        return block_ok() ? LUMAHIP_OK
+                          : fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", call, kind == DistWhat::Moments ? "8, " : "", block);
+    }
+    unsigned nbx() const { return (w + block - 1) / block; }   // (of a map with a valid block)
+    unsigned nby() const { return (h + block - 1) / block; }
+    size_t words_per_block() const { return kind == DistWhat::Moments ? 15 : 12; }
+    size_t words_per_frame() const { return map() ? (size_t)nbx() * nby() * words_per_block() : kind == DistWhat::Light ? (size_t)LIGHT_WORDS : 12; }
+    size_t words() const { return (size_t)nframes * words_per_frame(); }
+    size_t bytes() const { return words() * sizeof(uint64_t); }
+    const char *out_name() const { return kind == DistWhat::Moments ? "mom_dev" : kind == DistWhat::Map ? "map_dev" : "out_dev"; }
+    // the words the waves of a workgroup meet in (static LDS of the kernels, counted in every LDS budget)
+    size_t lds_bytes() const
+    {
+        return (kind == DistWhat::Moments ? (size_t)MOMENTS_MAP_LDS_WORDS : kind == DistWhat::Map ? (size_t)DIST_MAP_LDS_WORDS
+                : kind == DistWhat::Light ? (size_t)LIGHT_WORDS : 16) * sizeof(uint64_t);
+    }
+    bool zeroed() const { return !map(); }   // in front of the launch; a map's words are all written by it
+    // the two maps: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
+    int clamp_threads(int threads) const { return map() ? std::min(threads, 32 * (int)block) : threads; }
+    // out: non-null and 8-byte aligned
+    int check_out(lumahip_ctx *c, const uint64_t *out) const
+    {
+        return (!out || !is_aligned(out, 8)) ? fail(c, LUMAHIP_ERR_ARG, "%s must be non-null and 8-byte aligned", out_name()) : LUMAHIP_OK;
+    }
+};
+
+// ---- the checks the plans of the measuring calls (and of the transcode) share
+// a set of code planes a launch reads and what its planes are called in messages: pre + "plane k" + post
+struct PlaneSet {
+    const SrcPlanes &p;
+    const char *pre = "", *post = "";
+};
+// every set's three arrays (and whatever else the family wants non-null: others_given) -> "null argument"; then plane k of every set
+static inline int check_plane_sets(lumahip_ctx *c, std::initializer_list<PlaneSet> sets, bool others_given)
 {
-    return (!out || !is_aligned(out, 8)) ? fail(c, LUMAHIP_ERR_ARG, "out_dev must be non-null and 8-byte aligned") : LUMAHIP_OK;
+    for (const PlaneSet &s : sets)
+        others_given = others_given && s.p.planes && s.p.stride && s.p.pfs;
+    if (!others_given)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    for (int k = 0; k < 3; k++)
+        for (const PlaneSet &s : sets)
+            if (!s.p.planes[k])
+                return fail(c, LUMAHIP_ERR_ARG, "null plane %d", k);
+    return LUMAHIP_OK;
 }
-// out_dev may not share a byte with anything the launch reads: here, plane k of a set of code planes over the batch
-// (out_bytes: out_words_bytes(nframes), or the bytes of a distortion map)
-static inline bool out_overlaps_plane(const uint64_t *out, size_t out_bytes, const SrcPlanes &p, int k, unsigned w, unsigned h, unsigned nframes)
+// check_geom's tests of the size and of the profile, without its demand for a quantizer
+static inline int check_size(lumahip_ctx *c, unsigned w, unsigned h)
 {
-    return ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)p.planes[k], plane_extent(w, h, p.profile, k, p.stride[k], p.pfs[k], nframes));
+    return (w == 0 || h == 0 || (w & 1) || (h & 1)) ? fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (must be even, non-zero)", w, h) : LUMAHIP_OK;
+}
+static inline int check_profile(lumahip_ctx *c, int profile)
+{
+    return (profile < 0 || profile > 3) ? fail(c, LUMAHIP_ERR_ARG, "profile must be 0..3 (got %d)", profile) : LUMAHIP_OK;
+}
+// a plane set's strides and frame strides against (nframes, w, h)
+static inline int check_planes_layout(lumahip_ctx *c, const SrcPlanes &p, unsigned nframes, unsigned w, unsigned h)
+{
+    const SrcFrames geom{{nullptr, nullptr, nullptr}, Elem::F32, 0, nframes, w, h};   // (check_layout reads the geometry only)
+    return check_layout(c, geom, false, p.stride, p.pfs, p.profile);
+}
+// The words may not share a byte with anything the launch reads, judged by the byte count of what it writes: colour plane k of the
+// frames (f may be null), then plane k of every set, k = 0, 1, 2
+static inline int check_out_overlap(lumahip_ctx *c, const MeasureOut &m, const uint64_t *out, const SrcFrames *f, std::initializer_list<PlaneSet> sets)
+{
+    const size_t frame_span = f ? ((size_t)(m.nframes - 1) * f->frame_stride + (size_t)m.w * m.h) * elem_size(f->elem) : 0;
+    for (int k = 0; k < 3; k++) {
+        if (f && ranges_overlap((uintptr_t)out, m.bytes(), (uintptr_t)f->plane[k], frame_span))
+            return fail(c, LUMAHIP_ERR_ARG, "%s overlaps colour plane %d of the frames", m.out_name(), k);
+        for (const PlaneSet &s : sets)
+            if (ranges_overlap((uintptr_t)out, m.bytes(), (uintptr_t)s.p.planes[k],
+                               plane_extent(m.w, m.h, s.p.profile, k, s.p.stride[k], s.p.pfs[k], m.nframes)))
+                return fail(c, LUMAHIP_ERR_ARG, "%s overlaps %splane %d%s", m.out_name(), s.pre, k, s.post);
+    }
+    return LUMAHIP_OK;
 }
 // every base, stride and frame stride of these planes takes the vector accesses of VW pixels per thread and row
 template <typename B>
@@ -493,16 +584,56 @@ int launch_fused(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, s
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, a);
     return LUMAHIP_OK;
 }
-// ... of a measuring kernel (A::out): its words_per_frame words per frame are zeroed in front of it, and nothing follows it
+// ... of a measuring kernel, the one way every measuring dispatch closes: the words at out (what the kernel's arguments name out or
+// map) are zeroed in front of it where the record says so, and nothing follows it
 template <typename A>
-int launch_measuring(lumahip_ctx *c, void (*kern)(const A), int grid, int threads, size_t lds, hipStream_t s, const A &a, unsigned nframes,
-                     unsigned words_per_frame = 12)
+int launch_measure(lumahip_ctx *c, const MeasureOut &m, uint64_t *out, void (*kern)(const A), int grid, int threads, size_t lds, hipStream_t s,
+                   const A &a)
 {
-    HIPCHK(c, hipMemsetAsync(a.out, 0, (size_t)nframes * words_per_frame * sizeof(uint64_t), s));   // (12: out_words_bytes(nframes))
+    if (m.zeroed())
+        HIPCHK(c, hipMemsetAsync(out, 0, m.bytes(), s));
     if (int rc = launch_fused(c, kern, grid, threads, lds, s, a))
         return rc;
     HIPCHK(c, hipGetLastError());
     return LUMAHIP_OK;
+}
+// What the two maps add to a plan behind grid_for (whose rule runs over the standard tiles): the map's geometry -- threads = the
+// workgroup, clamped by MeasureOut::clamp_threads in front of make_geom -- and a grid of at most its tiles: a workgroup takes whole ones
+static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsigned h, unsigned block, int threads)
+{
+    lh::MapGeom m{};
+    m.B = (int)block;
+    m.S = (int)block / (2 * (threads / 64));
+    m.nbx = (int)((w + block - 1) / block);
+    m.nby = (int)((h + block - 1) / block);
+    m.mapTilesPerFrame = m.nby * g.tilesX;
+    m.totalMapTiles = m.mapTilesPerFrame * g.nframes;   // (<= the standard tiles, which make_geom has bounded)
+    return m;
+}
+static inline void map_shape(const MeasureOut &m, const lh::FrameGeom &g, int threads, lh::MapGeom &mg, int &grid)
+{
+    if (!m.map())
+        return;
+    mg = make_map_geom(g, m.w, m.h, m.block, threads);
+    grid = std::min(grid, mg.totalMapTiles);
+}
+
+// How a _device dispatch is launched (the transcode and every measuring call): stream as EncodeLaunch::stream, lanes as
+// EncodeLaunch::lanes
+struct StreamLaunch {
+    hipStream_t stream;
+    bool lanes = false;
+};
+// What their _device entry points do in front of the dispatch: the context; args_given: the packed forms' base pointer (the planar
+// forms' three pointers and the plane sets are the plans' to check)
+template <typename F>
+static inline int device_entry(lumahip_ctx *c, bool args_given, F dispatch)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!args_given)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    return dispatch(StreamLaunch{c->stream, true});
 }
 
 // ---- lumahip_encode.hip / lumahip_decode.hip
@@ -521,13 +652,9 @@ enc_kernel_t pick_enc_f16(int cs, bool sub, int vw, int mode);
 dec_kernel_t pick_dec_f16(int cs, bool sub, int vw, bool gl, bool yt, bool rb);
 
 // ---- lumahip_transcode.hip
-struct TranscodeLaunch {
-    hipStream_t stream;
-    bool lanes = false;   // as EncodeLaunch::lanes
-};
 // source planes under the context's source quantizer and src_sc -> destination planes under its quantizer and dst_sc
 int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
-                   float *stats, const TranscodeLaunch &o);
+                   float *stats, const StreamLaunch &o);
 typedef void (*trans_kernel_t)(const lh::TransArgs);
 // What transcode_plan decides for a launch over (source planes, target-side planes): the kernel's key (colour spaces,
 // subsamplings, vector width, the target's search mode as pick_planes takes it), the launch shape and the kernel arguments of both
@@ -538,30 +665,20 @@ struct TranscodePlan {
     size_t lds;      // dynamic LDS of the launch (the measuring kernels' words are static and counted in the budget)
     lh::DecArgs d;   // q, g, src, stride, src_frame_stride, sc, bps, aligned of the source planes
     lh::EncArgs e;   // q (the composite records for kmode 5), g, sc, bps, aligned of the target side
-    lh::MapGeom m;   // TransWhat::Map / Moments only
+    lh::MapGeom m;   // the two maps only
 };
-enum class TransWhat { Store, Measure, Map, Moments };
-static inline bool trans_is_map(TransWhat what) { return what == TransWhat::Map || what == TransWhat::Moments; }
-// Store: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one), out is ignored;
-// Measure: tgt are the given planes of lumahip_transcode_distortion_frames_device (read only: any overlap with the source
-// is fine), out its 12 * nframes words (non-null, 8-byte aligned, sharing no byte with either plane set), the workgroup is
-// clamped to the measuring kernels' launch bound;
-// Map: as Measure with out = the map of lumahip_transcode_distortion_map_frames_device (its own byte count is what may not
-// overlap), map_block 16, 32 or 64, lh::DIST_MAP_LDS_WORDS of LDS to meet in, the workgroup clamped further to 32 * map_block
-// threads and the grid to the number of map tiles;
-// Moments: as Map with out = the map of lumahip_transcode_moments_map_frames_device -- map_block 8, 16, 32 or 64, 15 words per block,
-// lh::MOMENTS_MAP_LDS_WORDS of LDS, the workgroup clamped to its kernels' launch bound (lh::transmoments_threads_bound) in the place
-// of the measuring kernels'.  Every error is raised here, the block size first, before anything of the launch is queued.
+// m == nullptr, the storing transcode: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one),
+// out is ignored.  Else a measuring call and what it delivers (MeasureOut; its nframes, w, h are the arguments'): tgt are the given
+// planes (read only: any overlap with the source is fine), out its words (non-null, 8-byte aligned, sharing no byte with either plane
+// set), the workgroup is clamped to the measuring kernels' launch bound -- the moments map's: to lh::transmoments_threads_bound in its
+// place -- and, the two maps, by the record's rule; their grid to the number of map tiles.  Every error is raised here, the block
+// size first, before anything of the launch is queued.
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
-                   TransWhat mode, const uint64_t *out, unsigned map_block, hipStream_t stream, TranscodePlan &p);
+                   const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 
 // ---- lumahip_distortion.hip: the frame-fed measuring calls
-struct DistortionLaunch {
-    hipStream_t stream;
-    bool lanes = false;   // as EncodeLaunch::lanes
-};
 // What distortion_plan decides for a launch that scores given planes against the frames' encode: the kernel's key as pick_dist
 // takes it, the launch shape and the kernel arguments of both sides
 struct DistortionPlan {
@@ -570,43 +687,19 @@ struct DistortionPlan {
     size_t lds;      // dynamic LDS of the launch (the words the waves meet in are static and counted in the budget)
     lh::EncArgs e;   // DistArgs::e
     lh::DecArgs g;   // DistArgs::g
+    lh::MapGeom m;   // the two maps only
 };
-// What the launch delivers.  Frame: the 12 words per frame (map_block ignored).  Map: the distortion map -- blocks of 16, 32 or 64,
-// 12 words each, lh::DIST_MAP_LDS_WORDS of LDS to meet in.  Moments: the moments map -- blocks of 8, 16, 32 or 64, 15 words each,
-// lh::MOMENTS_MAP_LDS_WORDS of LDS, the workgroup clamped to its kernels' launch bound (lh::moments_threads_bound).
-enum class DistWhat { Frame, Map, Moments };
-static inline int dist_words_per_block(DistWhat what) { return what == DistWhat::Moments ? 15 : 12; }
-static inline bool dist_map_block_ok(unsigned block) { return block == 16 || block == 32 || block == 64; }
-static inline bool dist_block_ok(DistWhat what, unsigned block) { return dist_map_block_ok(block) || (what == DistWhat::Moments && block == 8); }
-static inline size_t dist_map_words(unsigned w, unsigned h, unsigned block, int per_block = 12)
-{
-    return (size_t)((w + block - 1) / block) * ((h + block - 1) / block) * per_block;
-}
-// out: the launch's words (non-null, 8-byte aligned, sharing no byte with the frames or the given planes -- judged by the byte
-// count of what the launch writes); the workgroup of the two maps is clamped to a power of two of at most 64 * map_block / 2
-// threads (a map tile is a whole number of standard tiles).  Every error is raised here, the block size first, before anything of
-// the launch is queued.
-int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const uint64_t *out, DistWhat what, unsigned map_block,
+// m: what the launch delivers (its nframes, w, h are f's); out: its words (non-null, 8-byte aligned, sharing no byte with the frames
+// or the given planes); the workgroup of the two maps is clamped by the record's rule (a map tile is a whole number of standard
+// tiles), the moments map's also to its kernels' launch bound (lh::moments_threads_bound).  Every error is raised here, the block
+// size first, before anything of the launch is queued.
+int distortion_plan(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const MeasureOut &m, const uint64_t *out,
                     hipStream_t stream, DistortionPlan &p);
 
-// what the map kernels' helpers read beside g, the launch's frame-major geometry; threads = its workgroup, a power of two of at most 32 * block
-static inline lh::MapGeom make_map_geom(const lh::FrameGeom &g, unsigned w, unsigned h, unsigned block, int threads)
-{
-    lh::MapGeom m{};
-    m.B = (int)block;
-    m.S = (int)block / (2 * (threads / 64));
-    m.nbx = (int)((w + block - 1) / block);
-    m.nby = (int)((h + block - 1) / block);
-    m.mapTilesPerFrame = m.nby * g.tilesX;
-    m.totalMapTiles = m.mapTilesPerFrame * g.nframes;   // (<= the standard tiles, which make_geom has bounded)
-    return m;
-}
-
-// The one dispatch of the frame-fed measuring calls: the frames of f under the context's quantizer and sc against the given planes.
-// Frame: 12 words per frame at out (zeroed in front of the launch; block ignored); Map / Moments: nframes * nby * nbx * 12 / 15 words,
-// every one written by the launch
-int measure_frames_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, DistWhat what, unsigned block, uint64_t *out,
-                        const DistortionLaunch &o);
+// The one dispatch of the frame-fed measuring calls: the frames of f under the context's quantizer and sc against the given planes,
+// m.words() words at out
+int measure_frames_impl(lumahip_ctx *c, const SrcFrames &f, float sc, const SrcPlanes &given, const MeasureOut &m, uint64_t *out,
+                        const StreamLaunch &o);
 // pick_dist<Family, IN16> of lumahip_pick.hpp as the six kernel units export it (each compiles the kernels it names, side by side with
 // the others): lumahip_distortion.hip / _f16.hip, lumahip_distortion_map.hip / _f16.hip, lumahip_moments_map.hip / _f16.hip
 typedef void (*dist_kernel_t)(const lh::DistArgs);
@@ -616,11 +709,10 @@ map_kernel_t pick_dist_map_f32(int cs, bool sub, int vw, int mode), pick_dist_ma
 map_kernel_t pick_moments_map_f32(int cs, bool sub, int vw, int mode), pick_moments_map_f16(int cs, bool sub, int vw, int mode);
 
 // ---- lumahip_transcode.hip: the plane-fed measuring calls
-// The one dispatch of both: the source planes' transcode (transcode_impl's planes, never written) against the given planes.
-// what: Measure -- 12 words per frame at out (zeroed in front of the launch; block ignored) -- or Map / Moments -- nframes * nby * nbx *
-// 12 / 15 words, every one written by the launch
-int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
-                        float dst_sc, TransWhat what, unsigned block, uint64_t *out, const TranscodeLaunch &o);
+// The one dispatch of the three: the source planes' transcode (transcode_impl's planes, never written) against the given planes,
+// m.words() words at out; m carries nframes, w, h
+int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, const SrcPlanes &given, float dst_sc, const MeasureOut &m, uint64_t *out,
+                        const StreamLaunch &o);
 // pick_planes<TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, vw> of lumahip_pick.hpp as lumahip_transcode_distortion.hip /
 // lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip export it (each compiles the 48 kernels it names)
 typedef void (*transdist_kernel_t)(const lh::TransDistArgs);
@@ -630,25 +722,21 @@ transdist_map_kernel_t pick_transdist_map(int vw, int csd, bool subd, int cse, b
 transdist_map_kernel_t pick_transdist_moments_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
 
 // ---- lumahip_planes_measure.hip: two plane sets as they are (include/lumahip_compare.h)
-struct PlanesLaunch {
-    hipStream_t stream;
-    bool lanes = false;   // as EncodeLaunch::lanes
-};
-// e = the samples of set a, g = those of set b (one profile: b.profile is read, a.profile must equal it), no quantizer read.
-// Frame: 12 words per frame at out (zeroed in front of the launch; block ignored); Map / Moments: nframes * nby * nbx * 12 / 15 words,
-// every one written by the launch.  Every error is raised before anything is queued.
-int planes_measure_impl(lumahip_ctx *c, const SrcPlanes &a, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &b, DistWhat what,
-                        unsigned block, uint64_t *out, const PlanesLaunch &o);
+// e = the samples of set a, g = those of set b (one profile, which both sets carry), no quantizer read; m.words() words at out, m
+// carries nframes, w, h.  Every error is raised before anything is queued, the block size first.
+int planes_measure_impl(lumahip_ctx *c, const SrcPlanes &a, const SrcPlanes &b, const MeasureOut &m, uint64_t *out, const StreamLaunch &o);
 
 // ---- lumahip_light_level.hip: the content light level of frames or of code planes (include/lumahip_compare.h)
-struct LightLaunch {
-    hipStream_t stream;
-    bool lanes = false;   // as EncodeLaunch::lanes
-};
 // Exactly one of f (frames as they are; no quantizer read, sc ignored) and pl (code planes under the context's quantizer and sc) is
-// non-null.  lh::LIGHT_WORDS words per frame at out (zeroed in front of the launch).  Every error is raised before anything is queued.
-int light_level_impl(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, unsigned nframes, unsigned w, unsigned h, float sc, float scale,
-                     uint64_t *out, const LightLaunch &o);
+// non-null; m (DistWhat::Light) carries nframes, w, h; m.words() words at out.  Every error is raised before anything is queued.
+int light_level_impl(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, float sc, float scale, const MeasureOut &m, uint64_t *out,
+                     const StreamLaunch &o);
+// its test of the caller's scale (the host forms ask it too: nothing of a refused call is uploaded)
+static inline int check_light_scale(lumahip_ctx *c, float scale)
+{
+    return (!(scale > 0.0f) || !std::isfinite(scale)) ? fail(c, LUMAHIP_ERR_ARG, "light level: scale must be finite and > 0 (got %g)", (double)scale)
+                                                      : LUMAHIP_OK;
+}
 
 // ---- lumahip_misc.hip
 int seq_mean(lumahip_ctx *c, const float *chan0_dev, unsigned w, unsigned h, float *mean_host);

@@ -2,7 +2,7 @@
 // MaxFALL are made of, over max(R, G, B) and over the luminance, of frames as they are (lh::k_light_level, luma_kernels.hpp: float or
 // binary16, no quantizer, no tables, no dynamic LDS) or of code planes under the context's quantizer (lh::k_planes_light_level: the
 // floats lumahip_decode_frames_device would write, never written).  The twenty kernels are named here and nowhere else; beside them
-// the two pickers, the plan of a launch (light_plan), the one dispatch (light_level_impl) and the five _device entry points.  The
+// the two pickers, the plan of a launch (light_plan, on lumahip_internal.hpp's MeasureOut and shared checks), the one dispatch (light_level_impl) and the five _device entry points.  The
 // host forms are lumahip_host.hip's.
 #include "lumahip_internal.hpp"
 
@@ -56,26 +56,18 @@ struct LightPlan {
 // The one place that decides what a light-level launch may be and how it runs; exactly one of `f` (frames) and `pl` (code planes
 // under the context's quantizer and sc) is given.  Every error is raised here, before anything of the launch is queued.  The
 // frame-fed forms read no quantizer: a context that never had one set is fine.
-static int light_plan(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, unsigned nframes, unsigned w, unsigned h, float sc, float scale,
-                      uint64_t *out, LightPlan &p)
+static int light_plan(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, float sc, float scale, const MeasureOut &m, uint64_t *out,
+                      LightPlan &p)
 {
+    const unsigned nframes = m.nframes, w = m.w, h = m.h;
     p.planes = pl != nullptr;
-    if (f ? (!f->plane[0] || !f->plane[1] || !f->plane[2]) : (!pl->planes || !pl->stride || !pl->pfs))
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    if (pl)
-        for (int k = 0; k < 3; k++)
-            if (!pl->planes[k])
-                return fail(c, LUMAHIP_ERR_ARG, "null plane %d", k);
+    int rc;
+    if ((rc = f ? check_plane_sets(c, {}, f->plane[0] && f->plane[1] && f->plane[2]) : check_plane_sets(c, {{*pl}}, true)))
+        return rc;
     if (nframes == 0)
         return fail(c, LUMAHIP_ERR_ARG, "light level: nframes must be at least 1");
-    // (check_geom's tests without its demand for a quantizer)
-    if (w == 0 || h == 0 || (w & 1) || (h & 1))
-        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (must be even, non-zero)", w, h);
-    if (!(scale > 0.0f) || !std::isfinite(scale))
-        return fail(c, LUMAHIP_ERR_ARG, "light level: scale must be finite and > 0 (got %g)", (double)scale);
-    if (int rc = check_out_words(c, out))
+    if ((rc = check_size(c, w, h)) || (rc = check_light_scale(c, scale)) || (rc = m.check_out(c, out)))
         return rc;
-    const size_t out_bytes = (size_t)nframes * LIGHT_WORDS * sizeof(uint64_t);
     HIPCHK(c, hipSetDevice(c->device));
     p.f = LightArgs{};
     p.p = PlanesLightArgs{};
@@ -85,15 +77,10 @@ static int light_plan(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, u
     FrameGeom *g;
     if (f) {
         p.in16 = f->elem == Elem::F16;
-        const size_t esz = elem_size(f->elem);
         bool al4;
-        if (int rc = check_frame_alignment(c, *f, esz, &al4))
+        // (the words may not share a byte with anything the launch reads)
+        if ((rc = check_frame_alignment(c, *f, elem_size(f->elem), &al4)) || (rc = check_out_overlap(c, m, out, f, {})))
             return rc;
-        // the words may not share a byte with anything the launch reads
-        const size_t frame_span = ((size_t)(nframes - 1) * f->frame_stride + (size_t)w * h) * esz;
-        for (int k = 0; k < 3; k++)
-            if (ranges_overlap((uintptr_t)out, out_bytes, (uintptr_t)f->plane[k], frame_span))
-                return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps colour plane %d of the frames", k);
         p.vw = al4 ? 4 : 2;
         // no tables: the workgroup is the context's (lumahip_tune "block"), clamped to what the kernels are compiled for
         p.threads = std::min(block_threads_for(c, 0), LIGHT_BOUND);
@@ -105,16 +92,12 @@ static int light_plan(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, u
         g = &p.f.e.g;
     } else {
         const int profile = pl->profile;
-        if (profile < 0 || profile > 3)
-            return fail(c, LUMAHIP_ERR_ARG, "profile must be 0..3 (got %d)", profile);
+        if ((rc = check_profile(c, profile)))
+            return rc;
         if (!c->have_quant)
             return fail(c, LUMAHIP_ERR_STATE, "quantizer not set (call lumahip_set_quantizer first)");
-        const SrcFrames geom{{nullptr, nullptr, nullptr}, Elem::F32, 0, nframes, w, h};   // (the code planes' checks read the geometry only)
-        if (int rc = check_layout(c, geom, false, pl->stride, pl->pfs, profile))
+        if ((rc = check_planes_layout(c, *pl, nframes, w, h)) || (rc = check_out_overlap(c, m, out, nullptr, {{*pl}})))
             return rc;
-        for (int k = 0; k < 3; k++)
-            if (out_overlaps_plane(out, out_bytes, *pl, k, w, h, nframes))
-                return fail(c, LUMAHIP_ERR_ARG, "out_dev overlaps plane %d", k);
         // ---- the supported set: the tables the decode call would stage in LDS; what it leaves in global memory is refused here
         const int cs = c->q.cs;
         if (cs != CS_LUV && cs != CS_YCBCR && cs != CS_RGB && cs != CS_XYZ)
@@ -126,7 +109,7 @@ static int light_plan(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, u
         if (cs == CS_YCBCR && !c->q.ytab)
             return fail(c, LUMAHIP_ERR_UNSUPPORTED, "planes light level: no y table for this YCbCr stream (table values, LDS size or lumahip_tune \"ycbcr_tables\")");
         p.lds = lds_bytes(c, false, cs);
-        if (p.lds + LIGHT_WORDS * sizeof(uint64_t) > LUMAHIP_LDS_PER_WORKGROUP)
+        if (p.lds + m.lds_bytes() > LUMAHIP_LDS_PER_WORKGROUP)
             return fail(c, LUMAHIP_ERR_UNSUPPORTED, "planes light level: the tables take %zu bytes of LDS, a workgroup has %zu", p.lds, LUMAHIP_LDS_PER_WORKGROUP);
         p.cs = cs;
         p.sub = (profile == 0 || profile == 2);
@@ -158,32 +141,28 @@ static int light_plan(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, u
     return LUMAHIP_OK;
 }
 
-int light_level_impl(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, unsigned nframes, unsigned w, unsigned h, float sc, float scale,
-                     uint64_t *out, const LightLaunch &o)
+int light_level_impl(lumahip_ctx *c, const SrcFrames *f, const SrcPlanes *pl, float sc, float scale, const MeasureOut &m, uint64_t *out,
+                     const StreamLaunch &o)
 {
     LightPlan p;
-    if (int rc = light_plan(c, f, pl, nframes, w, h, sc, scale, out, p))
+    if (int rc = light_plan(c, f, pl, sc, scale, m, out, p))
         return rc;
     const hipStream_t s = launch_stream(c, o.stream, o.lanes);
-    if (!p.planes) {
-        const light_kernel_t kern = pick_light(p.vw, p.in16);
-        return launch_measuring(c, kern, p.grid, p.threads, 0, s, p.f, nframes, LIGHT_WORDS);
-    }
+    if (!p.planes)
+        return launch_measure(c, m, out, pick_light(p.vw, p.in16), p.grid, p.threads, 0, s, p.f);
     const planes_light_kernel_t kern = pick_planes_light(p.cs, p.sub, p.vw);
     if (!kern)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no planes light level kernel for colour space %d", p.cs);
-    return launch_measuring(c, kern, p.grid, p.threads, p.lds, s, p.p, nframes, LIGHT_WORDS);
+    return launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, s, p.p);
 }
 
 // what the four frame-fed _device entry points do in front of the dispatch; frames_given: the packed forms' base pointer (the planar
 // forms' three pointers are light_plan's to check)
 static int light_frames_entry(lumahip_ctx *c, bool frames_given, const SrcFrames &f, float scale, uint64_t *out)
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    if (!frames_given)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    return light_level_impl(c, &f, nullptr, f.nframes, f.w, f.h, 1.0f, scale, out, {c->stream, true});
+    return device_entry(c, frames_given, [&](const StreamLaunch &o) {
+        return light_level_impl(c, &f, nullptr, 1.0f, scale, {DistWhat::Light, "light level", 0, f.nframes, f.w, f.h}, out, o);
+    });
 }
 
 }  // namespace lhost
@@ -201,9 +180,9 @@ int lumahip_light_level_frames_device_planar_f16(lumahip_ctx *c, const uint16_t 
 int lumahip_planes_light_level_frames_device(lumahip_ctx *c, const unsigned char *const planes[3], const int stride[3], const size_t pfs[3],
                                              unsigned nframes, unsigned w, unsigned h, int profile, float sc, float scale, uint64_t *out_dev)
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
     const SrcPlanes pl{planes, stride, pfs, profile};
-    return light_level_impl(c, nullptr, &pl, nframes, w, h, sc, scale, out_dev, {c->stream, true});
+    return device_entry(c, true, [&](const StreamLaunch &o) {
+        return light_level_impl(c, nullptr, &pl, sc, scale, {DistWhat::Light, "light level", 0, nframes, w, h}, out_dev, o);
+    });
 }
 }  // extern "C"

@@ -1,7 +1,8 @@
 // lumahip_transcode.hip -- dispatch of the fused transcode kernels (lh::k_transcode, luma_kernels.hpp): code planes under the
 // context's source quantizer -> code planes under its quantizer, no float frame between them.  Its own translation unit: the 48
 // kernels compile side by side with the encode and decode units, and no kernel is in two code objects.  Also the plan of every
-// launch over two plane sets (transcode_plan) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the three
+// launch over two plane sets (transcode_plan: the family's own part; what a measuring launch delivers and the checks every plan
+// shares are lumahip_internal.hpp's) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the three
 // measuring calls over them, whose kernels lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip /
 // lumahip_transcode_moments_map.hip compile.
 #include "lumahip_internal.hpp"
@@ -13,28 +14,20 @@ using namespace lhost;
 namespace lhost {
 
 // The one place that decides what a launch over (source planes, target-side planes) may be and how it runs: argument checks, the
-// supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (TransWhat::Store: tgt =
-// the planes it writes; out = nullptr), for the transcode distortion (Measure: tgt = the given planes it reads, out = its words)
-// and for the transcode distortion map and the transcode moments map (Map / Moments: the same, out = the map of blocks of map_block
-// luma pixels; what differs between the two -- blocks accepted, words per block, LDS to meet in, the kernels' launch bound -- is
-// derived from the mode, as distortion_plan derives it from DistWhat).
+// supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (m == nullptr: tgt = the
+// planes it writes; out = nullptr) and for the transcode distortion, the transcode distortion map and the transcode moments map (tgt =
+// the given planes they read, out = their words; what differs between the three -- blocks accepted, words, LDS to meet in -- is the
+// record's to say, the kernels' launch bound this plan's).
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
-                   TransWhat mode, const uint64_t *out, unsigned map_block, hipStream_t stream, TranscodePlan &p)
+                   const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p)
 {
-    const bool moments = mode == TransWhat::Moments, map = trans_is_map(mode), measure = mode != TransWhat::Store;
-    const DistWhat kind = moments ? DistWhat::Moments : DistWhat::Map;   // (of a map mode: the record of its blocks)
-    const char *const what = moments ? "transcode moments map" : map ? "transcode distortion map" : measure ? "transcode distortion" : "transcode";
-    const char *const out_name = moments ? "mom_dev" : map ? "map_dev" : "out_dev";
-    if (map && !dist_block_ok(kind, map_block))
-        return fail(c, LUMAHIP_ERR_ARG, "%s: block must be %s16, 32 or 64 (got %u)", what, moments ? "8, " : "", map_block);
-    if (!src.planes || !src.stride || !src.pfs || !tgt.planes || !tgt.stride || !tgt.pfs || nframes == 0)
-        return fail(c, LUMAHIP_ERR_ARG, "null argument");
-    for (int k = 0; k < 3; k++)
-        if (!src.planes[k] || !tgt.planes[k])
-            return fail(c, LUMAHIP_ERR_ARG, "null plane %d", k);
+    const bool measure = m != nullptr, map = measure && m->map(), moments = measure && m->kind == DistWhat::Moments;
+    const char *const what = measure ? m->call : "transcode";
+    int rc;
+    if ((measure && (rc = m->check_block(c))) || (rc = check_plane_sets(c, {{src}, {tgt}}, nframes != 0)))
+        return rc;
     const int cse = c->q.cs;
-    int rc = check_geom(c, w, h, tgt.profile, cse);
-    if (rc)
+    if ((rc = check_geom(c, w, h, tgt.profile, cse)))
         return rc;
     if (src.profile < 0 || src.profile > 3)
         return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src.profile);
@@ -42,8 +35,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     if (!sq.have)
         return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
     const int csd = sq.q.cs;
-    const SrcFrames geom{{nullptr, nullptr, nullptr}, Elem::F32, 0, nframes, w, h};   // (the code planes' checks read the geometry only)
-    if ((rc = check_layout(c, geom, false, src.stride, src.pfs, src.profile)) || (rc = check_layout(c, geom, false, tgt.stride, tgt.pfs, tgt.profile)))
+    if ((rc = check_planes_layout(c, src, nframes, w, h)) || (rc = check_planes_layout(c, tgt, nframes, w, h)))
         return rc;
     if (!measure) {
         // no source plane may share a byte with a destination plane over the batch (the extent test of the rotating decode's buffers)
@@ -52,22 +44,9 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                 if (ranges_overlap((uintptr_t)src.planes[i], plane_extent(w, h, src.profile, i, src.stride[i], src.pfs[i], nframes),
                                    (uintptr_t)tgt.planes[j], plane_extent(w, h, tgt.profile, j, tgt.stride[j], tgt.pfs[j], nframes)))
                     return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
-    } else {
-        // both plane sets are read only and may overlap each other; the words may not share a byte with anything the launch reads
-        if (map) {
-            if (!out || !is_aligned(out, 8))
-                return fail(c, LUMAHIP_ERR_ARG, "%s must be non-null and 8-byte aligned", out_name);
-        } else if ((rc = check_out_words(c, out))) {
-            return rc;
-        }
-        const size_t out_bytes =
-            map ? (size_t)nframes * dist_map_words(w, h, map_block, dist_words_per_block(kind)) * sizeof(uint64_t) : out_words_bytes(nframes);
-        for (int k = 0; k < 3; k++) {
-            if (out_overlaps_plane(out, out_bytes, src, k, w, h, nframes))
-                return fail(c, LUMAHIP_ERR_ARG, "%s overlaps source plane %d", out_name, k);
-            if (out_overlaps_plane(out, out_bytes, tgt, k, w, h, nframes))
-                return fail(c, LUMAHIP_ERR_ARG, "%s overlaps given plane %d", out_name, k);
-        }
+    } else if ((rc = m->check_out(c, out)) || (rc = check_out_overlap(c, *m, out, nullptr, {{src, "source "}, {tgt, "given "}}))) {
+        // (both plane sets are read only and may overlap each other; the words may not share a byte with anything the launch reads)
+        return rc;
     }
     // ---- the supported set; everything else is refused here, before anything is launched
     if ((csd != CS_LUV && csd != CS_YCBCR) || (cse != CS_LUV && cse != CS_YCBCR))
@@ -90,7 +69,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     const size_t lds = (any_y ? sizeof(PowfTablesWide) : 0) + lut_lds_bytes(sq.q) + (csd == CS_YCBCR ? lut_lds_bytes(sq.q) + 2 * col : col) +
                        round16((size_t)qe.nbuckets * (qe.mode == LUT_LINKEY_LDS ? 8 : 4));
     // the words the waves of a measuring workgroup meet in: 12, or the blocks of a map tile
-    const size_t acc_lds = moments ? MOMENTS_MAP_LDS_WORDS * sizeof(uint64_t) : map ? DIST_MAP_LDS_WORDS * sizeof(uint64_t) : measure ? 128 : 0;
+    const size_t acc_lds = measure ? m->lds_bytes() : 0;
     if (lds + acc_lds > LUMAHIP_LDS_PER_WORKGROUP)
         return fail(c, LUMAHIP_ERR_UNSUPPORTED, "%s: the tables of both sides take %zu bytes of LDS, a workgroup has %zu", what, lds + acc_lds,
                     LUMAHIP_LDS_PER_WORKGROUP);
@@ -112,9 +91,8 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.threads = std::min(p.threads, moments   ? transmoments_threads_bound(csd, cse, p.vw)
                                     : measure ? TransDistFamily::bound(any_y)
                                               : TransFamily::bound(any_y));
-    // the map: the 2 NW rows of a standard tile divide the block (every workgroup size is a power of two)
     if (map)
-        p.threads = std::min(p.threads, 32 * (int)map_block);
+        p.threads = m->clamp_threads(p.threads);
     p.d = DecArgs{};
     if (!make_geom(p.d.g, w, h, p.vw, p.threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
@@ -129,19 +107,16 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.e.bps = tgt.profile > 1 ? 2 : 1;
     p.e.aligned = planes_aligned(tgt, p.vw) ? 1 : 0;
     p.grid = grid_for(c, p.threads, p.d.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
-    if (map) {
-        // the launch rule over the standard tiles; a workgroup takes whole map tiles
-        p.m = make_map_geom(p.d.g, w, h, map_block, p.threads);
-        p.grid = std::min(p.grid, p.m.totalMapTiles);
-    }
+    if (map)
+        map_shape(*m, p.d.g, p.threads, p.m, p.grid);
     return LUMAHIP_OK;
 }
 
 int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
-                   float *stats, const TranscodeLaunch &o)
+                   float *stats, const StreamLaunch &o)
 {
     TranscodePlan p;
-    int rc = transcode_plan(c, src, src_sc, nframes, w, h, {dst.planes, dst.stride, dst.pfs, dst.profile}, dst_sc, TransWhat::Store, nullptr, 0, o.stream, p);
+    int rc = transcode_plan(c, src, src_sc, nframes, w, h, {dst.planes, dst.stride, dst.pfs, dst.profile}, dst_sc, nullptr, nullptr, o.stream, p);
     if (rc)
         return rc;
     TransArgs a{};
@@ -167,25 +142,24 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     return LUMAHIP_OK;
 }
 
-int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
-                        float dst_sc, TransWhat what, unsigned block, uint64_t *out, const TranscodeLaunch &o)
+int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, const SrcPlanes &given, float dst_sc, const MeasureOut &m, uint64_t *out,
+                        const StreamLaunch &o)
 {
     TranscodePlan p;
-    if (int rc = transcode_plan(c, src, src_sc, nframes, w, h, given, dst_sc, what, out, block, o.stream, p))
+    if (int rc = transcode_plan(c, src, src_sc, m.nframes, m.w, m.h, given, dst_sc, &m, out, o.stream, p))
         return rc;
+    const auto no_kernel = [&] { return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no %s kernel for colour spaces %d -> %d", m.call, p.csd, p.cse); };
     DecArgs g{};
     g.g = p.d.g;
     read_planes(g, given, p.vw);
-    if (!trans_is_map(what)) {
+    if (!m.map()) {
         TransDistArgs a{};
         a.d = p.d;
         a.e = p.e;
         a.g = g;
         a.out = out;
         const transdist_kernel_t kern = pick_transdist(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
-        if (!kern)
-            return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode distortion kernel for colour spaces %d -> %d", p.csd, p.cse);
-        return launch_measuring(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a, nframes);
+        return kern ? launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a) : no_kernel();
     }
     TransDistMapArgs a{};
     a.d = p.d;
@@ -193,23 +167,9 @@ int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsi
     a.g = g;
     a.map = out;
     a.m = p.m;
-    const bool moments = what == TransWhat::Moments;
-    const transdist_map_kernel_t kern = (moments ? pick_transdist_moments_map : pick_transdist_map)(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
-    if (!kern)
-        return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no transcode %s map kernel for colour spaces %d -> %d", moments ? "moments" : "distortion", p.csd, p.cse);
-    if (int rc = launch_fused(c, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a))
-        return rc;
-    HIPCHK(c, hipGetLastError());
-    return LUMAHIP_OK;
-}
-
-// what the plane-fed measuring _device entry points do in front of the dispatch
-static int measure_planes_entry(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &given,
-                                float dst_sc, TransWhat what, unsigned block, uint64_t *out)
-{
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    return measure_planes_impl(c, src, src_sc, nframes, w, h, given, dst_sc, what, block, out, {c->stream, true});
+    const transdist_map_kernel_t kern =
+        (m.kind == DistWhat::Moments ? pick_transdist_moments_map : pick_transdist_map)(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
+    return kern ? launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a) : no_kernel();
 }
 
 // channel 0 of the decoded and colour-transformed frame (one frame, planes without a frame stride) into out_dev, w*h floats
@@ -248,10 +208,10 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
                                                unsigned char *const dst_planes[3], const int dst_stride[3], const size_t dst_pfs[3],
                                                int dst_profile, float dst_sc, float *stats)
 {
-    if (!c)
-        return LUMAHIP_ERR_ARG;
-    return transcode_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, nframes, w, h, {dst_planes, dst_stride, dst_pfs, dst_profile}, dst_sc,
-                          stats, {c->stream, true});
+    return device_entry(c, true, [&](const StreamLaunch &o) {
+        return transcode_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, nframes, w, h, {dst_planes, dst_stride, dst_pfs, dst_profile},
+                              dst_sc, stats, o);
+    });
 }
 
 // The three plane-fed measuring entry points (include/lumahip.h and, for the moments map, include/lumahip_measure.h have their full
@@ -260,11 +220,16 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
     const unsigned char *const src_planes[3], const int src_stride[3], const size_t src_pfs[3], int src_profile, float src_sc, unsigned nframes, \
         unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], const size_t given_pfs[3], int dst_profile, \
         float dst_sc
+#define CALL_Frame "transcode distortion"
+#define CALL_Map "transcode distortion map"
+#define CALL_Moments "transcode moments map"
 #define MEASURE(what, block, out)                                                                                                                \
-    measure_planes_entry(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, nframes, w, h, {given_planes, given_stride, given_pfs, dst_profile}, \
-                         dst_sc, TransWhat::what, block, out)
+    device_entry(c, true, [&](const StreamLaunch &o) {                                                                                           \
+        return measure_planes_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, {given_planes, given_stride, given_pfs, dst_profile}, dst_sc, \
+                                   {DistWhat::what, CALL_##what, block, nframes, w, h}, out, o);                                                 \
+    })
 extern "C" {
-int lumahip_transcode_distortion_frames_device(lumahip_ctx *c, MEASURE_PARAMS, uint64_t *out_dev) { return MEASURE(Measure, 0, out_dev); }
+int lumahip_transcode_distortion_frames_device(lumahip_ctx *c, MEASURE_PARAMS, uint64_t *out_dev) { return MEASURE(Frame, 0, out_dev); }
 int lumahip_transcode_distortion_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return MEASURE(Map, block, map_dev); }
 int lumahip_transcode_moments_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return MEASURE(Moments, block, mom_dev); }
 }  // extern "C"
