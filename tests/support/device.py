@@ -148,6 +148,11 @@ def from_frames(L, frames, w, h, profile, strides=None, *, padding):
     return Planes(L, w, h, profile, len(frames), fill=fill, strides=strides)
 
 
+def on_device(L, hp):
+    """the Planes of a host plane set (tests/support/measuring.py HostPlanes): the same bytes in the same layout"""
+    return Planes(L, hp.w, hp.h, hp.profile, hp.nf, fill=hp.bufs, strides=hp.st, gap=hp.gap, base=hp.base)
+
+
 def random_planes(L, rng, w, h, profile, nf, strides=None):
     """random bytes in the samples (out-of-range codes included), the sentinel in every row padding and gap"""
     frames = random_frames(rng, w, h, profile, nf, _strides(L, w, h, profile, strides))
@@ -170,13 +175,21 @@ def map_buf(nwords):
 
 
 # ---- the device calls
-def encode(c, L, fr, sc, profile, strides=None):
-    """the planes lumahip_encode_frames_device writes for these frames, as host buffers + their Planes"""
+def stats_buf(nf):
+    """the 3 nf floats a call writes its per-frame {sum, min, max} into, NaN before the call"""
+    import torch
+    return torch.full((3 * nf,), float("nan"), dtype=torch.float32, device=dev())
+
+
+def encode(c, L, fr, sc, profile, strides=None, stats=False):
+    """the planes lumahip_encode_frames_device writes for these frames, as host buffers + their Planes; stats: + the (nf, 3)
+    {sum, min, max} it reports"""
     import torch
     pl = Planes(L, fr.w, fr.h, profile, fr.nf, strides=strides)
-    c.encode_frames_device(fr.ptr, fr.fs, fr.nf, fr.w, fr.h, sc, profile, pl.ptrs, pl.st, pl.pfs)
+    sd = stats_buf(fr.nf) if stats else None
+    c.encode_frames_device(fr.ptr, fr.fs, fr.nf, fr.w, fr.h, sc, profile, pl.ptrs, pl.st, pl.pfs, sd.data_ptr() if stats else None)
     torch.cuda.synchronize()
-    return pl, pl.host()
+    return (pl, pl.host(), sd.cpu().numpy().reshape(fr.nf, 3)) if stats else (pl, pl.host())
 
 
 def _frame_fed(c, call, fr, form, args):
@@ -223,13 +236,15 @@ def two_calls(cd, ce, src, src_sc, dst, dst_sc, stats=None):
     return buf
 
 
-def transcoded(c, L, src, src_sc, dp, dst_sc, strides=None):
-    """what lumahip_transcode_frames_device writes for src: its Planes and their host buffers"""
+def transcoded(c, L, src, src_sc, dp, dst_sc, strides=None, gap=GAP, base=0, stats=False):
+    """what lumahip_transcode_frames_device writes for src into sentinel-filled planes (rows `strides` apart, `gap` bytes behind a
+    frame, `base` bytes into their buffers): its Planes and their host buffers; stats: + the (nf, 3) {sum, min, max} it reports"""
     import torch
-    dst = Planes(L, src.w, src.h, dp, src.nf, strides=strides)
-    fused(c, src, src_sc, dst, dst_sc)
+    dst = Planes(L, src.w, src.h, dp, src.nf, strides=strides, gap=gap, base=base)
+    sd = stats_buf(src.nf) if stats else None
+    fused(c, src, src_sc, dst, dst_sc, sd)
     torch.cuda.synchronize()
-    return dst, dst.host()
+    return (dst, dst.host(), sd.cpu().numpy().reshape(src.nf, 3)) if stats else (dst, dst.host())
 
 
 def measure(c, src, src_sc, given, dst_sc, out=None):

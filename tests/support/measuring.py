@@ -36,7 +36,7 @@ def contexts_of(cs, in16):
     return [(6, pq10, ()), (3, pq11, NO_HALF_TABLE), (7, lin12, ())] if in16 else [(5, pq10, ()), (3, pq11, NO_COMPOSITE), (7, lin12, ())]
 
 
-def _block(family, n):
+def block_of(family, n):
     """the block of row n of a (family, colour space): sizes go round with n % 3, so the blocks of one size go round too"""
     if family == "distortion":
         return None
@@ -62,13 +62,13 @@ def measuring_matrix():
                         for profile in PROFILES:
                             for (w, h) in SIZES:
                                 ident = "%s-%s-lm%d-%s-sc%g-p%d-%dx%d" % (family, name, lm, ft, sc, profile, w, h)
-                                out.append(Row(ident, family, cs, lm, cfg, tunes, in16, profile, w, h, sc, _block(family, n), forms[m % 2]))
+                                out.append(Row(ident, family, cs, lm, cfg, tunes, in16, profile, w, h, sc, block_of(family, n), forms[m % 2]))
                                 n += 1
                                 m += 1
                 tunes = () if cs != fk.YCC else NO_HALF_TABLE if in16 else NO_COMPOSITE
                 for profile, (w, h) in zip((1, 0) if in16 else (0, 1), SIZES[:2]):
                     ident = "%s-%s-pq8-%s-p%d-%dx%d" % (family, name, ft, profile, w, h)
-                    out.append(Row(ident, family, cs, 3, fk.pq8(cs), tunes, in16, profile, w, h, scs[-1], _block(family, n), forms[profile]))
+                    out.append(Row(ident, family, cs, 3, fk.pq8(cs), tunes, in16, profile, w, h, scs[-1], block_of(family, n), forms[profile]))
                     n += 1
     return out
 
@@ -127,21 +127,34 @@ def given_for(o, family, cfg, profile, w, h, sc, in16, block):
     if key not in _given:
         frames, e, _ = fk.expected(o, cfg, profile, w, h, sc, in16)
         rng = np.random.default_rng([FAMILIES.index(family), cfg[0], cfg[1], cfg[2], profile, w, h, int(sc), int(in16), block or 0])
-        nf = len(e)
-        if family == "distortion":
-            g = [perturb(rng, e[f], w, h, profile, frac=0.5 if w * h < 100 else 0.10) for f in range(nf)]
-        elif -(-w // block) > 1 and -(-h // block) > 1:
-            g = map_perturbed(rng, _Frames(e), e, w, h, profile, block)
-        else:       # (one block column or row: keeping it would leave frame 1 without a difference)
-            g = [perturb(rng, e[f], w, h, profile, frac=0.5) for f in range(nf)]
-        dist = np.stack([expected_distortion(e[f], g[f], w, h, profile) for f in range(nf)])
-        dmap = None if family == "distortion" else np.stack([expected_distortion_map(e[f], g[f], w, h, profile, block) for f in range(nf)])
-        words = dist if family == "distortion" else dmap if family == "distortion_map" else \
-            np.stack([expected_moments_map(e[f], g[f], w, h, profile, block) for f in range(nf)])
-        for a in [dist, words] + ([dmap] if dmap is not None else []) + [p for fr in g for p in fr]:
-            a.setflags(write=False)
-        _given[key] = Given(frames, e, g, words, dist, dmap)
+        _given[key] = Given(frames, e, *given_from(rng, family, e, w, h, profile, block))
     return _given[key]
+
+
+def words_of(family, e, g, w, h, profile, block):
+    """numpy's words of the family for two lists of frames of three (rows, stride) planes: (nf, 3, 4), (nf, nby, nbx, 3, 4) or
+    (nf, nby, nbx, 3, 5)"""
+    one = {"distortion": lambda a, b: expected_distortion(a, b, w, h, profile),
+           "distortion_map": lambda a, b: expected_distortion_map(a, b, w, h, profile, block),
+           "moments_map": lambda a, b: expected_moments_map(a, b, w, h, profile, block)}[family]
+    return np.stack([one(e[f], g[f]) for f in range(len(e))])
+
+
+def given_from(rng, family, e, w, h, profile, block):
+    """(g, words, dist, dmap) of given_for for the expected planes e of a launch, whichever front end they are expected of; read-only"""
+    nf = len(e)
+    if family == "distortion":
+        g = [perturb(rng, e[f], w, h, profile, frac=0.5 if w * h < 100 else 0.10) for f in range(nf)]
+    elif -(-w // block) > 1 and -(-h // block) > 1:
+        g = map_perturbed(rng, _Frames(e), e, w, h, profile, block)
+    else:       # (one block column or row: keeping it would leave frame 1 without a difference)
+        g = [perturb(rng, e[f], w, h, profile, frac=0.5) for f in range(nf)]
+    dist = words_of("distortion", e, g, w, h, profile, None)
+    dmap = None if family == "distortion" else words_of("distortion_map", e, g, w, h, profile, block)
+    words = dist if family == "distortion" else dmap if family == "distortion_map" else words_of("moments_map", e, g, w, h, profile, block)
+    for a in [dist, words] + ([dmap] if dmap is not None else []) + [p for fr in g for p in fr]:
+        a.setflags(write=False)
+    return g, words, dist, dmap
 
 
 def given_of(o, row):

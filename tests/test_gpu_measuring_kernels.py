@@ -46,7 +46,7 @@ pytestmark = pytest.mark.gpu
 
 from tests.support import frame_kernels as fk  # noqa: E402
 from tests.support import measuring as ms  # noqa: E402
-from tests.support.device import Frames, L, Planes, ctx, dist, dist_map, map_buf, out_buf  # noqa: E402,F401  (L is the module fixture)
+from tests.support.device import Frames, L, ctx, dist, dist_map, map_buf, on_device, out_buf  # noqa: E402,F401  (L is the module fixture)
 from tests.support.host import ERR_ARG, GAP, OUT_FILL, fold_map, nwords, widen_halves  # noqa: E402
 from tests.support.moments import fold_2x2, mom_map, mom_nwords, sse_of  # noqa: E402
 
@@ -71,10 +71,6 @@ def call(family, c, fr, sc, given, block, form):
     if family == "distortion":
         return dist(c, fr, sc, given, form)
     return (dist_map if family == "distortion_map" else mom_map)(c, fr, sc, given, block, form)
-
-
-def on_device(L, hp):
-    return Planes(L, hp.w, hp.h, hp.profile, hp.nf, fill=hp.bufs, strides=hp.st, gap=hp.gap, base=hp.base)
 
 
 def device_frames(frames, in16, pad=4, base=0):
