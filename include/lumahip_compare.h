@@ -117,6 +117,40 @@ int lumahip_light_level_frame_host(lumahip_ctx *ctx, const float *rgb, unsigned 
 int lumahip_planes_light_level_frame_host(lumahip_ctx *ctx, const unsigned char *const planes[3], const int stride[3], unsigned w, unsigned h,
                                           int profile, float sc, float scale, uint64_t out[8]);
 
+/* Half-resolution transcode: the next rung of a delivery ladder straight from the archive's code planes -- source planes of w x h
+ * under the context's source quantizer (lumahip_set_source_quantizer) to destination planes of (w/2) x (h/2) under its quantizer,
+ * averaged 2x2 in linear light, in one launch and without a float frame (lumahip_transcode_frames_device is the full-size call).
+ *
+ * What is computed (normative).  w and h are the SOURCE size; the destination planes have (w/2) x (h/2) luma samples in
+ * dst_profile's layout.  Per frame:
+ *   d[c][y][x]   exactly the float lumahip_decode_frames_device would store for the source planes under the source quantizer,
+ *                src_profile and src_sc (the division by src_sc carried out);
+ *   m[c][Y][X] = ((d[c][2Y][2X] + d[c][2Y][2X+1]) + (d[c][2Y+1][2X] + d[c][2Y+1][2X+1])) * 0.25f
+ *                in fp32, nothing contracted, in this association and no other (another order changes codes); a NaN's sign and
+ *                payload reach no output;
+ *   the destination planes are exactly what lumahip_encode_frames_device would write for m under the context's quantizer,
+ *   dst_profile and dst_sc; stats_dev (nullable) is that call's {sum, min, max} of m's transformed channel 0 per frame -- for a
+ *   YCbCr target the luminance, as the transcode call gives it.
+ *
+ * The device form is asynchronous on the context's stream, never waits on the host, takes part in unordered sections and honours
+ * lumahip_tune "grid_enc", "lane_grid_enc", "block" and "blocks_per_cu", like the transcode call.  The host form uploads one
+ * frame's source planes, runs one launch, downloads the destination planes and returns synchronously.  It has no mean_lum: the
+ * reference has no half-resolution operation whose sequential sum such a mean could reproduce.
+ *
+ * Errors come before anything is launched, and the destination is then untouched: LUMAHIP_ERR_ARG for w or h not a multiple of 4
+ * (the target must be even both ways), for strides or frame strides that do not hold their planes (the source at w x h, the
+ * destination at (w/2) x (h/2)), for a source plane that shares a byte with a destination plane over the batch, for null
+ * arguments and a bad profile; LUMAHIP_ERR_STATE unless both quantizers are set; LUMAHIP_ERR_UNSUPPORTED outside the transcode
+ * call's supported set, unchanged: Lu'v' and YCbCr on either side in all 16 profile pairs, source tables of at most 12 bits,
+ * a target with search mode 3 / 7 or the composite records, both sides' tables within 160 KiB of on-chip memory. */
+int lumahip_transcode_half_frames_device(lumahip_ctx *ctx, const unsigned char *const src_planes_dev[3], const int src_stride[3],
+                                         const size_t src_plane_frame_stride[3], int src_profile, float src_sc, unsigned nframes,
+                                         unsigned w, unsigned h, unsigned char *const dst_planes_dev[3], const int dst_stride[3],
+                                         const size_t dst_plane_frame_stride[3], int dst_profile, float dst_sc, float *stats_dev);
+int lumahip_transcode_half_frame_host(lumahip_ctx *ctx, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile,
+                                      float src_sc, unsigned w, unsigned h, unsigned char *const dst_planes[3], const int dst_stride[3],
+                                      int dst_profile, float dst_sc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,8 @@ _ABI_COMPARE = {
     "lumahip_planes_light_level_frames_device": (_i, _PLANES + (_f, _vp)),
     "lumahip_light_level_frame_host": (_i, (_vp, _vp, _u, _u, _f, _vp)),
     "lumahip_planes_light_level_frame_host": (_i, _PLANES_HOST + (_f, _vp)),
+    "lumahip_transcode_half_frames_device": (_i, _TWO_SETS + (_vp,)),
+    "lumahip_transcode_half_frame_host": (_i, _TWO_SETS_HOST),
 }
 COMPARE_SYMBOLS = tuple(_ABI_COMPARE)
 
@@ -240,7 +242,8 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_encode_f16.hip", "lumahip_decode_f16.hip", "lumahip_pick.hpp", "lumahip_transcode.hip", "lumahip_distortion.hip", "lumahip_distortion_f16.hip",
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
                   "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip",
-                  "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip", "lumahip_light_level.hip")
+                  "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip", "lumahip_light_level.hip",
+                  "lumahip_transcode_half.hip")
 
 
 def kernel_source_sha() -> str:
@@ -706,6 +709,19 @@ class Context:
                                                       _arr3(C.c_int, st), dst_profile, dst_sc, C.byref(mean) if want_mean else None))
         return out, st, (float(mean.value) if want_mean else None)
 
+    def transcode_half_frame(self, planes, strides, w, h, src_sc=1.0, src_profile=2, dst_sc=1.0, dst_profile=2, align=32, dst_strides=None):
+        """code planes of w x h under the source quantizer -> (planes, strides) of (w/2) x (h/2) under the quantizer, averaged 2x2
+        in linear light, one fused launch; w and h multiples of 4"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        _, hs, st, _ = plane_geometry(w // 2, h // 2, dst_profile, align)
+        if dst_strides is not None:
+            st = tuple(dst_strides)
+        out = [np.zeros((hs[p], st[p]), dtype=np.uint8) for p in range(3)]
+        self._chk(self.L.lumahip_transcode_half_frame_host(self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
+                                                           src_profile, src_sc, w, h, _arr3(C.c_void_p, [p.ctypes.data for p in out]),
+                                                           _arr3(C.c_int, st), dst_profile, dst_sc))
+        return out, st
+
     def distortion_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2) -> np.ndarray:
         """rgb: (3,h,w) float32; planes: the given code planes as three (rows, stride) uint8 arrays.  Returns a (3, 4) uint64 array:
         per plane {sse, sad, max_abs, n_differ} of the planes encode_frame would write against the given ones"""
@@ -878,6 +894,12 @@ class Context:
                                 dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr=None):
         self._two_sets(self.L.lumahip_transcode_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc,
                        nframes, w, h, dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr)
+
+    # w, h: the SOURCE size; the destination planes hold (w/2) x (h/2) luma samples (the 2x2 box in linear light)
+    def transcode_half_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
+                                     dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr=None):
+        self._two_sets(self.L.lumahip_transcode_half_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile,
+                       src_sc, nframes, w, h, dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr)
 
     # distortion of given planes against the frames' own encode: out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ}
     # as uint64 (zeroed by the call); the arguments are those of the matching encode call

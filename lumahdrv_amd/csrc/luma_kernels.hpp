@@ -771,6 +771,8 @@ struct DecUnit {
     bool valid;
 };
 
+// (dec_load_at below states the same loads for given coordinates: a change to the loads here is a change there too.  The two stay
+//  apart so that the kernels that call dec_load keep their listings; having dec_load call dec_load_at is due once that can be re-checked.)
 template <bool SUB, int VW>
 LH_DEV void dec_load(DecUnit<SUB, VW> &u, const DecArgs &a, int t, int tx, int ty, int NW)
 {
@@ -785,6 +787,47 @@ LH_DEV void dec_load(DecUnit<SUB, VW> &u, const DecArgs &a, int t, int tx, int t
         return;
     u.valid = true;
     const int f = u.f, ux = u.ux, uy = u.uy;
+    {
+        const unsigned char *s = a.src[0] + (size_t)f * a.src_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] +
+                                 (size_t)ux * VW * a.bps;
+        load_samples<VW>(s, u.y[0], a.bps, a.aligned);
+        load_samples<VW>(s + a.stride[0], u.y[1], a.bps, a.aligned);
+    }
+    if constexpr (SUB) {
+        constexpr int NQ = VW / 2;
+        load_samples<NQ>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)uy * a.stride[1] + (size_t)ux * NQ * a.bps,
+                         u.c1, a.bps, a.aligned);
+        load_samples<NQ>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)uy * a.stride[2] + (size_t)ux * NQ * a.bps,
+                         u.c2, a.bps, a.aligned);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            int row[VW];
+            load_samples<VW>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)(2 * uy + r) * a.stride[1] +
+                                 (size_t)ux * VW * a.bps, row, a.bps, a.aligned);
+#pragma unroll
+            for (int i = 0; i < VW; i++)
+                u.c1[r * VW + i] = row[i];
+            load_samples<VW>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)(2 * uy + r) * a.stride[2] +
+                                 (size_t)ux * VW * a.bps, row, a.bps, a.aligned);
+#pragma unroll
+            for (int i = 0; i < VW; i++)
+                u.c2[r * VW + i] = row[i];
+        }
+    }
+}
+
+// dec_load's loads for the unit at given coordinates: no tile arithmetic and no range test, both the caller's (k_transcode_half,
+// whose loop runs over the target's tiles and whose source units are in range whenever the target unit is).  Keep in step with
+// dec_load.  The unit records its coordinates as dec_load's does, so that a DecUnit is one thing wherever it was loaded; k_transcode_half
+// itself reads only the samples.
+template <bool SUB, int VW>
+LH_DEV void dec_load_at(DecUnit<SUB, VW> &u, const DecArgs &a, int f, int ux, int uy)
+{
+    u.valid = true;
+    u.f = f;
+    u.ux = ux;
+    u.uy = uy;
     {
         const unsigned char *s = a.src[0] + (size_t)f * a.src_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] +
                                  (size_t)ux * VW * a.bps;
@@ -1467,6 +1510,167 @@ __global__ __launch_bounds__(1024) void k_transcode(const TransArgs a)
         }
         dec_load<SUBD, VW>(nxt, a.d, t + G, tx, ty, NW);
         cur = nxt;
+    }
+    if (a.e.stats)
+        stats_flush(st, a.e.stats, tx);
+}
+
+// ---- HALF-RESOLUTION TRANSCODE ----------------------------------------------------------------------
+// k_transcode with a 2x2 box in linear light between DEC and ENC: the target planes hold (w/2) x (h/2) luma samples, target pixel
+// (X, Y) is m = ((d[2Y][2X] + d[2Y][2X+1]) + (d[2Y+1][2X] + d[2Y+1][2X+1])) * 0.25f of the floats d the decode stores (`/ sc`
+// carried out) -- fp32, this association, nothing contracted -- and the planes are what the encode writes for m.  a.d.g is the
+// source's geometry (w x h), a.e.g the target's (w/2 x h/2); the loop runs over the target's tiles.  A thread owns the target unit
+// (ux, uy), VW pixels x 2 rows, and fills it from the four source units (2ux + i, 2uy + j): source unit (i, j) is VW pixels x 2 rows
+// of the source and gives the VW/2 pixels from i * VW/2 on of target row j.  Per lane and row the source reads are two adjacent
+// VW-sample pieces, so a wave reads contiguous memory.  w and h are multiples of 4 and VW == 4 only when w/2 is one too
+// (transcode_plan), so the source has exactly twice the target's units both ways: the four are in range whenever the target unit is.
+
+// the target unit of tile t for this thread; false: none (the tile overhangs the frame, or t is past the last tile)
+LH_DEV bool half_locate(const FrameGeom &g, int t, int tx, int ty, int NW, int &f, int &ux, int &uy)
+{
+    if (t >= g.totalTiles)
+        return false;
+    int bx, by;
+    tile_coords(t, g, f, bx, by);
+    ux = bx * 64 + tx;
+    uy = by * NW + ty;
+    return ux < g.unitsX && uy < g.unitsY;
+}
+
+// How many of a target unit's four source units are loaded one iteration ahead, behind the previous unit's stores (the others are
+// loaded where they are decoded).  From the register report (profiles/transcode_half_codegen.txt): a 4:2:0 source unit is VW * 3
+// registers, a 4:4:4 one VW * 6.
+template <bool SUBD, int VW>
+constexpr int half_prefetch()
+{
+    return VW == 2 ? 4 : 2;
+}
+
+// Budget, one function of (CSD, CSE, VW) which the kernel's __launch_bounds__ / amdgpu_waves_per_eu are written with and
+// transcode_plan clamps the launch to (profiles/transcode_half_codegen.txt): with YCbCr on either side 512 threads, which leave the
+// fp64 powf chains 256 registers, as TransDistBound does for the measuring kernels; Lu'v' -> Lu'v' at VW 4 512 threads and three waves
+// per SIMD (168 registers: at 128 the target unit beside a decoded unit and the prefetched ones spill); at VW 2 k_transcode's 1024
+constexpr int transhalf_threads_bound(int csd, int cse, int vw)
+{
+    return (csd == CS_YCBCR || cse == CS_YCBCR || vw == 4) ? 512 : 1024;
+}
+constexpr int transhalf_waves(int csd, int cse, int vw)
+{
+    return (csd == CS_YCBCR || cse == CS_YCBCR) ? 2 : vw == 4 ? 3 : 4;
+}
+
+// the loads of the first NPF source units of target unit (f, ux, uy): source unit s is (2ux + (s & 1), 2uy + (s >> 1))
+template <bool SUBD, int VW, int NPF>
+LH_DEV void half_issue(DecUnit<SUBD, VW> (&pf)[NPF], const DecArgs &a, int f, int ux, int uy)
+{
+    dec_load_at<SUBD, VW>(pf[0], a, f, 2 * ux, 2 * uy);
+    if constexpr (NPF > 1)
+        dec_load_at<SUBD, VW>(pf[1], a, f, 2 * ux + 1, 2 * uy);
+    if constexpr (NPF > 2)
+        dec_load_at<SUBD, VW>(pf[2], a, f, 2 * ux, 2 * uy + 1);
+    if constexpr (NPF > 3)
+        dec_load_at<SUBD, VW>(pf[3], a, f, 2 * ux + 1, 2 * uy + 1);
+}
+
+// source unit S of target unit (f, ux, uy) -- prefetched (S < NPF) or loaded here -- decoded and folded into its VW/2 pixels of u.in
+template <int S, int CSD, bool SUBD, int VW, bool UVTAB, bool YT, bool SCFAST, int NPF, typename K>
+LH_DEV void half_fold(EncUnit<VW> &u, const DecUnit<SUBD, VW> (&pf)[NPF], const DecArgs &a, const K &kd, const float *s_lut, const float *s_uv, int f,
+                      int ux, int uy)
+{
+    constexpr int i = S & 1, j = S >> 1;
+    DecUnit<SUBD, VW> du;
+    if constexpr (S < NPF)
+        du = pf[S];
+    else
+        dec_load_at<SUBD, VW>(du, a, f, 2 * ux + i, 2 * uy + j);
+    float v[3][2][VW];
+    dec_values<CSD, SUBD, VW, UVTAB, YT, SCFAST>(du, a, kd, s_lut, s_uv, v);
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int p = 0; p < VW / 2; p++)
+            u.in[c][j][i * (VW / 2) + p] = ((v[c][0][2 * p] + v[c][0][2 * p + 1]) + (v[c][1][2 * p] + v[c][1][2 * p + 1])) * 0.25f;
+}
+
+// the four source units of a target unit, one at a time: at most one decoded unit is live beside the target unit
+template <int CSD, bool SUBD, int VW, bool UVTAB, bool YT, bool SCFAST, int NPF, typename K>
+LH_DEV void half_fill(EncUnit<VW> &u, const DecUnit<SUBD, VW> (&pf)[NPF], const DecArgs &a, const K &kd, const float *s_lut, const float *s_uv, int f,
+                      int ux, int uy)
+{
+    half_fold<0, CSD, SUBD, VW, UVTAB, YT, SCFAST>(u, pf, a, kd, s_lut, s_uv, f, ux, uy);
+    half_fold<1, CSD, SUBD, VW, UVTAB, YT, SCFAST>(u, pf, a, kd, s_lut, s_uv, f, ux, uy);
+    half_fold<2, CSD, SUBD, VW, UVTAB, YT, SCFAST>(u, pf, a, kd, s_lut, s_uv, f, ux, uy);
+    half_fold<3, CSD, SUBD, VW, UVTAB, YT, SCFAST>(u, pf, a, kd, s_lut, s_uv, f, ux, uy);
+}
+
+// k_transcode_half: k_transcode's tables, statistics and loop order -- the loads of the next target unit's source units are issued
+// after the current unit's stores
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__(transhalf_threads_bound(CSD, CSE, VW)) __attribute__((amdgpu_waves_per_eu(transhalf_waves(CSD, CSE, VW))))
+void k_transcode_half(const TransArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+    constexpr int NPF = half_prefetch<SUBD, VW>();
+
+    EncStats st;
+
+    DecUnit<SUBD, VW> pf[NPF];
+    int f = 0, ux = 0, uy = 0;
+    bool valid = half_locate(a.e.g, blockIdx.x, tx, ty, NW, f, ux, uy);
+    if (valid)
+        half_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+    for (int t = blockIdx.x; t < a.e.g.totalTiles; t += G) {
+        if (a.e.stats) {
+            const int tf = t / a.e.g.tilesPerFrame;  // wave-uniform
+            if (tf != st.frame) {
+                stats_flush(st, a.e.stats, tx);
+                st.frame = tf;
+            }
+        }
+        if (valid) {
+            EncUnit<VW> u;
+            if constexpr (Front::YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    half_fill<CSD, SUBD, VW, false, true, true>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+                else
+                    half_fill<CSD, SUBD, VW, false, true, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            } else {
+                half_fill<CSD, SUBD, VW, true, false, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, Front::YE, false, !Front::YE>(u, a.e, ke, c0, c1, c2, st);
+            if constexpr (Front::YE) {
+                // the luminance statistics of a YCbCr target, only for a launch that asks for them (k_transcode says why)
+                if (a.e.stats) {
+#pragma unroll
+                    for (int j = 0; j < 2 * VW; j++) {
+                        const float lum = pq_decode(div_ieee(c0[j], 255.0f), ke);
+                        st.sum += lum;
+                        st.mn = fminf(st.mn, lum);
+                        st.mx = fmaxf(st.mx, lum);
+                    }
+                }
+            }
+            // (the tile, and with it the frame, is wave-uniform: saying so keeps the planes' frame offsets scalar)
+            enc_emit<CSE, SUBE, VW, LM>(__builtin_amdgcn_readfirstlane(f), ux, uy, c0, c1, c2, a.e, static_cast<const float *>(nullptr), s_rec);   // (record searches: no table pointer)
+        }
+        valid = half_locate(a.e.g, t + G, tx, ty, NW, f, ux, uy);
+        if (valid)
+            half_issue<SUBD, VW>(pf, a.d, f, ux, uy);
     }
     if (a.e.stats)
         stats_flush(st, a.e.stats, tx);

@@ -1012,14 +1012,17 @@ struct StagedPlanes {
 // What those calls open with, after their null checks: the geometry against the target-side set `tgt`, the source set's profile and
 // quantizer (src = nullptr: frames in, one set; tgt = nullptr too: a frame alone, quantizers = false), the layouts, d_planes large
 // enough for [src][tgt].  quantizers = false: the sets are taken as they are (the plane-to-plane measures, the light level of a
-// frame), neither quantizer is asked for
-static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes *tgt, bool quantizers = true)
+// frame), neither quantizer is asked for.  tgt_scale 2 (the half-resolution transcode): w and h are multiples of 4 and the set `tgt`
+// is laid out at (w/2) x (h/2)
+static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes *tgt, bool quantizers = true, unsigned tgt_scale = 1)
 {
     int rc = quantizers ? check_geom(c, w, h, tgt->profile, c->q.cs) : check_size(c, w, h);
     if (!rc && !quantizers && tgt)
         rc = check_profile(c, tgt->profile);
     if (rc)
         return rc;
+    if (tgt_scale == 2 && ((w | h) & 3))
+        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (half resolution: must be multiples of 4)", w, h);
     if (src && (src->profile < 0 || src->profile > 3))
         return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src->profile);
     if (quantizers && src && !c->src.have)
@@ -1031,7 +1034,8 @@ static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *
     for (StagedPlanes *s : sets) {
         if (!s)
             continue;
-        plane_layout(s->L, w, h, s->profile, s->stride);
+        const unsigned sc = s == tgt ? tgt_scale : 1;
+        plane_layout(s->L, w / sc, h / sc, s->profile, s->stride);
         const int p = bad_plane(s->L, s->planes, s->stride);
         if (p >= 0)
             return fail(c, LUMAHIP_ERR_ARG, "%splane %d: null or stride %d < row bytes %d", s->name, p, s->stride[p], s->L.row_bytes[p]);
@@ -1108,6 +1112,28 @@ extern "C" int lumahip_transcode_frame_host(lumahip_ctx *c, const unsigned char 
             return rc;
         return seq_mean(c, c->d_frame, w, h, mean_lum);
     }
+    return LUMAHIP_OK;
+}
+
+// The same at half resolution (lumahip_transcode_half_frames_device): the destination set is staged and downloaded at (w/2) x (h/2).
+// No mean_lum: the reference has no half-resolution operation whose sequential sum it could reproduce.
+extern "C" int lumahip_transcode_half_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile,
+                                                 float src_sc, unsigned w, unsigned h, unsigned char *const dst_planes[3], const int dst_stride[3],
+                                                 int dst_profile, float dst_sc)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!src_planes || !src_stride || !dst_planes || !dst_stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    StagedPlanes src{"source ", src_planes, src_stride, src_profile}, dst{"destination ", dst_planes, dst_stride, dst_profile};
+    int rc = planes_staging(c, w, h, &src, &dst, true, 2);
+    if (rc)
+        return rc;
+    if ((rc = planes_up(c, src, h)) ||
+        (rc = transcode_half_impl(c, src.dev(), src_sc, 1, w, h, {dst.dp, dst_stride, NO_PFS, dst_profile}, dst_sc, nullptr, {c->stream, false})) ||
+        (rc = planes_d2h(c, dst_planes, dst.dp, dst_stride, dst.L, 0, h / 2, c->stream, false)))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return LUMAHIP_OK;
 }
 

@@ -6,7 +6,7 @@
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which instantiation of the fused kernels a launch takes: pick_enc<IN16> / pick_dec<OUT16> / pick_dist<IN16> /
-//                       pick_planes<TransFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, VW>, included by the
+//                       pick_planes<TransFamily | TransHalfFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, VW>, included by the
 //                       kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
@@ -17,6 +17,8 @@
 //   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
 //                       be --, the transcode dispatch and its entry point; measure_planes_impl, the one dispatch of the three plane-fed
 //                       measuring calls, and their three _device entry points
+//   lumahip_transcode_half.hip  pick_planes<TransHalfFamily, .> (every k_transcode_half), the half-resolution transcode's dispatch
+//                       (transcode_plan with scale 2) and its _device entry point of include/lumahip_compare.h
 //   lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip  pick_planes<
 //                       TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, .> (every k_transcode_distortion /
 //                       k_transcode_distortion_map / k_transcode_moments_map), exported as pick_transdist / pick_transdist_map /
@@ -664,7 +666,7 @@ struct TranscodePlan {
     bool subd, sube, any_y;
     size_t lds;      // dynamic LDS of the launch (the measuring kernels' words are static and counted in the budget)
     lh::DecArgs d;   // q, g, src, stride, src_frame_stride, sc, bps, aligned of the source planes
-    lh::EncArgs e;   // q (the composite records for kmode 5), g, sc, bps, aligned of the target side
+    lh::EncArgs e;   // q (the composite records for kmode 5), g (d's; scale 2: of the half-size target), sc, bps, aligned of the target side
     lh::MapGeom m;   // the two maps only
 };
 // m == nullptr, the storing transcode: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one),
@@ -674,7 +676,11 @@ struct TranscodePlan {
 // place -- and, the two maps, by the record's rule; their grid to the number of map tiles.  Every error is raised here, the block
 // size first, before anything of the launch is queued.
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
-                   const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p);
+                   const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p, unsigned scale = 1);
+// ---- lumahip_transcode_half.hip: pick_planes<TransHalfFamily, .> (every k_transcode_half), the dispatch and its entry point
+// source planes of w x h -> destination planes of (w/2) x (h/2): the 2x2 box in linear light between the decode and the encode
+int transcode_half_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
+                        float *stats, const StreamLaunch &o);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 

@@ -17,9 +17,11 @@ namespace lhost {
 // supported set, the LDS budget, the kernel's key, vector width and launch shape -- for the transcode call (m == nullptr: tgt = the
 // planes it writes; out = nullptr) and for the transcode distortion, the transcode distortion map and the transcode moments map (tgt =
 // the given planes they read, out = their words; what differs between the three -- blocks accepted, words, LDS to meet in -- is the
-// record's to say, the kernels' launch bound this plan's).
+// record's to say, the kernels' launch bound this plan's).  scale: 1, or 2 for the half-resolution transcode (lumahip_transcode_half.hip;
+// m == nullptr): w x h is the source's size, the target side is (w / scale) x (h / scale) -- its layout, its extents, its geometry
+// (p.e.g; p.d.g stays the source's), the vector width and the grid, which runs over the target's tiles.
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
-                   const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p)
+                   const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p, unsigned scale)
 {
     const bool measure = m != nullptr, map = measure && m->map(), moments = measure && m->kind == DistWhat::Moments;
     const char *const what = measure ? m->call : "transcode";
@@ -29,20 +31,23 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     const int cse = c->q.cs;
     if ((rc = check_geom(c, w, h, tgt.profile, cse)))
         return rc;
+    if (scale == 2 && ((w | h) & 3))
+        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (half resolution: must be multiples of 4)", w, h);
+    const unsigned tw = w / scale, th = h / scale;   // the target side's size
     if (src.profile < 0 || src.profile > 3)
         return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src.profile);
     const lumahip_ctx::SourceQuant &sq = c->src;
     if (!sq.have)
         return fail(c, LUMAHIP_ERR_STATE, "source quantizer not set (call lumahip_set_source_quantizer first)");
     const int csd = sq.q.cs;
-    if ((rc = check_planes_layout(c, src, nframes, w, h)) || (rc = check_planes_layout(c, tgt, nframes, w, h)))
+    if ((rc = check_planes_layout(c, src, nframes, w, h)) || (rc = check_planes_layout(c, tgt, nframes, tw, th)))
         return rc;
     if (!measure) {
         // no source plane may share a byte with a destination plane over the batch (the extent test of the rotating decode's buffers)
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++)
                 if (ranges_overlap((uintptr_t)src.planes[i], plane_extent(w, h, src.profile, i, src.stride[i], src.pfs[i], nframes),
-                                   (uintptr_t)tgt.planes[j], plane_extent(w, h, tgt.profile, j, tgt.stride[j], tgt.pfs[j], nframes)))
+                                   (uintptr_t)tgt.planes[j], plane_extent(tw, th, tgt.profile, j, tgt.stride[j], tgt.pfs[j], nframes)))
                     return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
     } else if ((rc = m->check_out(c, out)) || (rc = check_out_overlap(c, *m, out, nullptr, {{src, "source "}, {tgt, "given "}}))) {
         // (both plane sets are read only and may overlap each other; the words may not share a byte with anything the launch reads)
@@ -82,31 +87,36 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.kmode = ycode ? 5 : qe.mode;
     p.lds = lds;
     // four pixels per thread and row when every base and stride of both sides allows the vector accesses, else two
-    p.vw = ((w % 4) == 0 && planes_aligned(src, 4) && planes_aligned(tgt, 4)) ? 4 : 2;
-    const bool long_launch = (unsigned long long)w * h * nframes >= 60000000ull;   // as the encode dispatch
+    p.vw = ((tw % 4) == 0 && planes_aligned(src, 4) && planes_aligned(tgt, 4)) ? 4 : 2;
+    // as the encode dispatch; the half-resolution Lu'v' -> Lu'v' kernels always: at VW 4 they are compiled for three waves per SIMD,
+    // which three 256-thread workgroups per CU fill and one 512-thread workgroup does not (profiles/transcode_half_launch_shapes.txt)
+    const bool long_launch = scale == 2 || (unsigned long long)w * h * nframes >= 60000000ull;
     p.threads = block_threads_for(c, lds, long_launch && !any_y, any_y);
     // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
     // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
     // (the moments kernels: for lh::transmoments_threads_bound, the function their launch bound is written with)
     p.threads = std::min(p.threads, moments   ? transmoments_threads_bound(csd, cse, p.vw)
                                     : measure ? TransDistFamily::bound(any_y)
-                                              : TransFamily::bound(any_y));
+                                    : scale == 2 ? transhalf_threads_bound(csd, cse, p.vw)
+                                                 : TransFamily::bound(any_y));
     if (map)
         p.threads = m->clamp_threads(p.threads);
     p.d = DecArgs{};
+    p.e = EncArgs{};
     if (!make_geom(p.d.g, w, h, p.vw, p.threads / 64, nframes))
         return fail(c, LUMAHIP_ERR_ARG, "batch too large: more than 2^31 tiles in one launch");
+    p.e.g = p.d.g;
+    if (scale != 1)
+        make_geom(p.e.g, tw, th, p.vw, p.threads / 64, nframes);   // (no larger and no more tiles than the source's: it cannot fail where that did not)
     p.d.q = sq.q;
     p.d.sc = src_sc;
     read_planes(p.d, src, p.vw);
-    p.e = EncArgs{};
-    p.e.g = p.d.g;
     p.e.q = qe;
     p.e.q.cs = cse;
     p.e.sc = dst_sc;
     p.e.bps = tgt.profile > 1 ? 2 : 1;
     p.e.aligned = planes_aligned(tgt, p.vw) ? 1 : 0;
-    p.grid = grid_for(c, p.threads, p.d.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
+    p.grid = grid_for(c, p.threads, p.e.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
     if (map)
         map_shape(*m, p.d.g, p.threads, p.m, p.grid);
     return LUMAHIP_OK;
