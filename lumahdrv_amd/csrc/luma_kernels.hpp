@@ -771,8 +771,49 @@ struct DecUnit {
     bool valid;
 };
 
-// (dec_load_at below states the same loads for given coordinates: a change to the loads here is a change there too.  The two stay
-//  apart so that the kernels that call dec_load keep their listings; having dec_load call dec_load_at is due once that can be re-checked.)
+// Where row r of plane pl of the unit (f, ux, uy) begins, n samples of that plane to a unit row: THE statement of where a code
+// plane's samples live, for every function that reads one.  A unit is two luminance rows deep; SUB: and one row of either chroma
+// plane.  (The plane row is computed inside the sum, behind the frame's offset, and not handed in: with it computed first the
+// compiler orders instructions of some transcode kernels differently, profiles/plane_loads_codegen.txt.)
+template <bool SUB>
+LH_DEV const unsigned char *dec_row(const DecArgs &a, int pl, int f, int ux, int uy, int r, int n)
+{
+    const int rows = (SUB && pl) ? 1 : 2;   // plane rows to a unit
+    return a.src[pl] + (size_t)f * a.src_frame_stride[pl] + (size_t)(rows * uy + r) * a.stride[pl] + (size_t)ux * n * a.bps;
+}
+
+// The unpacking loads of the unit at u.f, u.ux, u.uy, once for everyone: dec_load (which finds the unit from its tile), dec_load_at
+// (which is given it) and dec_finish (for the rows its vector loads cannot take, aligned = 0)
+template <bool SUB, int VW>
+LH_DEV void dec_load_rows(DecUnit<SUB, VW> &u, const DecArgs &a)
+{
+    const int f = u.f, ux = u.ux, uy = u.uy;
+    {
+        const unsigned char *s = dec_row<SUB>(a, 0, f, ux, uy, 0, VW);
+        load_samples<VW>(s, u.y[0], a.bps, a.aligned);
+        load_samples<VW>(s + a.stride[0], u.y[1], a.bps, a.aligned);
+    }
+    if constexpr (SUB) {
+        constexpr int NQ = VW / 2;
+        load_samples<NQ>(dec_row<SUB>(a, 1, f, ux, uy, 0, NQ), u.c1, a.bps, a.aligned);
+        load_samples<NQ>(dec_row<SUB>(a, 2, f, ux, uy, 0, NQ), u.c2, a.bps, a.aligned);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            int row[VW];
+            load_samples<VW>(dec_row<SUB>(a, 1, f, ux, uy, r, VW), row, a.bps, a.aligned);
+#pragma unroll
+            for (int i = 0; i < VW; i++)
+                u.c1[r * VW + i] = row[i];
+            load_samples<VW>(dec_row<SUB>(a, 2, f, ux, uy, r, VW), row, a.bps, a.aligned);
+#pragma unroll
+            for (int i = 0; i < VW; i++)
+                u.c2[r * VW + i] = row[i];
+        }
+    }
+}
+
+// The unit of lane (tx, ty) in tile t; u.valid: the tile exists and the unit lies inside the frame
 template <bool SUB, int VW>
 LH_DEV void dec_load(DecUnit<SUB, VW> &u, const DecArgs &a, int t, int tx, int ty, int NW)
 {
@@ -786,41 +827,12 @@ LH_DEV void dec_load(DecUnit<SUB, VW> &u, const DecArgs &a, int t, int tx, int t
     if (u.ux >= a.g.unitsX || u.uy >= a.g.unitsY)
         return;
     u.valid = true;
-    const int f = u.f, ux = u.ux, uy = u.uy;
-    {
-        const unsigned char *s = a.src[0] + (size_t)f * a.src_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] +
-                                 (size_t)ux * VW * a.bps;
-        load_samples<VW>(s, u.y[0], a.bps, a.aligned);
-        load_samples<VW>(s + a.stride[0], u.y[1], a.bps, a.aligned);
-    }
-    if constexpr (SUB) {
-        constexpr int NQ = VW / 2;
-        load_samples<NQ>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)uy * a.stride[1] + (size_t)ux * NQ * a.bps,
-                         u.c1, a.bps, a.aligned);
-        load_samples<NQ>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)uy * a.stride[2] + (size_t)ux * NQ * a.bps,
-                         u.c2, a.bps, a.aligned);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            int row[VW];
-            load_samples<VW>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)(2 * uy + r) * a.stride[1] +
-                                 (size_t)ux * VW * a.bps, row, a.bps, a.aligned);
-#pragma unroll
-            for (int i = 0; i < VW; i++)
-                u.c1[r * VW + i] = row[i];
-            load_samples<VW>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)(2 * uy + r) * a.stride[2] +
-                                 (size_t)ux * VW * a.bps, row, a.bps, a.aligned);
-#pragma unroll
-            for (int i = 0; i < VW; i++)
-                u.c2[r * VW + i] = row[i];
-        }
-    }
+    dec_load_rows<SUB, VW>(u, a);
 }
 
-// dec_load's loads for the unit at given coordinates: no tile arithmetic and no range test, both the caller's (k_transcode_half,
-// whose loop runs over the target's tiles and whose source units are in range whenever the target unit is).  Keep in step with
-// dec_load.  The unit records its coordinates as dec_load's does, so that a DecUnit is one thing wherever it was loaded; k_transcode_half
-// itself reads only the samples.
+// The unit at given coordinates: no tile arithmetic and no range test, both the caller's (k_transcode_half, whose loop runs over
+// the target's tiles and whose source units are in range whenever the target unit is).  The unit records its coordinates as
+// dec_load's does, so that a DecUnit is one thing wherever it was loaded; k_transcode_half itself reads only the samples.
 template <bool SUB, int VW>
 LH_DEV void dec_load_at(DecUnit<SUB, VW> &u, const DecArgs &a, int f, int ux, int uy)
 {
@@ -828,34 +840,7 @@ LH_DEV void dec_load_at(DecUnit<SUB, VW> &u, const DecArgs &a, int f, int ux, in
     u.f = f;
     u.ux = ux;
     u.uy = uy;
-    {
-        const unsigned char *s = a.src[0] + (size_t)f * a.src_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] +
-                                 (size_t)ux * VW * a.bps;
-        load_samples<VW>(s, u.y[0], a.bps, a.aligned);
-        load_samples<VW>(s + a.stride[0], u.y[1], a.bps, a.aligned);
-    }
-    if constexpr (SUB) {
-        constexpr int NQ = VW / 2;
-        load_samples<NQ>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)uy * a.stride[1] + (size_t)ux * NQ * a.bps,
-                         u.c1, a.bps, a.aligned);
-        load_samples<NQ>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)uy * a.stride[2] + (size_t)ux * NQ * a.bps,
-                         u.c2, a.bps, a.aligned);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            int row[VW];
-            load_samples<VW>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)(2 * uy + r) * a.stride[1] +
-                                 (size_t)ux * VW * a.bps, row, a.bps, a.aligned);
-#pragma unroll
-            for (int i = 0; i < VW; i++)
-                u.c1[r * VW + i] = row[i];
-            load_samples<VW>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)(2 * uy + r) * a.stride[2] +
-                                 (size_t)ux * VW * a.bps, row, a.bps, a.aligned);
-#pragma unroll
-            for (int i = 0; i < VW; i++)
-                u.c2[r * VW + i] = row[i];
-        }
-    }
+    dec_load_rows<SUB, VW>(u, a);
 }
 
 // ---- the same loads as a REAL prefetch (round 6) ---------------------------------------------------------------------
@@ -919,6 +904,8 @@ LH_DEV void unpack_raw(const uint32_t (&r)[2], int (&c)[N], int bps)
 template <bool SUB, int VW>
 LH_DEV void dec_issue(DecRaw<SUB, VW> &u, const DecArgs &a, int t, int tx, int ty, int NW)
 {
+    // (dec_load's tile -> unit lines, written out a second time: behind a function shared with dec_load -- returning bool, or void
+    //  with the test on u.valid -- every kernel that calls dec_issue compiles to other instructions, profiles/plane_loads_codegen.txt)
     u.valid = false;
     if (t >= a.g.totalTiles)
         return;
@@ -932,18 +919,18 @@ LH_DEV void dec_issue(DecRaw<SUB, VW> &u, const DecArgs &a, int t, int tx, int t
     if (!a.aligned)
         return;   // (dec_finish loads these rows itself)
     const int f = u.f, ux = u.ux, uy = u.uy;
-    const unsigned char *s = a.src[0] + (size_t)f * a.src_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] + (size_t)ux * VW * a.bps;
+    const unsigned char *s = dec_row<SUB>(a, 0, f, ux, uy, 0, VW);
     load_raw<VW>(s, u.y[0], a.bps);
     load_raw<VW>(s + a.stride[0], u.y[1], a.bps);
     if constexpr (SUB) {
         constexpr int NQ = VW / 2;
-        load_raw<NQ>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)uy * a.stride[1] + (size_t)ux * NQ * a.bps, u.c1[0], a.bps);
-        load_raw<NQ>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)uy * a.stride[2] + (size_t)ux * NQ * a.bps, u.c2[0], a.bps);
+        load_raw<NQ>(dec_row<SUB>(a, 1, f, ux, uy, 0, NQ), u.c1[0], a.bps);
+        load_raw<NQ>(dec_row<SUB>(a, 2, f, ux, uy, 0, NQ), u.c2[0], a.bps);
     } else {
 #pragma unroll
         for (int r = 0; r < 2; r++) {
-            load_raw<VW>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)(2 * uy + r) * a.stride[1] + (size_t)ux * VW * a.bps, u.c1[r], a.bps);
-            load_raw<VW>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)(2 * uy + r) * a.stride[2] + (size_t)ux * VW * a.bps, u.c2[r], a.bps);
+            load_raw<VW>(dec_row<SUB>(a, 1, f, ux, uy, r, VW), u.c1[r], a.bps);
+            load_raw<VW>(dec_row<SUB>(a, 2, f, ux, uy, r, VW), u.c2[r], a.bps);
         }
     }
 }
@@ -979,28 +966,7 @@ LH_DEV void dec_finish(DecUnit<SUB, VW> &u, const DecRaw<SUB, VW> &w, const DecA
         }
         return;
     }
-    const int f = u.f, ux = u.ux, uy = u.uy;
-    const unsigned char *s = a.src[0] + (size_t)f * a.src_frame_stride[0] + (size_t)(2 * uy) * a.stride[0] + (size_t)ux * VW * a.bps;
-    load_samples<VW>(s, u.y[0], a.bps, 0);
-    load_samples<VW>(s + a.stride[0], u.y[1], a.bps, 0);
-    if constexpr (SUB) {
-        constexpr int NQ = VW / 2;
-        load_samples<NQ>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)uy * a.stride[1] + (size_t)ux * NQ * a.bps, u.c1, a.bps, 0);
-        load_samples<NQ>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)uy * a.stride[2] + (size_t)ux * NQ * a.bps, u.c2, a.bps, 0);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            int row[VW];
-            load_samples<VW>(a.src[1] + (size_t)f * a.src_frame_stride[1] + (size_t)(2 * uy + r) * a.stride[1] + (size_t)ux * VW * a.bps, row, a.bps, 0);
-#pragma unroll
-            for (int i = 0; i < VW; i++)
-                u.c1[r * VW + i] = row[i];
-            load_samples<VW>(a.src[2] + (size_t)f * a.src_frame_stride[2] + (size_t)(2 * uy + r) * a.stride[2] + (size_t)ux * VW * a.bps, row, a.bps, 0);
-#pragma unroll
-            for (int i = 0; i < VW; i++)
-                u.c2[r * VW + i] = row[i];
-        }
-    }
+    dec_load_rows<SUB, VW>(u, a);   // (a.aligned is 0 here)
 }
 
 // the unit's samples must be in registers HERE (the compiler may not sink the unpacking, and with it the wait for the loads,
@@ -1333,31 +1299,20 @@ __global__ __launch_bounds__(1024) void k_decode(const DecArgs a)
     const int G = gridDim.x;
 
     bool any_gather = false;
-#ifndef LH_DEC_PF
-#define LH_DEC_PF 1
-#endif
-    // PF: the real prefetch of DecRaw -- the kernels with microseconds of arithmetic per unit and four waves per SIMD (YCbCr)
     // How the next unit's rows are loaded (same-box A/B per kernel family, profiles/r06_decode_prefetch.txt):
-    //   PFM 1  raw loads BEFORE this unit is processed, unpacked between its arithmetic and its stores (DecRaw above): the YCbCr
-    //          kernels (-2.5 % on unrelated pixels, +5 % on pictures) and every 4:4:4 kernel (six row loads per unit that used to be
-    //          six serial round trips: -10 ... -17 %);
-    //   PFM 2  raw loads AFTER this unit's stores, unpacked at the top of the next iteration: the four loads go out back to back
-    //          instead of one round trip each, in the order (stores, then loads) of the HBM-bound kernels: good for the HBM-bound
-    //          4:2:0 kernels with 8-bit samples (-5 %), bad for 16-bit ones (below); not instantiated by default;
-    //   PFM 0  dec_load as before round 6: the HBM-bound 4:2:0 kernels with 16-BIT samples (BASELINE's profile 2), where either
-    //          form above is 4 - 6 % SLOWER -- four loads in flight per wave instead of one round trip after another is more
-    //          concurrency than that traffic mix likes (the same finding as "5 workgroups per CU, not 8", lumahip_launch.hip).
-    // The 4:2:0 kernels of the HBM-bound colour spaces keep PFM 0 for both sample sizes (carrying both loops and picking by the
-    // sample size at run time gave 8-bit 4:2:0 -3.6 % and cost the 13-bit tables +1 %: not worth a second loop in BASELINE's kernel).
-#ifndef LH_DEC_PFM_SUB
-#define LH_DEC_PFM_SUB 0
-#endif
-    auto run = [&](auto pfm_tag) {
-    constexpr int PFM = decltype(pfm_tag)::value;
-    constexpr bool PF = PFM == 1;
+    //   PF   raw loads BEFORE this unit is processed, unpacked between its arithmetic and its stores (DecRaw above): the YCbCr
+    //        kernels (-2.5 % on unrelated pixels, +5 % on pictures) and every 4:4:4 kernel (six row loads per unit that used to be
+    //        six serial round trips: -10 ... -17 %);
+    //   !PF  dec_load behind this unit's stores: the 4:2:0 kernels of the HBM-bound colour spaces, whose 16-bit samples (BASELINE's
+    //        profile 2) are 4 - 6 % SLOWER with four loads in flight per wave instead of one round trip after another.
+    // (The record also holds the rejected third form, raw loads after the stores: it helped only 8-bit 4:2:0.)
+    // The loop stays inside this lambda, a leftover of the time it was instantiated per form: written straight into the kernel
+    // nearly every k_decode compiles to other instructions (profiles/plane_loads_codegen.txt).
+    auto run = [&](auto pf_tag) {
+    constexpr bool PF = decltype(pf_tag)::value;
     DecUnit<SUB, VW> cur, nxt;
     DecRaw<SUB, VW> nxt_w;
-    if constexpr (PFM != 0) {
+    if constexpr (PF) {
         dec_issue<SUB, VW>(nxt_w, a, blockIdx.x, tx, ty, NW);
         dec_finish<SUB, VW>(cur, nxt_w, a);
     } else {
@@ -1395,21 +1350,12 @@ __global__ __launch_bounds__(1024) void k_decode(const DecArgs a)
         } else {
             hook();
         }
-        if constexpr (PFM == 2) {
-            dec_issue<SUB, VW>(nxt_w, a, t + G, tx, ty, NW);
-            dec_finish<SUB, VW>(nxt, nxt_w, a);   // (nothing between the loads depends on them: the waits sit here, behind all of them)
-        } else if constexpr (PFM == 0) {
+        if constexpr (!PF)
             dec_load<SUB, VW>(nxt, a, t + G, tx, ty, NW);
-        }
         cur = nxt;
     }
     };   // run
-    if constexpr (LH_DEC_PF == 0)
-        run(std::integral_constant<int, 0>());
-    else if constexpr (CS == CS_YCBCR || !SUB)
-        run(std::integral_constant<int, 1>());
-    else
-        run(std::integral_constant<int, LH_DEC_PFM_SUB>());
+    run(std::integral_constant<bool, (CS == CS_YCBCR || !SUB)>());
     if constexpr (RB) {
         if (a.rb_flag) {   // (kernel argument: uniform)
             if (any_gather)
@@ -1760,12 +1706,10 @@ struct DistMeasureUnit {
     LH_DEVS void row(int pl, int r, const int (&codes)[N]) const
     {
         int given[N];
-        if (d.aligned) {
+        if (d.aligned) {   // (given_row's lines, written out: see there)
             unpack_raw<N>(pl == 0 ? g.y[r] : pl == 1 ? g.c1[r] : g.c2[r], given, d.bps);
         } else {
-            const int y0 = (SUB && pl) ? g.uy : 2 * g.uy;   // first plane row of the unit
-            load_samples<N>(d.src[pl] + (size_t)g.f * d.src_frame_stride[pl] + (size_t)(y0 + r) * d.stride[pl] + (size_t)g.ux * N * d.bps, given,
-                            d.bps, 0);
+            load_samples<N>(dec_row<SUB>(d, pl, g.f, g.ux, g.uy, r, N), given, d.bps, 0);
         }
 #pragma unroll
         for (int i = 0; i < N; i++) {
@@ -2195,19 +2139,17 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) void 
 // another record (MomentBlockAcc): 15 words per block, LDS adds only, no shortcut for waves without a difference.  B = 8 makes a
 // block 2 lanes at VW 4 (map_lanes_meet's pair step alone) and a map tile 32 blocks.
 // Reads 12 + 3 B per pixel (6 + 3 from binary16 frames), writes 120 B per block; no scratch planes, no global atomic, no memset.
-// Row r of plane pl of the given unit exactly as DistMeasureUnit::row fetches it.  That one keeps its own copy of these lines: with
-// the fetch behind a function -- free, member of a base, by reference or by value -- the compiler allocates the registers of every
-// k_distortion, k_distortion_map and k_transcode_distortion(_map) kernel differently (same instructions, other registers and order;
-// profiles/moments_map_codegen.txt), and those kernels are measured as they are.
+// Row r of plane pl of the given unit: the prefetched words where the set is `aligned`, else loaded here.  DistMeasureUnit::row
+// keeps these four lines written out (the address itself is dec_row's in both): calling this function from there, tried again with
+// dec_row in place, still gives every k_distortion(_map), k_transcode_distortion(_map) and k_planes_distortion(_map) kernel other
+// instruction counts or orders (profiles/plane_loads_codegen.txt, and before it profiles/moments_map_codegen.txt).
 template <bool SUB, int VW, int N>
 LH_DEV void given_row(const DecRaw<SUB, VW> &g, const DecArgs &d, int pl, int r, int (&given)[N])
 {
     if (d.aligned) {
         unpack_raw<N>(pl == 0 ? g.y[r] : pl == 1 ? g.c1[r] : g.c2[r], given, d.bps);
     } else {
-        const int y0 = (SUB && pl) ? g.uy : 2 * g.uy;   // first plane row of the unit
-        load_samples<N>(d.src[pl] + (size_t)g.f * d.src_frame_stride[pl] + (size_t)(y0 + r) * d.stride[pl] + (size_t)g.ux * N * d.bps, given,
-                        d.bps, 0);
+        load_samples<N>(dec_row<SUB>(d, pl, g.f, g.ux, g.uy, r, N), given, d.bps, 0);
     }
 }
 
