@@ -209,6 +209,16 @@ _ABI_COMPARE = {
 }
 COMPARE_SYMBOLS = tuple(_ABI_COMPARE)
 
+# The calls include/lumahip_ladder.h declares (a half-size rendition scored against the source's half-resolution transcode), bound
+# like _ABI's; tests/test_transcode_half_distortion_host.py holds this table and the header to each other.
+_ABI_LADDER = {
+    "lumahip_transcode_half_distortion_frames_device": (_i, _TWO_SETS + (_vp,)),
+    "lumahip_transcode_half_distortion_map_frames_device": (_i, _TWO_SETS + (_u, _vp)),
+    "lumahip_transcode_half_distortion_frame_host": (_i, _TWO_SETS_HOST + (_vp,)),
+    "lumahip_transcode_half_distortion_map_frame_host": (_i, _TWO_SETS_HOST + (_u, _vp, _sz)),
+}
+LADDER_SYMBOLS = tuple(_ABI_LADDER)
+
 
 class LumaHipError(RuntimeError):
     """Counterpart of the reference's LumaException (include/luma/luma_exception.h:53-71)."""
@@ -243,7 +253,7 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
                   "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip",
                   "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip", "lumahip_light_level.hip",
-                  "lumahip_transcode_half.hip")
+                  "lumahip_transcode_half.hip", "lumahip_transcode_half_distortion.hip", "lumahip_transcode_half_distortion_map.hip")
 
 
 def kernel_source_sha() -> str:
@@ -276,7 +286,7 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()) + list(_ABI_COMPARE.items()):
+    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()) + list(_ABI_COMPARE.items()) + list(_ABI_LADDER.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
@@ -593,13 +603,13 @@ class Context:
         return self._measured(fn, args, w, h, words, dims, block)
 
     def _measure_planes(self, fn, planes, strides, w, h, given_planes, given_strides, src_sc, src_profile, dst_sc, dst_profile, dims=None,
-                        block=None, words=4):
-        """the plane-fed measuring host forms"""
+                        block=None, words=4, scale=1):
+        """the plane-fed measuring host forms; scale 2: w x h is the source's size, the given planes and the words are of (w/2) x (h/2)"""
         planes = [np.ascontiguousarray(p) for p in planes]
         given_planes = [np.ascontiguousarray(p) for p in given_planes]
         args = (_arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides), src_profile, src_sc, w, h,
                 _arr3(C.c_void_p, [p.ctypes.data for p in given_planes]), _arr3(C.c_int, given_strides), dst_profile, dst_sc)
-        return self._measured(fn, args, w, h, words, dims, block)
+        return self._measured(fn, args, w // scale, h // scale, words, dims, block)
 
     def _measure_two_sets(self, fn, a_planes, a_strides, w, h, b_planes, b_strides, profile, words, dims=None, block=None):
         """the plane-to-plane measuring host forms"""
@@ -761,6 +771,21 @@ class Context:
         moments_sample_counts(w, h, dst_profile, block) and code_ssim apply unchanged"""
         return self._measure_planes(self.L.lumahip_transcode_moments_map_frame_host, planes, strides, w, h, given_planes, given_strides,
                                     src_sc, src_profile, dst_sc, dst_profile, moments_map_dims, block, words=5)
+
+    def transcode_half_distortion_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
+                                        dst_profile=2) -> np.ndarray:
+        """planes: code planes of w x h under the source quantizer; given_planes: code planes of (w/2) x (h/2) in the target's format.
+        Returns a (3, 4) uint64 array: per plane {sse, sad, max_abs, n_differ} of the planes transcode_half_frame would write against
+        the given ones, in one fused launch; code_psnr applies unchanged"""
+        return self._measure_planes(self.L.lumahip_transcode_half_distortion_frame_host, planes, strides, w, h, given_planes, given_strides,
+                                    src_sc, src_profile, dst_sc, dst_profile, scale=2)
+
+    def transcode_half_distortion_map_frame(self, planes, strides, w, h, given_planes, given_strides, src_sc=1.0, src_profile=2, dst_sc=1.0,
+                                            dst_profile=2, block=16) -> np.ndarray:
+        """transcode_half_distortion_frame's words per block of block x block luma pixels (16, 32 or 64) of the half-size target: a
+        (nby, nbx, 3, 4) uint64 array with distortion_map_dims(w // 2, h // 2, block), in one launch"""
+        return self._measure_planes(self.L.lumahip_transcode_half_distortion_map_frame_host, planes, strides, w, h, given_planes,
+                                    given_strides, src_sc, src_profile, dst_sc, dst_profile, distortion_map_dims, block, scale=2)
 
     def planes_distortion_frame(self, a_planes, a_strides, w, h, b_planes, b_strides, profile=2) -> np.ndarray:
         """two sets of code planes of one profile, three (rows, stride) uint8 arrays each, compared as they are (no quantizer
@@ -992,6 +1017,23 @@ class Context:
         self._two_sets(self.L.lumahip_transcode_moments_map_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
                        src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
                        block, mom_ptr)
+
+    # given planes of (w/2) x (h/2) against the source planes' half-resolution transcode (include/lumahip_ladder.h): the arguments are
+    # transcode_distortion_frames_device's, w x h the source's size; out_ptr receives nframes x 3 planes x 4 words (zeroed by the call)
+    def transcode_half_distortion_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w,
+                                                h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc, out_ptr):
+        self._two_sets(self.L.lumahip_transcode_half_distortion_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
+                       src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
+                       out_ptr)
+
+    # the same per block x block luma pixels of the half-size target (16, 32 or 64): map_ptr receives nframes x nby x nbx x 3 planes x 4
+    # words with distortion_map_dims(w // 2, h // 2, block), every word written by the launch
+    def transcode_half_distortion_map_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc,
+                                                    nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile,
+                                                    dst_sc, block, map_ptr):
+        self._two_sets(self.L.lumahip_transcode_half_distortion_map_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides,
+                       src_profile, src_sc, nframes, w, h, given_plane_ptrs, given_strides, given_plane_frame_strides, dst_profile, dst_sc,
+                       block, map_ptr)
 
     # two sets of code planes of one profile compared as they are (include/lumahip_compare.h; no quantizer needed): out_ptr receives
     # nframes x 3 planes x {sse, sad, max_abs, n_differ} as uint64 (zeroed by the call), e from set A and g from set B

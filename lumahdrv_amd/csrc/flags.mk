@@ -22,6 +22,9 @@ FLAGS_lumahip_transcode_distortion := $(FLAGS_lumahip_transcode)
 FLAGS_lumahip_transcode_distortion_map := $(FLAGS_lumahip_transcode)
 #   lumahip_transcode_moments_map: the same -- k_transcode_moments_map is k_transcode_distortion_map with another consumer.
 FLAGS_lumahip_transcode_moments_map := $(FLAGS_lumahip_transcode)
+#   lumahip_transcode_half_distortion / _map: the same -- their kernels are k_transcode_half's front end with the measuring consumers.
+FLAGS_lumahip_transcode_half_distortion := $(FLAGS_lumahip_transcode)
+FLAGS_lumahip_transcode_half_distortion_map := $(FLAGS_lumahip_transcode)
 #   lumahip_distortion / _f16: the encode units' strategy -- k_distortion is k_encode up to the codes, with the stores replaced by
 #   integer accumulation.  Not measured either way yet.
 FLAGS_lumahip_distortion := $(FLAGS_lumahip_encode)

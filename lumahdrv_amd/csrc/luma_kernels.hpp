@@ -2390,6 +2390,159 @@ void k_transcode_moments_map(const TransDistMapArgs a)
     }
 }
 
+// ---- HALF-RESOLUTION TRANSCODE DISTORTION, PER FRAME AND PER BLOCK ----------------------------------
+// How far GIVEN code planes of (w/2) x (h/2) are from the planes k_transcode_half would write for source planes of w x h: e is the
+// sample that kernel stores (the decoded floats, the 2x2 box ((a + b) + (c + d)) * 0.25f, the target's encode), g the sample that is
+// there.  k_transcode_half's front end (half_locate / half_issue / half_fill over the TARGET's tiles, a.e.g; a.d.g is the source's
+// geometry) with k_transcode_distortion's consumer and flush site, and with k_transcode_distortion_map's loop and owner per word.
+// The argument structs are those kernels' (TransDistArgs, TransDistMapArgs); a.g carries the target's geometry (a.g.g == a.e.g), so
+// dec_issue finds the given unit of a target tile as it finds any unit, and the given words are issued right behind half_issue's
+// loads for the next target unit.  Reads 4 x 3 + 3 B per target pixel at profile 2 on both sides; no scratch planes, no float frame.
+// Register budget (profiles/transcode_half_distortion_codegen.txt has the compiler's table): k_transcode_half's kernels plus the
+// consumer's accumulators (18 registers per frame, 15 per block) and up to 8 given words.  One function of (CSD, CSE, VW) per
+// kernel, which its __launch_bounds__ / amdgpu_waves_per_eu are written with and transcode_plan clamps the launch to.  Every kernel
+// is bounded at 512 threads; YCbCr on either side gets two waves per SIMD (256 registers), Lu'v' -> Lu'v' three (168).  Under that
+// bound a YCbCr 4:4:4 source (88 - 148 B of scratch per lane at 256 registers) and a Lu'v' 4:4:4 source with a Lu'v' target (148 -
+// 232 B at 168) cannot be had at VW 4 without scratch: transhalfdist_vw4 says which families exist at VW 4, the plan asks it, and
+// the others are instantiated at VW 2 only.
+constexpr int transhalfdist_threads_bound(int csd, int cse, int vw) { return 512; }
+constexpr int transhalfdist_waves(int csd, int cse, int vw) { return (csd == CS_YCBCR || cse == CS_YCBCR) ? 2 : 3; }
+constexpr int transhalfmap_threads_bound(int csd, int cse, int vw) { return transhalfdist_threads_bound(csd, cse, vw); }
+constexpr int transhalfmap_waves(int csd, int cse, int vw) { return transhalfdist_waves(csd, cse, vw); }
+// whether the kernels of source (csd, subd) and target colour space cse exist at VW 4 (both calls decide alike: the front end is
+// what fills the registers)
+constexpr bool transhalfdist_vw4(int csd, bool subd, int cse) { return subd || (csd == CS_LUV && cse == CS_YCBCR); }
+
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__(transhalfdist_threads_bound(CSD, CSE, VW)) __attribute__((amdgpu_waves_per_eu(transhalfdist_waves(CSD, CSE, VW))))
+void k_transcode_half_distortion(const TransDistArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *const s_acc = dist_words();
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+    constexpr int NPF = half_prefetch<SUBD, VW>();
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    DistAcc acc;
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    DecUnit<SUBD, VW> pf[NPF];
+    DecRaw<SUBE, VW> given;
+    int f = 0, ux = 0, uy = 0;
+    bool valid = half_locate(a.e.g, blockIdx.x, tx, ty, NW, f, ux, uy);
+    if (valid)
+        half_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+    dec_issue<SUBE, VW>(given, a.g, blockIdx.x, tx, ty, NW);
+    for (int t = blockIdx.x;; t += G) {
+        const bool done = t >= a.e.g.totalTiles;
+        dist_flush(acc, s_acc, done ? -2 : t / a.e.g.tilesPerFrame, a.out);
+        if (done)
+            break;
+        if (valid) {
+            EncUnit<VW> u;
+            if constexpr (Front::YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    half_fill<CSD, SUBD, VW, false, true, true>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+                else
+                    half_fill<CSD, SUBD, VW, false, true, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            } else {
+                half_fill<CSD, SUBD, VW, true, false, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, Front::YE, false, false>(u, a.e, ke, c0, c1, c2, st);
+            const DistMeasureUnit<SUBE, VW> out{given, a.g, acc, mask};
+            enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+        }
+        valid = half_locate(a.e.g, t + G, tx, ty, NW, f, ux, uy);
+        if (valid)
+            half_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+        dec_issue<SUBE, VW>(given, a.g, t + G, tx, ty, NW);
+    }
+}
+
+// MapGeom is of the target's geometry; map_subtile names the next target tile, whose source units and, right behind them, given
+// words are issued before the flush and are in flight across its barriers
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__(transhalfmap_threads_bound(CSD, CSE, VW)) __attribute__((amdgpu_waves_per_eu(transhalfmap_waves(CSD, CSE, VW))))
+void k_transcode_half_distortion_map(const TransDistMapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long *const s_map = dist_map_words();
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+    constexpr int NPF = half_prefetch<SUBD, VW>();
+
+    const int mask = a.g.bps == 2 ? 0xffff : 0xff;
+    DistBlockAcc acc;
+    EncStats st;   // (enc_transform's parameter; unused with STATS = false)
+    DecUnit<SUBD, VW> pf[NPF];
+    DecRaw<SUBE, VW> given;
+    int m = blockIdx.x, s = 0;
+    int f = 0, ux = 0, uy = 0;
+    bool valid;
+    {
+        const int t = map_subtile(a.m, a.e.g, m, 0);
+        valid = half_locate(a.e.g, t, tx, ty, NW, f, ux, uy);
+        if (valid)
+            half_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+        dec_issue<SUBE, VW>(given, a.g, t, tx, ty, NW);
+    }
+    while (m < a.m.totalMapTiles) {   // workgroup-uniform
+        if (valid) {
+            EncUnit<VW> u;
+            if constexpr (Front::YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    half_fill<CSD, SUBD, VW, false, true, true>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+                else
+                    half_fill<CSD, SUBD, VW, false, true, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            } else {
+                half_fill<CSD, SUBD, VW, true, false, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, Front::YE, false, false>(u, a.e, ke, c0, c1, c2, st);
+            const DistMeasureUnit<SUBE, VW, DistBlockAcc> out{given, a.g, acc, mask};
+            enc_codes<CSE, SUBE, VW, LM>(c0, c1, c2, a.e.q, static_cast<const float *>(nullptr), s_rec, out);   // (record searches: no table pointer)
+        }
+        const bool last = s + 1 == a.m.S;
+        const int mn = last ? m + G : m, sn = last ? 0 : s + 1;
+        const int t = map_subtile(a.m, a.e.g, mn, sn);
+        valid = half_locate(a.e.g, t, tx, ty, NW, f, ux, uy);
+        if (valid)
+            half_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+        dec_issue<SUBE, VW>(given, a.g, t, tx, ty, NW);
+        if (last) {
+            dist_map_flush<VW>(acc, s_map, a.m, a.e.g, a.map, m, tx);
+            acc.reset();
+        }
+        m = mn;
+        s = sn;
+    }
+}
+
 // ---- PLANES IN, AS THEY ARE -------------------------------------------------------------------------
 // The third front end over the same three consumers: e is not computed, it is the sample present in a plane set A, as g is the one
 // present in a set B -- both read as the decoder reads them, no quantizer on either side (DecArgs::q stays unused), no tables, no

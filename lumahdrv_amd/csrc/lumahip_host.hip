@@ -1137,7 +1137,7 @@ extern "C" int lumahip_transcode_half_frame_host(lumahip_ctx *c, const unsigned 
     return LUMAHIP_OK;
 }
 
-// The one host form of the eleven measuring _frame_host entry points: one frame's inputs in host memory -> what the call delivers
+// The one host form of the thirteen measuring _frame_host entry points: one frame's inputs in host memory -> what the call delivers
 // (m, of one frame), synchronously on the context's stream.  The inputs: a float frame (frame; rgb may then not be null) and / or the
 // plane sets src and tgt as planes_staging takes them (quantizers: its flag), which the context's staging holds while `dispatch(f, d_out,
 // launch)` runs the family's device dispatch on them: f = the staged frame, d_out = m.words() device words.  scale: the light level's,
@@ -1145,8 +1145,10 @@ extern "C" int lumahip_transcode_half_frame_host(lumahip_ctx *c, const unsigned 
 // quantizers, strides), out_words below a map's words (per-frame words: ignored) -- before anything is uploaded.
 template <typename F>
 static int measure_host(lumahip_ctx *c, const MeasureOut &m, bool frame, const float *rgb, StagedPlanes *src, StagedPlanes *tgt, bool quantizers,
-                        const float *scale, uint64_t *out, size_t out_words, F dispatch)
+                        const float *scale, uint64_t *out, size_t out_words, F dispatch, const SourceSize *full = nullptr)
 {
+    // full: the half-resolution calls -- the source set is staged at its own size, the set `tgt` at the record's, half of it
+    const unsigned sw = full ? full->w : m.w, sh = full ? full->h : m.h;
     if (!c)
         return LUMAHIP_ERR_ARG;
     if ((frame && !rgb) || (src && (!src->planes || !src->stride)) || (tgt && (!tgt->planes || !tgt->stride)) || !out)
@@ -1154,7 +1156,7 @@ static int measure_host(lumahip_ctx *c, const MeasureOut &m, bool frame, const f
     int rc;
     // (the scale's test sits where it always sat: behind the size of a frame that comes alone, in front of a plane set's staging)
     if ((rc = m.check_block(c)) || (scale && ((!tgt && (rc = check_size(c, m.w, m.h))) || (rc = check_light_scale(c, *scale)))) ||
-        (rc = planes_staging(c, m.w, m.h, src, tgt, quantizers)))
+        (rc = planes_staging(c, sw, sh, src, tgt, quantizers, full ? full->scale : 1)))
         return rc;
     // (the words' count needs a checked geometry)
     if (m.map() && out_words < m.words())
@@ -1163,7 +1165,7 @@ static int measure_host(lumahip_ctx *c, const MeasureOut &m, bool frame, const f
     if ((rc = ensure(c, (void **)&c->d_arr, &c->d_arr_cap, m.bytes())) ||
         (frame && ((rc = ensure(c, (void **)&c->d_frame, &c->d_frame_cap, nfl * sizeof(float))) ||
                    (rc = xfer_h2d(c, c->d_frame, rgb, nfl * sizeof(float), c->stream)))) ||
-        (src && (rc = planes_up(c, *src, m.h))) || (tgt && (rc = planes_up(c, *tgt, m.h))) ||
+        (src && (rc = planes_up(c, *src, sh))) || (tgt && (rc = planes_up(c, *tgt, m.h))) ||
         (rc = dispatch(packed_frames(static_cast<const float *>(c->d_frame), nfl, 1, m.w, m.h), reinterpret_cast<uint64_t *>(c->d_arr),
                        StreamLaunch{c->stream, false})))
         return rc;
@@ -1183,12 +1185,13 @@ static int measure_frame_host(lumahip_ctx *c, const float *rgb, float sc, int pr
 // ... of the plane-fed calls (lumahip_transcode.hip): source planes and given planes
 static int measure_planes_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile, float src_sc,
                                const unsigned char *const given_planes[3], const int given_stride[3], int dst_profile, float dst_sc,
-                               const MeasureOut &m, uint64_t *out, size_t out_words)
+                               const MeasureOut &m, uint64_t *out, size_t out_words, const SourceSize *full = nullptr)
 {
     StagedPlanes src{"source ", src_planes, src_stride, src_profile}, given{"given ", given_planes, given_stride, dst_profile};
-    return measure_host(c, m, false, nullptr, &src, &given, true, nullptr, out, out_words, [&](const SrcFrames &, uint64_t *d, const StreamLaunch &o) {
-        return measure_planes_impl(c, src.dev(), src_sc, given.dev(), dst_sc, m, d, o);
-    });
+    return measure_host(
+        c, m, false, nullptr, &src, &given, true, nullptr, out, out_words,
+        [&](const SrcFrames &, uint64_t *d, const StreamLaunch &o) { return measure_planes_impl(c, src.dev(), src_sc, given.dev(), dst_sc, m, d, o, full); },
+        full);
 }
 
 // ... of the plane-to-plane calls (lumahip_planes_measure.hip): two plane sets of one profile; no quantizer is read
@@ -1246,6 +1249,27 @@ extern "C" int lumahip_transcode_moments_map_frame_host(lumahip_ctx *c, const un
 {
     return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, given_planes, given_stride, dst_profile, dst_sc,
                                {DistWhat::Moments, "transcode moments map", block, 1, w, h}, mom, mom_words);
+}
+
+// The two half-resolution calls (include/lumahip_ladder.h): w x h is the source's size, the given set and the words are of (w/2) x (h/2)
+extern "C" int lumahip_transcode_half_distortion_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                            int src_profile, float src_sc, unsigned w, unsigned h,
+                                                            const unsigned char *const given_planes[3], const int given_stride[3],
+                                                            int dst_profile, float dst_sc, uint64_t out[12])
+{
+    const SourceSize full{w, h, 2};
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, given_planes, given_stride, dst_profile, dst_sc,
+                               {DistWhat::Frame, "half-resolution transcode distortion", 0, 1, w / 2, h / 2}, out, 12, &full);
+}
+
+extern "C" int lumahip_transcode_half_distortion_map_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3],
+                                                                int src_profile, float src_sc, unsigned w, unsigned h,
+                                                                const unsigned char *const given_planes[3], const int given_stride[3],
+                                                                int dst_profile, float dst_sc, unsigned block, uint64_t *map, size_t map_words)
+{
+    const SourceSize full{w, h, 2};
+    return measure_planes_host(c, src_planes, src_stride, src_profile, src_sc, given_planes, given_stride, dst_profile, dst_sc,
+                               {DistWhat::Map, "half-resolution transcode distortion map", block, 1, w / 2, h / 2}, map, map_words, &full);
 }
 
 extern "C" int lumahip_planes_distortion_frame_host(lumahip_ctx *c, const unsigned char *const a_planes[3], const int a_stride[3], unsigned w,

@@ -6,8 +6,8 @@
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which instantiation of the fused kernels a launch takes: pick_enc<IN16> / pick_dec<OUT16> / pick_dist<IN16> /
-//                       pick_planes<TransFamily | TransHalfFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, VW>, included by the
-//                       kernel units below and by nothing else
+//                       pick_planes<TransFamily | TransHalfFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily |
+//                       TransHalfDistFamily | TransHalfDistMapFamily, VW>, included by the kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
 //                       tables next to the kernel that builds them
@@ -15,14 +15,17 @@
 //                       pick_enc_f16 / pick_dec_f16 to the two dispatch functions) and the _f16 device entry points (+ the
 //                       narrowing probe)
 //   lumahip_transcode.hip  pick_planes<TransFamily, .> (every k_transcode), transcode_plan -- what a launch over two plane sets may
-//                       be --, the transcode dispatch and its entry point; measure_planes_impl, the one dispatch of the three plane-fed
-//                       measuring calls, and their three _device entry points
+//                       be --, the transcode dispatch and its entry point; measure_planes_impl, the one dispatch of the five plane-fed
+//                       measuring calls, and their five _device entry points (two of them include/lumahip_ladder.h's)
 //   lumahip_transcode_half.hip  pick_planes<TransHalfFamily, .> (every k_transcode_half), the half-resolution transcode's dispatch
 //                       (transcode_plan with scale 2) and its _device entry point of include/lumahip_compare.h
 //   lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip  pick_planes<
 //                       TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, .> (every k_transcode_distortion /
 //                       k_transcode_distortion_map / k_transcode_moments_map), exported as pick_transdist / pick_transdist_map /
 //                       pick_transdist_moments_map; nothing else
+//   lumahip_transcode_half_distortion.hip / lumahip_transcode_half_distortion_map.hip  pick_planes<TransHalfDistFamily |
+//                       TransHalfDistMapFamily, .> (every k_transcode_half_distortion / k_transcode_half_distortion_map), exported as
+//                       pick_transhalf_dist / pick_transhalf_dist_map; nothing else
 //   lumahip_distortion.hip  pick_dist<DistFamily, false> (every float-frame k_distortion), distortion_plan -- what a launch that scores
 //                       given planes against frames may be --, measure_frames_impl, the one dispatch of the frame-fed measuring calls
 //                       (distortion, distortion map, moments map), their twelve _device entry points and the two *_map_dims
@@ -42,7 +45,7 @@
 //   closing launch (launch_measure), the launch options (StreamLaunch) and the entry helper (device_entry) stand beside it, once.
 //   lumahip_misc.hip    stand-alone transform, synthetic frames, the reference's mean luminance, probes, timing helper
 //   lumahip_host.hip    the _host entry points: staging, host <-> device transfers, the one 3-stage pipeline of the banded,
-//                       batched and stream push / pop forms, the one host form of the eleven measuring calls (measure_host)
+//                       batched and stream push / pop forms, the one host form of the thirteen measuring calls (measure_host)
 //                                                                                                         (no kernels)
 //   lumahip_pool.hip    the HBM chunk pool;  lumahip_multi.hip  many GPUs in one process                  (no kernels)
 #pragma once
@@ -64,6 +67,7 @@
 #include "../../include/lumahip.h"
 #include "../../include/lumahip_measure.h"
 #include "../../include/lumahip_compare.h"
+#include "../../include/lumahip_ladder.h"
 #include "luma_kernels.hpp"
 #include "host_lut.hpp"
 #include "lut_index.hpp"
@@ -500,6 +504,7 @@ struct MeasureOut {
 struct PlaneSet {
     const SrcPlanes &p;
     const char *pre = "", *post = "";
+    unsigned w = 0, h = 0;   // the set's own size where it is not the record's (the source set of the half-resolution calls); 0: the record's
 };
 // every set's three arrays (and whatever else the family wants non-null: others_given) -> "null argument"; then plane k of every set
 static inline int check_plane_sets(lumahip_ctx *c, std::initializer_list<PlaneSet> sets, bool others_given)
@@ -539,7 +544,7 @@ static inline int check_out_overlap(lumahip_ctx *c, const MeasureOut &m, const u
             return fail(c, LUMAHIP_ERR_ARG, "%s overlaps colour plane %d of the frames", m.out_name(), k);
         for (const PlaneSet &s : sets)
             if (ranges_overlap((uintptr_t)out, m.bytes(), (uintptr_t)s.p.planes[k],
-                               plane_extent(m.w, m.h, s.p.profile, k, s.p.stride[k], s.p.pfs[k], m.nframes)))
+                               plane_extent(s.w ? s.w : m.w, s.h ? s.h : m.h, s.p.profile, k, s.p.stride[k], s.p.pfs[k], m.nframes)))
                 return fail(c, LUMAHIP_ERR_ARG, "%s overlaps %splane %d%s", m.out_name(), s.pre, k, s.post);
     }
     return LUMAHIP_OK;
@@ -670,7 +675,9 @@ struct TranscodePlan {
     lh::MapGeom m;   // the two maps only
 };
 // m == nullptr, the storing transcode: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one),
-// out is ignored.  Else a measuring call and what it delivers (MeasureOut; its nframes, w, h are the arguments'): tgt are the given
+// out is ignored.  Else a measuring call and what it delivers (MeasureOut; its nframes, w, h are the target side's: the arguments', or
+// with scale 2 -- the half-resolution transcode distortion and its map -- w / 2 and h / 2, and the workgroup is then clamped to
+// lh::transhalfdist_threads_bound / lh::transhalfmap_threads_bound and the vector width held to lh::transhalfdist_vw4): tgt are the given
 // planes (read only: any overlap with the source is fine), out its words (non-null, 8-byte aligned, sharing no byte with either plane
 // set), the workgroup is clamped to the measuring kernels' launch bound -- the moments map's: to lh::transmoments_threads_bound in its
 // place -- and, the two maps, by the record's rule; their grid to the number of map tiles.  Every error is raised here, the block
@@ -715,10 +722,16 @@ map_kernel_t pick_dist_map_f32(int cs, bool sub, int vw, int mode), pick_dist_ma
 map_kernel_t pick_moments_map_f32(int cs, bool sub, int vw, int mode), pick_moments_map_f16(int cs, bool sub, int vw, int mode);
 
 // ---- lumahip_transcode.hip: the plane-fed measuring calls
-// The one dispatch of the three: the source planes' transcode (transcode_impl's planes, never written) against the given planes,
-// m.words() words at out; m carries nframes, w, h
+// The size of a measuring call's source set where it is not the record's: the half-resolution calls (scale 2), whose record and
+// given set are of (w / 2) x (h / 2)
+struct SourceSize {
+    unsigned w, h, scale;
+};
+// The one dispatch of the five: the source planes' transcode (transcode_impl's planes, never written) against the given planes,
+// m.words() words at out; m carries nframes, w, h.  full: the source's size of the two half-resolution calls, whose e is
+// transcode_half_impl's sample
 int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, const SrcPlanes &given, float dst_sc, const MeasureOut &m, uint64_t *out,
-                        const StreamLaunch &o);
+                        const StreamLaunch &o, const SourceSize *full = nullptr);
 // pick_planes<TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, vw> of lumahip_pick.hpp as lumahip_transcode_distortion.hip /
 // lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip export it (each compiles the 48 kernels it names)
 typedef void (*transdist_kernel_t)(const lh::TransDistArgs);
@@ -726,6 +739,10 @@ typedef void (*transdist_map_kernel_t)(const lh::TransDistMapArgs);
 transdist_kernel_t pick_transdist(int vw, int csd, bool subd, int cse, bool sube, int mode);
 transdist_map_kernel_t pick_transdist_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
 transdist_map_kernel_t pick_transdist_moments_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
+// pick_planes<TransHalfDistFamily | TransHalfDistMapFamily, vw> as lumahip_transcode_half_distortion.hip /
+// lumahip_transcode_half_distortion_map.hip export it (each compiles the kernels it names)
+transdist_kernel_t pick_transhalf_dist(int vw, int csd, bool subd, int cse, bool sube, int mode);
+transdist_map_kernel_t pick_transhalf_dist_map(int vw, int csd, bool subd, int cse, bool sube, int mode);
 
 // ---- lumahip_planes_measure.hip: two plane sets as they are (include/lumahip_compare.h)
 // e = the samples of set a, g = those of set b (one profile, which both sets carry), no quantizer read; m.words() words at out, m

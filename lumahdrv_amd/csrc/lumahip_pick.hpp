@@ -5,14 +5,16 @@
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
 // export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_planes<TransFamily, 4 | 2>,
-// lumahip_transcode_half.hip pick_planes<TransHalfFamily, 4 | 2>.  The nine measuring
+// lumahip_transcode_half.hip pick_planes<TransHalfFamily, 4 | 2>.  The eleven measuring
 // units take one picker each and export it to the two dispatch functions (measure_planes_impl, measure_frames_impl):
 // lumahip_transcode_distortion.hip pick_planes<TransDistFamily, 4 | 2> as pick_transdist; lumahip_transcode_distortion_map.hip
 // pick_planes<TransDistMapFamily, 4 | 2> as pick_transdist_map; lumahip_transcode_moments_map.hip pick_planes<TransMomentsMapFamily,
-// 4 | 2> as pick_transdist_moments_map; lumahip_distortion.hip / lumahip_distortion_f16.hip
+// 4 | 2> as pick_transdist_moments_map; lumahip_transcode_half_distortion.hip pick_planes<TransHalfDistFamily, 4 | 2> as
+// pick_transhalf_dist; lumahip_transcode_half_distortion_map.hip pick_planes<TransHalfDistMapFamily, 4 | 2> as pick_transhalf_dist_map;
+// lumahip_distortion.hip / lumahip_distortion_f16.hip
 // pick_dist<DistFamily, false / true> as pick_dist_f32 / _f16; lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip
 // pick_dist<DistMapFamily, false / true> as pick_dist_map_f32 / _f16; lumahip_moments_map.hip / lumahip_moments_map_f16.hip
-// pick_dist<MomentsMapFamily, false / true> as pick_moments_map_f32 / _f16.  Included by those fifteen units only.
+// pick_dist<MomentsMapFamily, false / true> as pick_moments_map_f32 / _f16.  Included by those seventeen units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -137,6 +139,31 @@ struct TransMomentsMapFamily {   // (launch bound: lh::transmoments_threads_boun
     using kernel_t = transdist_map_kernel_t;
     template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
     static kernel_t kernel() { return lh::k_transcode_moments_map<CSD, SUBD, CSE, SUBE, VW, LM>; }
+};
+// lh::k_transcode_half_distortion / lh::k_transcode_half_distortion_map, named by lumahip_transcode_half_distortion.hip /
+// lumahip_transcode_half_distortion_map.hip only (launch bounds: lh::transhalfdist_threads_bound / lh::transhalfmap_threads_bound, which
+// transcode_plan clamps the launch to).  The source families lh::transhalfdist_vw4 denies have no VW 4 kernel: the plan gives them VW 2
+struct TransHalfDistFamily {
+    using kernel_t = transdist_kernel_t;
+    template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+    static kernel_t kernel()
+    {
+        if constexpr (VW == 4 && !lh::transhalfdist_vw4(CSD, SUBD, CSE))
+            return nullptr;
+        else
+            return lh::k_transcode_half_distortion<CSD, SUBD, CSE, SUBE, VW, LM>;
+    }
+};
+struct TransHalfDistMapFamily {
+    using kernel_t = transdist_map_kernel_t;
+    template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+    static kernel_t kernel()
+    {
+        if constexpr (VW == 4 && !lh::transhalfdist_vw4(CSD, SUBD, CSE))
+            return nullptr;
+        else
+            return lh::k_transcode_half_distortion_map<CSD, SUBD, CSE, SUBE, VW, LM>;
+    }
 };
 
 // source colour space / subsampling, target colour space / subsampling, the target's search mode -- Lu'v': LUT_THRESH_LDS or

@@ -2,9 +2,9 @@
 // context's source quantizer -> code planes under its quantizer, no float frame between them.  Its own translation unit: the 48
 // kernels compile side by side with the encode and decode units, and no kernel is in two code objects.  Also the plan of every
 // launch over two plane sets (transcode_plan: the family's own part; what a measuring launch delivers and the checks every plan
-// shares are lumahip_internal.hpp's) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the three
+// shares are lumahip_internal.hpp's) and, beside it, the one dispatch (measure_planes_impl) and the entry points of the five
 // measuring calls over them, whose kernels lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip /
-// lumahip_transcode_moments_map.hip compile.
+// lumahip_transcode_moments_map.hip / lumahip_transcode_half_distortion.hip / lumahip_transcode_half_distortion_map.hip compile.
 #include "lumahip_internal.hpp"
 #include "lumahip_pick.hpp"
 
@@ -18,8 +18,9 @@ namespace lhost {
 // planes it writes; out = nullptr) and for the transcode distortion, the transcode distortion map and the transcode moments map (tgt =
 // the given planes they read, out = their words; what differs between the three -- blocks accepted, words, LDS to meet in -- is the
 // record's to say, the kernels' launch bound this plan's).  scale: 1, or 2 for the half-resolution transcode (lumahip_transcode_half.hip;
-// m == nullptr): w x h is the source's size, the target side is (w / scale) x (h / scale) -- its layout, its extents, its geometry
-// (p.e.g; p.d.g stays the source's), the vector width and the grid, which runs over the target's tiles.
+// m == nullptr) and for the half-resolution transcode distortion and its map (m built for w / 2 x h / 2): w x h is the source's size,
+// the target side is (w / scale) x (h / scale) -- its layout, its extents, its geometry (p.e.g; p.d.g stays the source's), the
+// vector width, the map's geometry and the grid, which runs over the target's tiles.
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
                    const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p, unsigned scale)
 {
@@ -49,7 +50,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                 if (ranges_overlap((uintptr_t)src.planes[i], plane_extent(w, h, src.profile, i, src.stride[i], src.pfs[i], nframes),
                                    (uintptr_t)tgt.planes[j], plane_extent(tw, th, tgt.profile, j, tgt.stride[j], tgt.pfs[j], nframes)))
                     return fail(c, LUMAHIP_ERR_ARG, "source plane %d and destination plane %d overlap over this batch", i, j);
-    } else if ((rc = m->check_out(c, out)) || (rc = check_out_overlap(c, *m, out, nullptr, {{src, "source "}, {tgt, "given "}}))) {
+    } else if ((rc = m->check_out(c, out)) || (rc = check_out_overlap(c, *m, out, nullptr, {{src, "source ", "", w, h}, {tgt, "given "}}))) {
         // (both plane sets are read only and may overlap each other; the words may not share a byte with anything the launch reads)
         return rc;
     }
@@ -88,6 +89,9 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.lds = lds;
     // four pixels per thread and row when every base and stride of both sides allows the vector accesses, else two
     p.vw = ((tw % 4) == 0 && planes_aligned(src, 4) && planes_aligned(tgt, 4)) ? 4 : 2;
+    // (the half-resolution measuring kernels of some source families exist at VW 2 only: lh::transhalfdist_vw4)
+    if (measure && scale == 2 && !transhalfdist_vw4(csd, p.subd, cse))
+        p.vw = 2;
     // as the encode dispatch; the half-resolution Lu'v' -> Lu'v' kernels always: at VW 4 they are compiled for three waves per SIMD,
     // which three 256-thread workgroups per CU fill and one 512-thread workgroup does not (profiles/transcode_half_launch_shapes.txt)
     const bool long_launch = scale == 2 || (unsigned long long)w * h * nframes >= 60000000ull;
@@ -95,10 +99,12 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
     // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
     // (the moments kernels: for lh::transmoments_threads_bound, the function their launch bound is written with)
-    p.threads = std::min(p.threads, moments   ? transmoments_threads_bound(csd, cse, p.vw)
-                                    : measure ? TransDistFamily::bound(any_y)
-                                    : scale == 2 ? transhalf_threads_bound(csd, cse, p.vw)
-                                                 : TransFamily::bound(any_y));
+    // (the half-resolution measuring kernels: for lh::transhalfdist_threads_bound / lh::transhalfmap_threads_bound, likewise)
+    p.threads = std::min(p.threads, moments                 ? transmoments_threads_bound(csd, cse, p.vw)
+                                    : measure && scale == 2 ? (map ? transhalfmap_threads_bound(csd, cse, p.vw) : transhalfdist_threads_bound(csd, cse, p.vw))
+                                    : measure               ? TransDistFamily::bound(any_y)
+                                    : scale == 2            ? transhalf_threads_bound(csd, cse, p.vw)
+                                                            : TransFamily::bound(any_y));
     if (map)
         p.threads = m->clamp_threads(p.threads);
     p.d = DecArgs{};
@@ -118,7 +124,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     p.e.aligned = planes_aligned(tgt, p.vw) ? 1 : 0;
     p.grid = grid_for(c, p.threads, p.e.g.totalTiles, 0, 0, any_y ? 1 : 0, true);
     if (map)
-        map_shape(*m, p.d.g, p.threads, p.m, p.grid);
+        map_shape(*m, p.e.g, p.threads, p.m, p.grid);   // (the target side's geometry: the record's size)
     return LUMAHIP_OK;
 }
 
@@ -153,14 +159,16 @@ int transcode_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
 }
 
 int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, const SrcPlanes &given, float dst_sc, const MeasureOut &m, uint64_t *out,
-                        const StreamLaunch &o)
+                        const StreamLaunch &o, const SourceSize *full)
 {
     TranscodePlan p;
-    if (int rc = transcode_plan(c, src, src_sc, m.nframes, m.w, m.h, given, dst_sc, &m, out, o.stream, p))
+    const bool half = full != nullptr;
+    if (int rc = transcode_plan(c, src, src_sc, m.nframes, half ? full->w : m.w, half ? full->h : m.h, given, dst_sc, &m, out, o.stream, p,
+                                half ? full->scale : 1))
         return rc;
     const auto no_kernel = [&] { return fail(c, LUMAHIP_ERR_UNSUPPORTED, "no %s kernel for colour spaces %d -> %d", m.call, p.csd, p.cse); };
     DecArgs g{};
-    g.g = p.d.g;
+    g.g = p.e.g;   // (the target side's geometry: the source's, or with `full` the half-size one)
     read_planes(g, given, p.vw);
     if (!m.map()) {
         TransDistArgs a{};
@@ -168,7 +176,7 @@ int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, cons
         a.e = p.e;
         a.g = g;
         a.out = out;
-        const transdist_kernel_t kern = pick_transdist(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
+        const transdist_kernel_t kern = (half ? pick_transhalf_dist : pick_transdist)(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
         return kern ? launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a) : no_kernel();
     }
     TransDistMapArgs a{};
@@ -177,8 +185,8 @@ int measure_planes_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, cons
     a.g = g;
     a.map = out;
     a.m = p.m;
-    const transdist_map_kernel_t kern =
-        (m.kind == DistWhat::Moments ? pick_transdist_moments_map : pick_transdist_map)(p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
+    const transdist_map_kernel_t kern = (m.kind == DistWhat::Moments ? pick_transdist_moments_map : half ? pick_transhalf_dist_map : pick_transdist_map)(
+        p.vw, p.csd, p.subd, p.cse, p.sube, p.kmode);
     return kern ? launch_measure(c, m, out, kern, p.grid, p.threads, p.lds, launch_stream(c, o.stream, o.lanes), a) : no_kernel();
 }
 
@@ -224,8 +232,8 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
     });
 }
 
-// The three plane-fed measuring entry points (include/lumahip.h and, for the moments map, include/lumahip_measure.h have their full
-// prototypes): MEASURE_PARAMS, then the call's own tail.
+// The five plane-fed measuring entry points (include/lumahip.h and, for the moments map, include/lumahip_measure.h, for the two
+// half-resolution calls include/lumahip_ladder.h have their full prototypes): MEASURE_PARAMS, then the call's own tail.
 #define MEASURE_PARAMS                                                                                                                      \
     const unsigned char *const src_planes[3], const int src_stride[3], const size_t src_pfs[3], int src_profile, float src_sc, unsigned nframes, \
         unsigned w, unsigned h, const unsigned char *const given_planes[3], const int given_stride[3], const size_t given_pfs[3], int dst_profile, \
@@ -233,6 +241,13 @@ extern "C" int lumahip_transcode_frames_device(lumahip_ctx *c, const unsigned ch
 #define CALL_Frame "transcode distortion"
 #define CALL_Map "transcode distortion map"
 #define CALL_Moments "transcode moments map"
+// (the half-resolution calls: the record is the half-size target's, w x h stays the source's)
+#define MEASURE_HALF(what, block, out)                                                                                                           \
+    device_entry(c, true, [&](const StreamLaunch &o) {                                                                                           \
+        const SourceSize full{w, h, 2};                                                                                                          \
+        return measure_planes_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, {given_planes, given_stride, given_pfs, dst_profile}, dst_sc, \
+                                   {DistWhat::what, "half-resolution " CALL_##what, block, nframes, w / 2, h / 2}, out, o, &full);               \
+    })
 #define MEASURE(what, block, out)                                                                                                                \
     device_entry(c, true, [&](const StreamLaunch &o) {                                                                                           \
         return measure_planes_impl(c, {src_planes, src_stride, src_pfs, src_profile}, src_sc, {given_planes, given_stride, given_pfs, dst_profile}, dst_sc, \
@@ -242,4 +257,6 @@ extern "C" {
 int lumahip_transcode_distortion_frames_device(lumahip_ctx *c, MEASURE_PARAMS, uint64_t *out_dev) { return MEASURE(Frame, 0, out_dev); }
 int lumahip_transcode_distortion_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return MEASURE(Map, block, map_dev); }
 int lumahip_transcode_moments_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *mom_dev) { return MEASURE(Moments, block, mom_dev); }
+int lumahip_transcode_half_distortion_frames_device(lumahip_ctx *c, MEASURE_PARAMS, uint64_t *out_dev) { return MEASURE_HALF(Frame, 0, out_dev); }
+int lumahip_transcode_half_distortion_map_frames_device(lumahip_ctx *c, MEASURE_PARAMS, unsigned block, uint64_t *map_dev) { return MEASURE_HALF(Map, block, map_dev); }
 }  // extern "C"
