@@ -219,6 +219,14 @@ _ABI_LADDER = {
 }
 LADDER_SYMBOLS = tuple(_ABI_LADDER)
 
+# The calls include/lumahip_rungs.h declares (the lower rungs of a ladder made from the source planes: the quarter-resolution
+# transcode), bound like _ABI's; tests/test_transcode_quarter_host.py holds this table and the header to each other.
+_ABI_RUNGS = {
+    "lumahip_transcode_quarter_frames_device": (_i, _TWO_SETS + (_vp,)),
+    "lumahip_transcode_quarter_frame_host": (_i, _TWO_SETS_HOST),
+}
+RUNGS_SYMBOLS = tuple(_ABI_RUNGS)
+
 
 class LumaHipError(RuntimeError):
     """Counterpart of the reference's LumaException (include/luma/luma_exception.h:53-71)."""
@@ -253,7 +261,8 @@ KERNEL_SOURCES = ("luma_device.hpp", "luma_kernels.hpp", "pow_glibc.hpp", "lumah
                   "lumahip_transcode_distortion.hip", "lumahip_distortion_map.hip", "lumahip_distortion_map_f16.hip",
                   "lumahip_transcode_distortion_map.hip", "lumahip_moments_map.hip", "lumahip_moments_map_f16.hip",
                   "lumahip_transcode_moments_map.hip", "lumahip_planes_measure.hip", "lumahip_light_level.hip",
-                  "lumahip_transcode_half.hip", "lumahip_transcode_half_distortion.hip", "lumahip_transcode_half_distortion_map.hip")
+                  "lumahip_transcode_half.hip", "lumahip_transcode_half_distortion.hip", "lumahip_transcode_half_distortion_map.hip",
+                  "lumahip_transcode_quarter.hip")
 
 
 def kernel_source_sha() -> str:
@@ -286,7 +295,8 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()) + list(_ABI_COMPARE.items()) + list(_ABI_LADDER.items()):
+    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_MEASURE.items()) + list(_ABI_COMPARE.items()) + list(_ABI_LADDER.items()) + \
+            list(_ABI_RUNGS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, list(argtypes)
     _lib = L
@@ -732,6 +742,19 @@ class Context:
                                                            _arr3(C.c_int, st), dst_profile, dst_sc))
         return out, st
 
+    def transcode_quarter_frame(self, planes, strides, w, h, src_sc=1.0, src_profile=2, dst_sc=1.0, dst_profile=2, align=32, dst_strides=None):
+        """code planes of w x h under the source quantizer -> (planes, strides) of (w/4) x (h/4) under the quantizer, averaged 2x2
+        in linear light twice with nothing quantized in between, one fused launch; w and h multiples of 8"""
+        planes = [np.ascontiguousarray(p) for p in planes]
+        _, hs, st, _ = plane_geometry(w // 4, h // 4, dst_profile, align)
+        if dst_strides is not None:
+            st = tuple(dst_strides)
+        out = [np.zeros((hs[p], st[p]), dtype=np.uint8) for p in range(3)]
+        self._chk(self.L.lumahip_transcode_quarter_frame_host(self.h, _arr3(C.c_void_p, [p.ctypes.data for p in planes]), _arr3(C.c_int, strides),
+                                                              src_profile, src_sc, w, h, _arr3(C.c_void_p, [p.ctypes.data for p in out]),
+                                                              _arr3(C.c_int, st), dst_profile, dst_sc))
+        return out, st
+
     def distortion_frame(self, rgb: np.ndarray, planes, strides, sc=1.0, profile=2) -> np.ndarray:
         """rgb: (3,h,w) float32; planes: the given code planes as three (rows, stride) uint8 arrays.  Returns a (3, 4) uint64 array:
         per plane {sse, sad, max_abs, n_differ} of the planes encode_frame would write against the given ones"""
@@ -924,6 +947,12 @@ class Context:
     def transcode_half_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
                                      dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr=None):
         self._two_sets(self.L.lumahip_transcode_half_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile,
+                       src_sc, nframes, w, h, dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr)
+
+    # w, h: the SOURCE size; the destination planes hold (w/4) x (h/4) luma samples (the 2x2 box twice, on floats; include/lumahip_rungs.h)
+    def transcode_quarter_frames_device(self, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile, src_sc, nframes, w, h,
+                                        dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr=None):
+        self._two_sets(self.L.lumahip_transcode_quarter_frames_device, src_plane_ptrs, src_strides, src_plane_frame_strides, src_profile,
                        src_sc, nframes, w, h, dst_plane_ptrs, dst_strides, dst_plane_frame_strides, dst_profile, dst_sc, stats_ptr)
 
     # distortion of given planes against the frames' own encode: out_ptr receives nframes x 3 planes x {sse, sad, max_abs, n_differ}

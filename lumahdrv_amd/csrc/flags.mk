@@ -16,6 +16,8 @@ FLAGS_lumahip_encode_f16 := $(FLAGS_lumahip_encode)
 FLAGS_lumahip_transcode :=
 #   lumahip_transcode_half: the transcode unit's -- k_transcode_half is k_transcode with four source units folded into one target unit.
 FLAGS_lumahip_transcode_half := $(FLAGS_lumahip_transcode)
+#   lumahip_transcode_quarter: the same -- k_transcode_quarter is k_transcode_half with sixteen source units folded into one target unit.
+FLAGS_lumahip_transcode_quarter := $(FLAGS_lumahip_transcode)
 #   lumahip_transcode_distortion: the transcode unit's -- its kernels are k_transcode's front end with the measuring consumer.
 FLAGS_lumahip_transcode_distortion := $(FLAGS_lumahip_transcode)
 #   lumahip_transcode_distortion_map: the same -- k_transcode_distortion_map is k_transcode_distortion with the accumulation in space.

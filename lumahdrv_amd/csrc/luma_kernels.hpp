@@ -1622,6 +1622,210 @@ void k_transcode_half(const TransArgs a)
         stats_flush(st, a.e.stats, tx);
 }
 
+// ---- QUARTER-RESOLUTION TRANSCODE -------------------------------------------------------------------
+// k_transcode_half's 2x2 box applied twice to floats, nothing quantized between the two: the target planes hold (w/4) x (h/4) luma
+// samples, target pixel (X, Y) is M = ((m[2Y][2X] + m[2Y][2X+1]) + (m[2Y+1][2X] + m[2Y+1][2X+1])) * 0.25f of the half-size means m
+// k_transcode_half encodes -- fp32, this association, nothing contracted -- and the planes are what the encode writes for M.  a.d.g is
+// the source's geometry (w x h), a.e.g the target's (w/4 x h/4); the loop runs over the target's tiles (half_locate).  A thread owns
+// the target unit (ux, uy), VW pixels x 2 rows, and fills it from the sixteen source units (4ux + i, 4uy + j), i, j in 0..3: source
+// unit (i, j) gives the VW/2 means from i * VW/2 on of m's row 4uy + j, which belongs to target row j >> 1 as its upper (j even) or
+// lower (j odd) row of means.  Per lane and row the source reads are four adjacent VW-sample pieces whatever the order of the walk, so
+// a wave reads contiguous memory.  w and h are multiples of 8 and VW == 4 only when w/4 is a multiple of 4 (transcode_plan), so the
+// source has exactly four times the target's units both ways: the sixteen are in range whenever the target unit is.
+//
+// The walk is a loop that is NOT unrolled, over the 2 * VW target pixels of the unit: step k fills pixel k % VW of row k / VW from
+// the source units under it -- VW 4: two, each one's two means a pair-sum, (m00 + m01) from the upper and (m10 + m11) from the lower;
+// VW 2: four, one mean each, upper left, upper right, lower left, lower right -- which are decoded one at a time and folded in the
+// spec's association; M goes into its place in u.in by selects (the step is wave-uniform, the unit stays in registers).  Unrolled,
+// the sixteen copies of the decode arithmetic (twice that for a YCbCr source) made a unit of 5.3 M listing lines whose kernels
+// sat at the register cap of every budget (profiles/transcode_quarter_codegen.txt); the loop's body is k_transcode_half's size.  Slot e of step k is source unit (quarter_i, quarter_j).
+template <int VW>
+constexpr int quarter_slots()
+{
+    return VW == 4 ? 2 : 4;
+}
+template <int VW>
+LH_DEV int quarter_i(int k, int e)
+{
+    return VW == 4 ? k % VW : 2 * (k % VW) + (e & 1);
+}
+template <int VW>
+LH_DEV int quarter_j(int k, int e)
+{
+    return 2 * (k / VW) + (VW == 4 ? e : e >> 1);
+}
+
+// How many of a step's slots are loaded ahead (the others are loaded where they are decoded): a slot loaded ahead is refilled with
+// the next step's unit right behind its own decode, so that the load runs under the decodes that follow, and after the last step
+// with the first step's unit of the thread's next target unit, behind this one's stores.  From the register report
+// (profiles/transcode_quarter_codegen.txt): a 4:2:0 source unit is VW * 3 registers, a 4:4:4 one VW * 6, and all of a step's slots
+// fit beside the target unit (6 * VW floats) and one decoded unit -- except a 4:4:4 source at VW 2, whose four units ahead (48
+// registers) left the four Lu'v' -> Lu'v' kernels 32 B of scratch under their 128 registers: those sources load the upper two ahead.
+template <bool SUBD, int VW>
+constexpr int quarter_prefetch()
+{
+    return (VW == 2 && !SUBD) ? 2 : quarter_slots<VW>();
+}
+
+// Budget, one function pair of (CSD, CSE, VW) which the kernel's __launch_bounds__ / amdgpu_waves_per_eu are written with and
+// transcode_plan clamps the launch to: transhalf_*'s values, which the resource report (profiles/transcode_quarter_codegen.txt) gives
+// no reason to move -- the live set is k_transcode_half's plus the step and the sums of the pixel in progress.  With YCbCr on either
+// side 512 threads and two waves per SIMD (256 registers for the fp64 powf chains); Lu'v' -> Lu'v' at VW 4 512 threads and three waves
+// (168 registers); at VW 2 k_transcode's 1024 threads and four waves (128).
+constexpr int transquarter_threads_bound(int csd, int cse, int vw) { return transhalf_threads_bound(csd, cse, vw); }
+constexpr int transquarter_waves(int csd, int cse, int vw) { return transhalf_waves(csd, cse, vw); }
+
+// the loads of the slots of step k of target unit (f, ux, uy) that are loaded ahead
+template <bool SUBD, int VW, int NPF>
+LH_DEV void quarter_issue(DecUnit<SUBD, VW> (&pf)[NPF], const DecArgs &a, int f, int ux, int uy, int k = 0)
+{
+#pragma unroll
+    for (int e = 0; e < NPF; e++)
+        dec_load_at<SUBD, VW>(pf[e], a, f, 4 * ux + quarter_i<VW>(k, e), 4 * uy + quarter_j<VW>(k, e));
+}
+
+// slot E of step k of target unit (f, ux, uy) -- loaded ahead (E < NPF; then refilled for step k + 1) or loaded here -- decoded: its
+// VW/2 half-size means per channel, k_transcode_half's
+template <int E, int CSD, bool SUBD, int VW, bool UVTAB, bool YT, bool SCFAST, int NPF, typename K>
+LH_DEV void quarter_means(float (&m)[3][VW / 2], DecUnit<SUBD, VW> (&pf)[NPF], const DecArgs &a, const K &kd, const float *s_lut, const float *s_uv, int f,
+                          int ux, int uy, int k)
+{
+    DecUnit<SUBD, VW> du;
+    if constexpr (E < NPF)
+        du = pf[E];
+    else
+        dec_load_at<SUBD, VW>(du, a, f, 4 * ux + quarter_i<VW>(k, E), 4 * uy + quarter_j<VW>(k, E));
+    float v[3][2][VW];
+    dec_values<CSD, SUBD, VW, UVTAB, YT, SCFAST>(du, a, kd, s_lut, s_uv, v);
+    if constexpr (E < NPF)
+        if (k + 1 < 2 * VW)   // (wave-uniform)
+            dec_load_at<SUBD, VW>(pf[E], a, f, 4 * ux + quarter_i<VW>(k + 1, E), 4 * uy + quarter_j<VW>(k + 1, E));
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int p = 0; p < VW / 2; p++)
+            m[c][p] = ((v[c][0][2 * p] + v[c][0][2 * p + 1]) + (v[c][1][2 * p] + v[c][1][2 * p + 1])) * 0.25f;
+}
+
+// the sixteen source units of a target unit, step by step: at most one decoded unit is live beside the target unit
+template <int CSD, bool SUBD, int VW, bool UVTAB, bool YT, bool SCFAST, int NPF, typename K>
+LH_DEV void quarter_fill(EncUnit<VW> &u, DecUnit<SUBD, VW> (&pf)[NPF], const DecArgs &a, const K &kd, const float *s_lut, const float *s_uv, int f, int ux,
+                         int uy)
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+        for (int q = 0; q < 2 * VW; q++)
+            u.in[c][q / VW][q % VW] = 0.0f;
+#pragma unroll 1
+    for (int k = 0; k < 2 * VW; k++) {
+        float M[3];
+        if constexpr (VW == 4) {
+            float up[3][2], lo[3][2];
+            quarter_means<0, CSD, SUBD, VW, UVTAB, YT, SCFAST>(up, pf, a, kd, s_lut, s_uv, f, ux, uy, k);
+            float ps[3];   // the upper pair-sums wait for the lower ones
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                ps[c] = up[c][0] + up[c][1];
+            quarter_means<1, CSD, SUBD, VW, UVTAB, YT, SCFAST>(lo, pf, a, kd, s_lut, s_uv, f, ux, uy, k);
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                M[c] = (ps[c] + (lo[c][0] + lo[c][1])) * 0.25f;
+        } else {
+            float m0[3][1], m1[3][1];
+            quarter_means<0, CSD, SUBD, VW, UVTAB, YT, SCFAST>(m0, pf, a, kd, s_lut, s_uv, f, ux, uy, k);
+            quarter_means<1, CSD, SUBD, VW, UVTAB, YT, SCFAST>(m1, pf, a, kd, s_lut, s_uv, f, ux, uy, k);
+            float ps[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                ps[c] = m0[c][0] + m1[c][0];
+            quarter_means<2, CSD, SUBD, VW, UVTAB, YT, SCFAST>(m0, pf, a, kd, s_lut, s_uv, f, ux, uy, k);
+            quarter_means<3, CSD, SUBD, VW, UVTAB, YT, SCFAST>(m1, pf, a, kd, s_lut, s_uv, f, ux, uy, k);
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                M[c] = (ps[c] + (m0[c][0] + m1[c][0])) * 0.25f;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+#pragma unroll
+            for (int q = 0; q < 2 * VW; q++)
+                u.in[c][q / VW][q % VW] = q == k ? M[c] : u.in[c][q / VW][q % VW];
+    }
+}
+
+// k_transcode_quarter: k_transcode_half's tables, statistics and loop order -- the loads of the first steps of the next target unit's
+// walk are issued after the current unit's stores
+template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+__global__ __launch_bounds__(transquarter_threads_bound(CSD, CSE, VW)) __attribute__((amdgpu_waves_per_eu(transquarter_waves(CSD, CSE, VW))))
+void k_transcode_quarter(const TransArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using Front = PlaneFront<CSD, CSE, LM>;
+    stage_tables<Front::WHAT_D, Front::WHAT_E>(smem, a.d.q, a.e.q);
+    constexpr int off = lds_table_offset<Front::WHAT_D | Front::WHAT_E>();
+    const float *s_lut = reinterpret_cast<const float *>(smem + off);
+    const float *s_uv = reinterpret_cast<const float *>(smem + off + lds_lut_bytes(a.d.q));   // u'v' table, or y table + chroma terms
+    const uint32_t *s_rec = reinterpret_cast<const uint32_t *>(smem + off + lds_quant_bytes<Front::WHAT_D>(a.d.q));
+    const PowfTablesWide *pw = reinterpret_cast<const PowfTablesWide *>(smem);
+    const XformConst kd = make_xform_const<CSD>(a.d.sc, a.d.q.Lmax, pw);
+    const XformConst ke = make_xform_const<CSE>(a.e.sc, a.e.q.Lmax, pw);
+
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int NW = blockDim.x >> 6;
+    const int G = gridDim.x;
+    constexpr int NPF = quarter_prefetch<SUBD, VW>();
+
+    EncStats st;
+
+    DecUnit<SUBD, VW> pf[NPF];
+    int f = 0, ux = 0, uy = 0;
+    bool valid = half_locate(a.e.g, blockIdx.x, tx, ty, NW, f, ux, uy);
+    if (valid)
+        quarter_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+    for (int t = blockIdx.x; t < a.e.g.totalTiles; t += G) {
+        if (a.e.stats) {
+            const int tf = t / a.e.g.tilesPerFrame;  // wave-uniform
+            if (tf != st.frame) {
+                stats_flush(st, a.e.stats, tx);
+                st.frame = tf;
+            }
+        }
+        if (valid) {
+            EncUnit<VW> u;
+            if constexpr (Front::YD) {
+                // two copies of the decode arithmetic, chosen by a kernel argument, as in k_decode
+                if (kd.sc_mode == 1)
+                    quarter_fill<CSD, SUBD, VW, false, true, true>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+                else
+                    quarter_fill<CSD, SUBD, VW, false, true, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            } else {
+                quarter_fill<CSD, SUBD, VW, true, false, false>(u, pf, a.d, kd, s_lut, s_uv, f, ux, uy);
+            }
+            float c0[2 * VW], c1[2 * VW], c2[2 * VW];
+            enc_transform<CSE, VW, Front::YE, false, !Front::YE>(u, a.e, ke, c0, c1, c2, st);
+            if constexpr (Front::YE) {
+                // the luminance statistics of a YCbCr target, only for a launch that asks for them (k_transcode says why)
+                if (a.e.stats) {
+#pragma unroll
+                    for (int j = 0; j < 2 * VW; j++) {
+                        const float lum = pq_decode(div_ieee(c0[j], 255.0f), ke);
+                        st.sum += lum;
+                        st.mn = fminf(st.mn, lum);
+                        st.mx = fmaxf(st.mx, lum);
+                    }
+                }
+            }
+            // (the tile, and with it the frame, is wave-uniform: saying so keeps the planes' frame offsets scalar)
+            enc_emit<CSE, SUBE, VW, LM>(__builtin_amdgcn_readfirstlane(f), ux, uy, c0, c1, c2, a.e, static_cast<const float *>(nullptr), s_rec);   // (record searches: no table pointer)
+        }
+        valid = half_locate(a.e.g, t + G, tx, ty, NW, f, ux, uy);
+        if (valid)
+            quarter_issue<SUBD, VW>(pf, a.d, f, ux, uy);
+    }
+    if (a.e.stats)
+        stats_flush(st, a.e.stats, tx);
+}
+
 // The decoded-and-transformed channel 0 of one frame, pixel by pixel with the complete functions (the array the reference's
 // sequential mean sums, k_seq_sum): only for the host call's rare exact mean (lumahip_transcode_frame_host).
 struct TransChan0Args {

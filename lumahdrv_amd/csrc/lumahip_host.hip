@@ -1013,7 +1013,7 @@ struct StagedPlanes {
 // quantizer (src = nullptr: frames in, one set; tgt = nullptr too: a frame alone, quantizers = false), the layouts, d_planes large
 // enough for [src][tgt].  quantizers = false: the sets are taken as they are (the plane-to-plane measures, the light level of a
 // frame), neither quantizer is asked for.  tgt_scale 2 (the half-resolution transcode): w and h are multiples of 4 and the set `tgt`
-// is laid out at (w/2) x (h/2)
+// is laid out at (w/2) x (h/2); tgt_scale 4 (the quarter-resolution transcode): multiples of 8, and (w/4) x (h/4)
 static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *src, StagedPlanes *tgt, bool quantizers = true, unsigned tgt_scale = 1)
 {
     int rc = quantizers ? check_geom(c, w, h, tgt->profile, c->q.cs) : check_size(c, w, h);
@@ -1023,6 +1023,8 @@ static int planes_staging(lumahip_ctx *c, unsigned w, unsigned h, StagedPlanes *
         return rc;
     if (tgt_scale == 2 && ((w | h) & 3))
         return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (half resolution: must be multiples of 4)", w, h);
+    if (tgt_scale == 4 && ((w | h) & 7))
+        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (quarter resolution: must be multiples of 8)", w, h);
     if (src && (src->profile < 0 || src->profile > 3))
         return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src->profile);
     if (quantizers && src && !c->src.have)
@@ -1132,6 +1134,28 @@ extern "C" int lumahip_transcode_half_frame_host(lumahip_ctx *c, const unsigned 
     if ((rc = planes_up(c, src, h)) ||
         (rc = transcode_half_impl(c, src.dev(), src_sc, 1, w, h, {dst.dp, dst_stride, NO_PFS, dst_profile}, dst_sc, nullptr, {c->stream, false})) ||
         (rc = planes_d2h(c, dst_planes, dst.dp, dst_stride, dst.L, 0, h / 2, c->stream, false)))
+        return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LUMAHIP_OK;
+}
+
+// The same at quarter resolution (lumahip_transcode_quarter_frames_device, include/lumahip_rungs.h): the destination set is staged and
+// downloaded at (w/4) x (h/4).  No mean_lum, as above.
+extern "C" int lumahip_transcode_quarter_frame_host(lumahip_ctx *c, const unsigned char *const src_planes[3], const int src_stride[3], int src_profile,
+                                                    float src_sc, unsigned w, unsigned h, unsigned char *const dst_planes[3], const int dst_stride[3],
+                                                    int dst_profile, float dst_sc)
+{
+    if (!c)
+        return LUMAHIP_ERR_ARG;
+    if (!src_planes || !src_stride || !dst_planes || !dst_stride)
+        return fail(c, LUMAHIP_ERR_ARG, "null argument");
+    StagedPlanes src{"source ", src_planes, src_stride, src_profile}, dst{"destination ", dst_planes, dst_stride, dst_profile};
+    int rc = planes_staging(c, w, h, &src, &dst, true, 4);
+    if (rc)
+        return rc;
+    if ((rc = planes_up(c, src, h)) ||
+        (rc = transcode_quarter_impl(c, src.dev(), src_sc, 1, w, h, {dst.dp, dst_stride, NO_PFS, dst_profile}, dst_sc, nullptr, {c->stream, false})) ||
+        (rc = planes_d2h(c, dst_planes, dst.dp, dst_stride, dst.L, 0, h / 4, c->stream, false)))
         return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return LUMAHIP_OK;

@@ -6,7 +6,7 @@
 //   lumahip_tables.hpp  what those tables are made of: owning device buffer, process-wide host cache, per-context LRU
 //   lumahip_launch.hip  launch geometry: LDS bytes, threads per workgroup, persistent workgroups per CU   (no kernels)
 //   lumahip_pick.hpp    which instantiation of the fused kernels a launch takes: pick_enc<IN16> / pick_dec<OUT16> / pick_dist<IN16> /
-//                       pick_planes<TransFamily | TransHalfFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily |
+//                       pick_planes<TransFamily | TransHalfFamily | TransQuarterFamily | TransDistFamily | TransDistMapFamily | TransMomentsMapFamily |
 //                       TransHalfDistFamily | TransHalfDistMapFamily, VW>, included by the kernel units below and by nothing else
 //   lumahip_encode.hip  pick_enc<false> (every float-frame k_encode), the encode dispatch, the other encode-side kernels
 //   lumahip_decode.hip  pick_dec<false> (every float-frame k_decode), the decode dispatch, the array kernels, the red / blue
@@ -19,6 +19,8 @@
 //                       measuring calls, and their five _device entry points (two of them include/lumahip_ladder.h's)
 //   lumahip_transcode_half.hip  pick_planes<TransHalfFamily, .> (every k_transcode_half), the half-resolution transcode's dispatch
 //                       (transcode_plan with scale 2) and its _device entry point of include/lumahip_compare.h
+//   lumahip_transcode_quarter.hip  pick_planes<TransQuarterFamily, .> (every k_transcode_quarter), the quarter-resolution transcode's
+//                       dispatch (transcode_plan with scale 4) and its _device entry point of include/lumahip_rungs.h
 //   lumahip_transcode_distortion.hip / lumahip_transcode_distortion_map.hip / lumahip_transcode_moments_map.hip  pick_planes<
 //                       TransDistFamily | TransDistMapFamily | TransMomentsMapFamily, .> (every k_transcode_distortion /
 //                       k_transcode_distortion_map / k_transcode_moments_map), exported as pick_transdist / pick_transdist_map /
@@ -68,6 +70,7 @@
 #include "../../include/lumahip_measure.h"
 #include "../../include/lumahip_compare.h"
 #include "../../include/lumahip_ladder.h"
+#include "../../include/lumahip_rungs.h"
 #include "luma_kernels.hpp"
 #include "host_lut.hpp"
 #include "lut_index.hpp"
@@ -671,11 +674,12 @@ struct TranscodePlan {
     bool subd, sube, any_y;
     size_t lds;      // dynamic LDS of the launch (the measuring kernels' words are static and counted in the budget)
     lh::DecArgs d;   // q, g, src, stride, src_frame_stride, sc, bps, aligned of the source planes
-    lh::EncArgs e;   // q (the composite records for kmode 5), g (d's; scale 2: of the half-size target), sc, bps, aligned of the target side
+    lh::EncArgs e;   // q (the composite records for kmode 5), g (d's; scale 2 / 4: of the half-size / quarter-size target), sc, bps, aligned of the target side
     lh::MapGeom m;   // the two maps only
 };
 // m == nullptr, the storing transcode: tgt are the planes lumahip_transcode_frames_device writes (no source plane may overlap one),
-// out is ignored.  Else a measuring call and what it delivers (MeasureOut; its nframes, w, h are the target side's: the arguments', or
+// out is ignored; scale 2 or 4: the half- / quarter-resolution transcode, tgt of (w / scale) x (h / scale), the workgroup clamped to
+// lh::transhalf_threads_bound / lh::transquarter_threads_bound.  Else a measuring call and what it delivers (MeasureOut; its nframes, w, h are the target side's: the arguments', or
 // with scale 2 -- the half-resolution transcode distortion and its map -- w / 2 and h / 2, and the workgroup is then clamped to
 // lh::transhalfdist_threads_bound / lh::transhalfmap_threads_bound and the vector width held to lh::transhalfdist_vw4): tgt are the given
 // planes (read only: any overlap with the source is fine), out its words (non-null, 8-byte aligned, sharing no byte with either plane
@@ -688,6 +692,10 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
 // source planes of w x h -> destination planes of (w/2) x (h/2): the 2x2 box in linear light between the decode and the encode
 int transcode_half_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
                         float *stats, const StreamLaunch &o);
+// ---- lumahip_transcode_quarter.hip: pick_planes<TransQuarterFamily, .> (every k_transcode_quarter), the dispatch and its entry point
+// source planes of w x h -> destination planes of (w/4) x (h/4): the 2x2 box in linear light twice, on floats, between the decode and the encode
+int transcode_quarter_impl(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const DstPlanes &dst, float dst_sc,
+                           float *stats, const StreamLaunch &o);
 // the decoded and colour-transformed channel 0 of ONE frame (w*h floats at out_dev), with the complete per-pixel functions
 int transcode_channel0(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned w, unsigned h, float dst_sc, float *out_dev, hipStream_t s);
 

@@ -1,11 +1,12 @@
 // lumahip_pick.hpp -- which instantiation of the fused kernels (lh::k_encode / k_decode / k_transcode / k_distortion /
 // k_distortion_map / k_moments_map / k_transcode_distortion / k_transcode_distortion_map / k_transcode_moments_map, luma_kernels.hpp)
-// a launch takes (and of k_transcode_half).
+// a launch takes (and of k_transcode_half and k_transcode_quarter).
 // Naming a kernel here instantiates it, so this file decides which kernels exist, and the translation unit that instantiates
 // a picker is the one that compiles its kernels: lumahip_encode.hip / lumahip_decode.hip take pick_enc<false> / pick_dec<false>
 // (float frames), lumahip_encode_f16.hip / lumahip_decode_f16.hip take pick_enc<true> / pick_dec<true> (binary16 frames) and
 // export them as pick_enc_f16 / pick_dec_f16; lumahip_transcode.hip takes pick_planes<TransFamily, 4 | 2>,
-// lumahip_transcode_half.hip pick_planes<TransHalfFamily, 4 | 2>.  The eleven measuring
+// lumahip_transcode_half.hip pick_planes<TransHalfFamily, 4 | 2>, lumahip_transcode_quarter.hip pick_planes<TransQuarterFamily, 4 | 2>.
+// The eleven measuring
 // units take one picker each and export it to the two dispatch functions (measure_planes_impl, measure_frames_impl):
 // lumahip_transcode_distortion.hip pick_planes<TransDistFamily, 4 | 2> as pick_transdist; lumahip_transcode_distortion_map.hip
 // pick_planes<TransDistMapFamily, 4 | 2> as pick_transdist_map; lumahip_transcode_moments_map.hip pick_planes<TransMomentsMapFamily,
@@ -14,7 +15,7 @@
 // lumahip_distortion.hip / lumahip_distortion_f16.hip
 // pick_dist<DistFamily, false / true> as pick_dist_f32 / _f16; lumahip_distortion_map.hip / lumahip_distortion_map_f16.hip
 // pick_dist<DistMapFamily, false / true> as pick_dist_map_f32 / _f16; lumahip_moments_map.hip / lumahip_moments_map_f16.hip
-// pick_dist<MomentsMapFamily, false / true> as pick_moments_map_f32 / _f16.  Included by those seventeen units only.
+// pick_dist<MomentsMapFamily, false / true> as pick_moments_map_f32 / _f16.  Included by those eighteen units only.
 #pragma once
 #include "lumahip_internal.hpp"
 
@@ -122,6 +123,11 @@ struct TransHalfFamily {   // lh::k_transcode_half, named by lumahip_transcode_h
     using kernel_t = trans_kernel_t;
     template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
     static kernel_t kernel() { return lh::k_transcode_half<CSD, SUBD, CSE, SUBE, VW, LM>; }
+};
+struct TransQuarterFamily {   // lh::k_transcode_quarter, named by lumahip_transcode_quarter.hip only (launch bound: lh::transquarter_threads_bound, which transcode_plan clamps the launch to)
+    using kernel_t = trans_kernel_t;
+    template <int CSD, bool SUBD, int CSE, bool SUBE, int VW, int LM>
+    static kernel_t kernel() { return lh::k_transcode_quarter<CSD, SUBD, CSE, SUBE, VW, LM>; }
 };
 struct TransDistFamily {
     using kernel_t = transdist_kernel_t;

@@ -20,7 +20,8 @@ namespace lhost {
 // record's to say, the kernels' launch bound this plan's).  scale: 1, or 2 for the half-resolution transcode (lumahip_transcode_half.hip;
 // m == nullptr) and for the half-resolution transcode distortion and its map (m built for w / 2 x h / 2): w x h is the source's size,
 // the target side is (w / scale) x (h / scale) -- its layout, its extents, its geometry (p.e.g; p.d.g stays the source's), the
-// vector width, the map's geometry and the grid, which runs over the target's tiles.
+// vector width, the map's geometry and the grid, which runs over the target's tiles.  scale 4: the quarter-resolution transcode
+// (lumahip_transcode_quarter.hip; m == nullptr only: no measuring call takes it), the same with (w / 4) x (h / 4).
 int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned nframes, unsigned w, unsigned h, const SrcPlanes &tgt, float dst_sc,
                    const MeasureOut *m, const uint64_t *out, hipStream_t stream, TranscodePlan &p, unsigned scale)
 {
@@ -34,6 +35,8 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
         return rc;
     if (scale == 2 && ((w | h) & 3))
         return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (half resolution: must be multiples of 4)", w, h);
+    if (scale == 4 && ((w | h) & 7))
+        return fail(c, LUMAHIP_ERR_ARG, "Invalid frame size %ux%u (quarter resolution: must be multiples of 8)", w, h);
     const unsigned tw = w / scale, th = h / scale;   // the target side's size
     if (src.profile < 0 || src.profile > 3)
         return fail(c, LUMAHIP_ERR_ARG, "source profile must be 0..3 (got %d)", src.profile);
@@ -93,8 +96,10 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
     if (measure && scale == 2 && !transhalfdist_vw4(csd, p.subd, cse))
         p.vw = 2;
     // as the encode dispatch; the half-resolution Lu'v' -> Lu'v' kernels always: at VW 4 they are compiled for three waves per SIMD,
-    // which three 256-thread workgroups per CU fill and one 512-thread workgroup does not (profiles/transcode_half_launch_shapes.txt)
-    const bool long_launch = scale == 2 || (unsigned long long)w * h * nframes >= 60000000ull;
+    // which three 256-thread workgroups per CU fill and one 512-thread workgroup does not (profiles/transcode_half_launch_shapes.txt);
+    // the quarter-resolution ones, compiled for the same, likewise: 0.170 ms in three 256-thread workgroups per CU against 0.215 - 0.255 in
+    // every other shape swept at 8 x 4K (profiles/transcode_quarter_launch_shapes.txt)
+    const bool long_launch = scale != 1 || (unsigned long long)w * h * nframes >= 60000000ull;
     p.threads = block_threads_for(c, lds, long_launch && !any_y, any_y);
     // the measuring kernels are compiled for at most lh::TransDistBound threads (512 with YCbCr on either side, which is what the
     // rule above gives those pairs unless the tables or lumahip_tune "block" ask for more)
@@ -104,6 +109,7 @@ int transcode_plan(lumahip_ctx *c, const SrcPlanes &src, float src_sc, unsigned 
                                     : measure && scale == 2 ? (map ? transhalfmap_threads_bound(csd, cse, p.vw) : transhalfdist_threads_bound(csd, cse, p.vw))
                                     : measure               ? TransDistFamily::bound(any_y)
                                     : scale == 2            ? transhalf_threads_bound(csd, cse, p.vw)
+                                    : scale == 4            ? transquarter_threads_bound(csd, cse, p.vw)
                                                             : TransFamily::bound(any_y));
     if (map)
         p.threads = m->clamp_threads(p.threads);
